@@ -14,8 +14,15 @@ GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 import onepose_amd  # noqa: E402
 
 # before any test module makes a HIP call: four frames in flight want a hardware queue each (runtime.py; opt-in since round 6 --
-# importing the package no longer touches the environment, tests/test_module_api.py::test_import_has_no_process_wide_side_effect)
-onepose_amd.configure_hip_queues()
+# importing the package no longer touches the environment, tests/test_module_api.py::test_import_has_no_process_wide_side_effect).
+# The suite runs on the package's pool: an inherited GPU_MAX_HW_QUEUES that leaves no queue per frame in flight (the HIP default of 4
+# included) is raised to it, where configure_hip_queues() would keep the caller's value.
+try:
+    _inherited_pool = int(os.environ.get("GPU_MAX_HW_QUEUES", ""))
+except ValueError:
+    _inherited_pool = 0
+if _inherited_pool <= onepose_amd.runtime.FRAMES_IN_FLIGHT:
+    os.environ["GPU_MAX_HW_QUEUES"] = str(onepose_amd.runtime.HW_QUEUES)
 
 
 def pytest_configure(config):

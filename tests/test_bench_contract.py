@@ -1,9 +1,10 @@
-"""bench.py prints exactly one JSON line with the driver's contract keys (plus roofline / cpu_baseline objects)."""
+"""bench.py prints exactly one JSON line with the driver's contract keys (plus, with --full, roofline / cpu_baseline objects)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -25,7 +26,7 @@ def run(*flags, env=None):
 
 @gpu
 def test_default_line_contract():
-    d = run("--steps", "6", "--warmup", "2", "--no-cpu-baseline")
+    d = run("--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline")
     assert REQUIRED <= set(d) and d["metric"] == "query_frames_per_sec" and d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32"
     assert d["value"] > 100 and "workload" in d["config"] and "model" not in d["config"]
@@ -63,10 +64,80 @@ def test_default_line_contract():
         assert pt["conf_of_planted_pairs_min_max"][1] > 0.9
 
 
+
+@gpu
+def test_plain_line_times_exactly_the_asked_steps_and_dumps_outputs(tmp_path, bench_golden_meta):
+    """A plain run (no --full) times exactly --steps steps once and carries none of the --full extras; --dump-outputs writes what the
+    timed path computed in its last step, the same bits from run to run, and on the golden frame it is the reference's own output."""
+    d = run("--steps", "6", "--warmup", "2")
+    assert REQUIRED <= set(d) and d["metric"] == "query_frames_per_sec" and d["steps"] == 6 and d["warmup"] == 2 and d["dtype"] == "f32"
+    c = d["config"]
+    assert c["timed_pass_repetitions"] == 1 and len(c["timed_pass_seconds"]) == 1 and c["discarded_first_pass_seconds"] is None
+    assert abs(d["ms_per_step"] - c["timed_pass_seconds"][0] / 6 * 1e3) < 1e-2 and d["value"] > 100
+    assert not {"roofline", "cpu_baseline", "parity_check", "parity_check_trained_weights"} & set(d)
+    assert not {"single_frame_latency_ms", "module_forward_frames_per_sec", "other_gemm_arithmetics", "other_baseline_configs"} & set(c)
+    # --steps 1: the last (only) step is pool frame 0, the inputs of the reference-run golden head_rand
+    dumps = []
+    for rep in range(2):
+        out = tmp_path / f"dump{rep}"
+        run("--steps", "1", "--warmup", "1", "--dump-outputs", str(out))
+        a = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert set(a) == {"conf_matrix", "matches0", "matches1", "matching_scores0", "matching_scores1"}
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20 and all(v.dtype in (np.float32, np.float64) for v in a.values())
+        assert a["conf_matrix"].shape == (1, 1000, 7000) and a["matches0"].shape == (1, 1000) and a["matching_scores1"].shape == (1, 7000)
+        dumps.append(a)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)
+    g, sub = np.load(os.path.join(ROOT, "tests", "golden", "bench_head_rand.npz")), bench_golden_meta["cases"]["head_rand"]["sub"]
+    cm = dumps[0]["conf_matrix"]
+    assert np.abs(cm[:, ::sub[0], ::sub[1]] - g["conf_sub"]).max() < 1e-4 and np.abs(cm.max(2) - g["conf_rowmax"]).max() < 1e-4
+    assert (cm.argmax(2) == g["indices0_raw"]).all() and (cm.argmax(1) == g["indices1_raw"]).all()
+
+
+def test_plain_dry_run_line_is_one_pass_without_the_full_legs():
+    """Without --full the line is one K-step pass: no discarded first pass, no BASELINE configs[2] / configs[4] legs (CPU stand-in steps)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    d = run("--gpus", "2", "--dry-run", "--steps", "10", "--warmup", "1", env=env)
+    assert d["n_gpus"] == 2 and d["steps"] == 10 and "other_baseline_configs" not in d["config"]
+    assert d["ms_per_step"] >= 2.0                 # a stub step sleeps 2 ms
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--dump-outputs", "x"], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT, env=env)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+
+
+def test_dump_outputs_writes_the_callers_arrays_within_the_limit(tmp_path):
+    """bench.dump_outputs: pred and conf_matrix as float32 / float64 .npy; a conf_matrix beyond the limit becomes a fixed, seeded sample
+    of whole rows, the same rows every time, with their flat indices."""
+    import types
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    b, n1, n2 = 2, 60, 300
+    fake = types.SimpleNamespace(conf=torch.rand(b, n1, n2, generator=g), m0=torch.randint(-1, n2, (b, n1), generator=g),
+                                 m1=torch.randint(-1, n1, (b, n2), generator=g), s0=torch.rand(b, n1, generator=g), s1=torch.rand(b, n2, generator=g))
+    bench.dump_outputs(fake, str(tmp_path / "whole"))
+    a = {f[:-4]: np.load(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole")}
+    assert set(a) == {"conf_matrix", "matches0", "matches1", "matching_scores0", "matching_scores1"}
+    np.testing.assert_array_equal(a["conf_matrix"], fake.conf.numpy())
+    np.testing.assert_array_equal(a["matches1"], fake.m1.numpy())
+    assert a["matches1"].dtype == np.float64 and a["matching_scores0"].dtype == np.float32
+    limit = (1 << 20) + 60 * 1024
+    for rep in ("s0", "s1"):
+        bench.dump_outputs(fake, str(tmp_path / rep), limit=limit)
+    files = sorted(os.listdir(tmp_path / "s0"))
+    assert files == sorted(os.listdir(tmp_path / "s1")) and "conf_matrix.npy" not in files
+    assert sum(os.path.getsize(tmp_path / "s0" / f) for f in files) <= limit
+    rows, idx = np.load(tmp_path / "s0" / "conf_matrix_rows.npy"), np.load(tmp_path / "s0" / "conf_matrix_row_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < b * n1 and rows.shape == (len(idx), n2) and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(rows, fake.conf.numpy().reshape(b * n1, n2)[idx.astype(np.int64)])
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "s0" / f), np.load(tmp_path / "s1" / f))
+
 @gpu
 def test_split_bf16_batch8_line():
     """BASELINE configs[2]: its own line, dtype bf16x3, priced against the bf16 peak, never the headline metric config."""
-    d = run("--config", "bf16x3-b8", "--steps", "4", "--warmup", "1", "--reps", "2", "--no-cpu-baseline")
+    d = run("--full", "--config", "bf16x3-b8", "--steps", "4", "--warmup", "1", "--reps", "2", "--no-cpu-baseline")
     assert d["dtype"] == "bf16x3" and d["config"]["batch"] == 8 and d["config"]["name"] == "bf16x3-b8"
     pc = d["parity_check"]          # the mode's own measured tolerance: conf within 1e-4, a handful of near-tie flips in 64000
     assert d["roofline"]["peak"] > 2000 and pc["max_abs_conf_err"] < 1e-4 and pc["argmax_flips"] <= 8 and pc["argmax_checked"] == 64000
@@ -75,7 +146,7 @@ def test_split_bf16_batch8_line():
 @gpu
 def test_bf16x6_batch8_is_the_bit_exact_configs2_line():
     """The configs[2] line that meets north_star's index rule: six-term split, zero arg-max flips against the reference golden."""
-    d = run("--config", "bf16x6-b8", "--steps", "4", "--warmup", "1", "--reps", "2", "--no-cpu-baseline")
+    d = run("--full", "--config", "bf16x6-b8", "--steps", "4", "--warmup", "1", "--reps", "2", "--no-cpu-baseline")
     assert d["dtype"] == "bf16x6" and d["config"]["batch"] == 8 and "configs[2]" in d["config"]["workload"]
     pc = d["parity_check"]
     assert pc["max_abs_conf_err"] < 1e-4 and pc["argmax_flips"] == 0 and pc["argmax_checked"] == 64000
@@ -87,7 +158,7 @@ def test_launched_under_torchrun_world1_runs_the_rccl_path():
     --gpus 1` initialises the nccl (= RCCL) process group, runs the barrier pairs and the device-tensor all_gather the 8-GPU
     job uses, and its value agrees with the un-launched run of the same protocol (the driver's 'N=1 SCALE agrees with BENCH')."""
     import socket
-    flags = ["--gpus", "1", "--steps", "40", "--warmup", "10", "--no-cpu-baseline", "--no-side-arithmetics"]
+    flags = ["--full", "--gpus", "1", "--steps", "40", "--warmup", "10", "--no-cpu-baseline", "--no-side-arithmetics"]
     plain = run(*flags)
     assert plain["config"]["process_group"] is None
     s = socket.socket()
@@ -115,7 +186,7 @@ def test_gpus_n_launches_n_ranks_by_itself():
     """`python bench.py --gpus 2` without a torchrun environment spawns 2 ranks (here: CPU stand-in steps over gloo) and
     rank 0 prints one line with n_gpus 2; a WORLD_SIZE that contradicts --gpus is refused, never silently used."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    d = run("--gpus", "2", "--dry-run", "--steps", "10", "--warmup", "1", "--reps", "2", env=env)
+    d = run("--full", "--gpus", "2", "--dry-run", "--steps", "10", "--warmup", "1", "--reps", "2", env=env)
     assert d["n_gpus"] == 2 and d["data"] == "dry-run" and len(d["config"]["per_rank_frames_per_sec"]) == 2
     assert d["config"]["ranks_seen"] == 2 and len(set(d["config"]["rank_devices"])) == 2   # two ranks, two distinct "devices" (processes)
     # the BASELINE configs[2] / configs[4] legs of the default line run on EVERY rank (their passes hold barriers, their rates one all_gather)
@@ -147,7 +218,7 @@ def test_configs2_invocation_dry_run():
 def test_trained_weights_config_line():
     """`--config trained`: the headline shape on TRAINED weights; its parity_check compares conf values of O(1) and the thresholded
     matches with the reference's own output (tests/golden/trained_head.npz)."""
-    d = run("--config", "trained", "--steps", "6", "--warmup", "2", "--reps", "2", "--no-cpu-baseline")
+    d = run("--full", "--config", "trained", "--steps", "6", "--warmup", "2", "--reps", "2", "--no-cpu-baseline")
     pc = d["parity_check"]
     assert "trained_head" in pc["against"] and pc["max_abs_conf_err"] < 1e-4 and pc["argmax_flips"] == 0
     assert pc["conf_of_planted_pairs_min_max"][1] > 0.9 and pc["max_abs_conf_err_on_planted_pairs"] < 1e-4
@@ -198,7 +269,7 @@ def test_cpu_baseline_legs():
 def test_hbm_kernels_report_an_hbm_roofline():
     """--kernel gats / conf_finalize: bytes / time against the 8 TB/s HBM peak, not flops against the matrix peak."""
     for k in ("gats", "conf_finalize"):
-        d = run("--kernel", k, "--steps", "6", "--warmup", "2", "--reps", "2", "--no-cpu-baseline", "--no-side-arithmetics")
+        d = run("--full", "--kernel", k, "--steps", "6", "--warmup", "2", "--reps", "2", "--no-cpu-baseline", "--no-side-arithmetics")
         rf = d["roofline"]
         assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and rf["peak"] == 8000.0 and 0.1 < rf["frac"] < 1.0, rf
         assert rf["algorithmic_bytes_per_launch"] > 5e7 and rf["traffic"] >= rf["algorithmic_bytes_per_launch"] * 0.9

@@ -28,7 +28,7 @@ for spec in a.settings:
     for kv in filter(None, spec.split(",")):
         k, v = kv.split("=")
         env[("SPP_" if a.extractor else "GATSSPG_") + k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--tuning-lib", "--steps", a.steps, "--warmup", "10", "--reps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--tuning-lib", "--steps", a.steps, "--warmup", "10", "--reps", "3",
            "--no-cpu-baseline"]
     cmd += ["--extractor"] if a.extractor else ["--config", a.config, "--kernel", a.kernel]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)

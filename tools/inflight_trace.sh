@@ -2,7 +2,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/r04h; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 60 --warmup 8 --reps 1 --no-cpu-baseline --no-side-arithmetics --streams 4"
+B="python $R/bench.py --full --steps 60 --warmup 8 --reps 1 --no-cpu-baseline --no-side-arithmetics --streams 4"
 rocprofv3 --kernel-trace --stats -d $O/prof_s4 -o r -- $B > $O/prof_s4.log 2>&1
 rocprofv3 --kernel-trace --stats -d $O/prof_s4_fp16x4 -o r -- $B --config fp16x4 > $O/prof_s4_fp16x4.log 2>&1
 for d in prof_s4 prof_s4_fp16x4; do python $R/tools/rocpd_stats.py $(find $O/$d -name "*.db" | head -1) > $O/kernel_stats_$d.txt 2>&1; done

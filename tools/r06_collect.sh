@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 PART=${1:-tests}; TAG=${2:-r06}
 O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
-PROF="--reps 1 --min-timed-seconds 0 --no-cpu-baseline --no-side-arithmetics"
+PROF="--full --reps 1 --min-timed-seconds 0 --no-cpu-baseline --no-side-arithmetics"
 CONFIGS="headline fp16x4 fp32-b8 fp16x4-b8 stress-b4 fp16x4-stress-b4"
 steps_of() { case $1 in *stress-b4) echo 6;; *b8) echo 10;; *) echo 50;; esac; }
 case $PART in
@@ -20,15 +20,15 @@ tests)
   python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -3 $O/smoke.log
   ;;
 lines)
-  python bench.py > $O/bench_headline.json 2> $O/bench_headline.err
-  python bench.py --steps 20 --warmup 5 > $O/bench_headline_driver_protocol.json 2>/dev/null
-  python bench.py --amortised --no-cpu-baseline --no-side-arithmetics > $O/bench_amortised.json 2>/dev/null
+  python bench.py --full > $O/bench_headline.json 2> $O/bench_headline.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_headline_driver_protocol.json 2>/dev/null
+  python bench.py --full --amortised --no-cpu-baseline --no-side-arithmetics > $O/bench_amortised.json 2>/dev/null
   for c in fp16x4 fp16x4-b8 bf16x6 bf16x6-b8 fp16x3 bf16x3 fp32-b8 real real-b8 fp16x4-real fp16x4-real-b8 stress-b4 fp16x4-stress-b4 trained fp16x4-trained trained-hard; do
     steps=100; [[ $c == *b8* || $c == *stress* ]] && steps=20
-    python bench.py --config $c --steps $steps --warmup 5 --no-cpu-baseline > $O/bench_config_$c.json 2>/dev/null
+    python bench.py --full --config $c --steps $steps --warmup 5 --no-cpu-baseline > $O/bench_config_$c.json 2>/dev/null
   done
-  python bench.py --kernel gats --no-cpu-baseline --no-side-arithmetics > $O/bench_kernel_gats_hbm_roofline.json 2>/dev/null
-  python bench.py --kernel conf_finalize --no-cpu-baseline --no-side-arithmetics > $O/bench_kernel_conf_finalize_hbm_roofline.json 2>/dev/null
+  python bench.py --full --kernel gats --no-cpu-baseline --no-side-arithmetics > $O/bench_kernel_gats_hbm_roofline.json 2>/dev/null
+  python bench.py --full --kernel conf_finalize --no-cpu-baseline --no-side-arithmetics > $O/bench_kernel_conf_finalize_hbm_roofline.json 2>/dev/null
   python bench.py --extractor --no-cpu-baseline > $O/spp_bench_extractor.json 2>/dev/null
   python bench.py --extractor --extractor-precision fp16x4 --no-cpu-baseline > $O/spp_bench_extractor_fp16x4.json 2>/dev/null
   python bench.py --pipeline --matcher-precision fp16x4 --extractor-precision fp16x4 > $O/pipeline_bench_fp16x4_both_stages.json 2>/dev/null

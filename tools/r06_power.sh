@@ -7,7 +7,7 @@ cd $R
 (rocm-smi --showmaxpower; rocm-smi --showpower --showclocks --showperflevel; amd-smi static --limit 2>/dev/null | head -30) > $O/smi_idle.txt 2>&1
 sample() {   # $1 tag, rest: bench flags
   tag=$1; shift
-  python bench.py "$@" --warmup 20 --reps 2 --no-cpu-baseline --no-side-arithmetics > $O/bench_$tag.json 2>/dev/null &
+  python bench.py --full "$@" --warmup 20 --reps 2 --no-cpu-baseline --no-side-arithmetics > $O/bench_$tag.json 2>/dev/null &
   BP=$!
   : > $O/smi_$tag.txt
   while kill -0 $BP 2>/dev/null; do

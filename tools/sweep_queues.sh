@@ -9,7 +9,7 @@ for c in $CS; do
 for q in $QS; do
 for s in $SS; do
   if [ $q = default ]; then unset GPU_MAX_HW_QUEUES; else export GPU_MAX_HW_QUEUES=$q; fi
-  python bench.py --config $c --steps 150 --warmup 20 --reps 3 --no-cpu-baseline --no-side-arithmetics --streams $s 2>/dev/null | python -c "
+  python bench.py --full --config $c --steps 150 --warmup 20 --reps 3 --no-cpu-baseline --no-side-arithmetics --streams $s 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ out=gpurun_out/sweep_streams.log
 : > $out
 for s in 1 2 3 4 6 8; do
   echo "== streams=$s" >> $out
-  python bench.py --steps 200 --warmup 20 --no-cpu-baseline --streams $s 2>/dev/null | python -c "
+  python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --streams $s 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
