@@ -1,0 +1,64 @@
+"""ctypes binding of libsuperglue_hip.so (C ABI declared in include/superglue/superglue.h).
+
+Built in-tree by ``python -m onepose_amd.build_ext`` (hipcc, gfx950).  No fallback: if the shared
+object is missing, ``load()`` raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_size_t, c_void_p
+
+from ._native import NativeError
+from .build_ext import SG_LIB_PATH as LIB_PATH
+
+LAYER_SELF, LAYER_CROSS = 0, 1
+
+
+def num_raw(n_layers):
+    """Float tensors of the reference state_dict (num_batches_tracked skipped): SG_NUM_RAW."""
+    return 29 + 16 * n_layers
+
+
+_P = c_void_p
+# name -> (restype, argtypes); every symbol include/superglue/superglue.h declares
+SYMBOLS = {
+    "sg_version": (c_int, []),
+    "sg_last_error": (c_char_p, []),
+    "sg_packed_weights_bytes": (c_size_t, [c_int]),
+    "sg_pack_weights": (c_int, [POINTER(c_void_p), c_int, _P, _P]),
+    "sg_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sg_forward": (c_int, [_P, c_int, POINTER(c_int32), c_int, c_float, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                           c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sg_keypoint_encode": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
+                                   c_size_t, _P]),
+    "sg_layer": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "sg_sinkhorn": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "sg_match_tail": (c_int, [_P, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
+_lib = None
+
+
+def load():
+    """dlopen the HIP library and bind every entry point.  Raises if it has not been built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise NativeError(
+            f"{LIB_PATH} is missing: the SuperGlue HIP extension has not been built "
+            "(run `python -m onepose_amd.build_ext`; needs hipcc).  There is no CPU / PyTorch fallback.")
+    lib = ctypes.CDLL(LIB_PATH)
+    for name, (restype, argtypes) in SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _lib = lib
+    return lib
+
+
+def check(rc, what):
+    if rc != 0:
+        msg = load().sg_last_error()
+        raise NativeError(f"{what} failed: {msg.decode() if msg else 'unknown error'}")

@@ -1,5 +1,5 @@
-"""Build libgatsspg_hip.so (matcher), libspp_hip.so (SuperPoint extractor) and libpnp_hip.so (RANSAC-EPnP) in-tree with hipcc for gfx950
-(cross-compiles without a GPU).
+"""Build libgatsspg_hip.so (matcher), libspp_hip.so (SuperPoint extractor), libpnp_hip.so (RANSAC-EPnP) and libsuperglue_hip.so
+(SuperGlue 2D-2D matcher) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m onepose_amd.build_ext [--force] [--remarks] [--profiling] [--tuning]
 
@@ -26,6 +26,10 @@ SPP_HEADERS = ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", os.path.jo
 PNP_LIB_PATH = os.path.join(LIB_DIR, "libpnp_hip.so")
 PNP_SOURCES = ["pnp_kernels.hip"]
 PNP_HEADERS = [os.path.join("..", "..", "include", "pnp.h")]
+# the SuperGlue sources live in csrc/superglue/ and include/superglue/: source_hash() (top-level files only) does not see them
+SG_LIB_PATH = os.path.join(LIB_DIR, "libsuperglue_hip.so")
+SG_SOURCES = [os.path.join("superglue", "superglue.hip")]
+SG_HEADERS = [os.path.join("..", "..", "include", "superglue", "superglue.h")]
 
 
 def _hipcc():
@@ -44,7 +48,7 @@ def _stale(lib, deps):
 
 def is_stale():
     return (_stale(LIB_PATH, SOURCES + HEADERS) or _stale(SPP_LIB_PATH, SPP_SOURCES + SPP_HEADERS)
-            or _stale(PNP_LIB_PATH, PNP_SOURCES + PNP_HEADERS))
+            or _stale(PNP_LIB_PATH, PNP_SOURCES + PNP_HEADERS) or _stale(SG_LIB_PATH, SG_SOURCES + SG_HEADERS))
 
 
 def source_hash():
@@ -66,14 +70,14 @@ def tuning_path(lib):
 
 
 def build(force=False, remarks=False, verbose=True, profiling=False, tuning=False, syntax_only=False):
-    """Compile every HIP source for gfx950 into onepose_amd/lib/lib{gatsspg,spp,pnp}_hip.so.
+    """Compile every HIP source for gfx950 into onepose_amd/lib/lib{gatsspg,spp,pnp,superglue}_hip.so.
     tuning / profiling builds go to lib*_tuning.so (environment knobs; profiling adds -DGATSSPG_PROFILING_BUILD: timing-only
     ablation variants + the mlp0 timeline hook) -- the package never loads those.  syntax_only: front-end check only."""
     os.makedirs(LIB_DIR, exist_ok=True)
     special = tuning or profiling
     for lib, srcs, deps in ((LIB_PATH, SOURCES, SOURCES + HEADERS), (SPP_LIB_PATH, SPP_SOURCES, SPP_SOURCES + SPP_HEADERS),
-                            (PNP_LIB_PATH, PNP_SOURCES, PNP_SOURCES + PNP_HEADERS)):
-        if special and lib == PNP_LIB_PATH:
+                            (PNP_LIB_PATH, PNP_SOURCES, PNP_SOURCES + PNP_HEADERS), (SG_LIB_PATH, SG_SOURCES, SG_SOURCES + SG_HEADERS)):
+        if special and lib in (PNP_LIB_PATH, SG_LIB_PATH):     # no tuning knobs
             continue
         out = tuning_path(lib) if special else lib
         if not force and not syntax_only and not _stale(out, deps):

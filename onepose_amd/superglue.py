@@ -1,0 +1,278 @@
+"""MI355X-native SuperGlue 2D-2D matcher: host-side mirror of the reference module.
+
+Drop-in for ``src/models/matchers/SuperGlue/superglue.py::SuperGlue`` (reference :173-276): same constructor
+(``SuperGlue(config)``, the reference ``default_config`` merged with ``config``), same submodule tree and
+``state_dict`` keys (``superglue_outdoor.pth`` loads with ``strict=True``), same ``forward(data) -> dict`` contract.
+Every stage runs as hand-written HIP kernels behind the C ABI of ``include/superglue/superglue.h``; the
+modules below are parameter containers.  There is no PyTorch compute path and no CPU fallback.
+Inference only: BatchNorm uses its running statistics and ``forward`` in training mode raises.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _native_sg
+from ._native import NativeError
+from .superpoint import _on_device, _stream
+
+D = 256
+HEADS = 4
+KENC_LAYERS = [32, 64, 128, 256]
+
+
+def _mlp(channels):
+    """Conv1d(k=1) + BatchNorm1d + ReLU between every pair of widths, a bare Conv1d last (reference MLP layout, :47-59)."""
+    mods = []
+    for i in range(1, len(channels)):
+        mods.append(nn.Conv1d(channels[i - 1], channels[i], kernel_size=1, bias=True))
+        if i < len(channels) - 1:
+            mods += [nn.BatchNorm1d(channels[i]), nn.ReLU()]
+    return nn.Sequential(*mods)
+
+
+class _KeypointEncoder(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.encoder = _mlp([3] + KENC_LAYERS + [D])
+
+
+class _MultiHeadedAttention(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.merge = nn.Conv1d(D, D, kernel_size=1)
+        self.proj = nn.ModuleList([nn.Conv1d(D, D, kernel_size=1) for _ in range(3)])
+
+
+class _AttentionalPropagation(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.attn = _MultiHeadedAttention()
+        self.mlp = _mlp([2 * D, 2 * D, D])
+
+
+class _AttentionalGNN(nn.Module):
+    def __init__(self, names):
+        super().__init__()
+        self.layers = nn.ModuleList([_AttentionalPropagation() for _ in names])
+        self.names = list(names)
+
+
+def _check(t, name, dev):
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a tensor")
+    if t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, expected {dev}")
+    return t.to(torch.float32).contiguous()
+
+
+class SuperGlueEngine:
+    """Raw-tensor entry to the HIP matcher of one module: packed weights once per weight version and device, workspaces
+    cached per (shape, device, stream) so one module serves several streams at once.  Outputs may be preallocated
+    (``out=``) by callers that keep frames in flight."""
+
+    def __init__(self, module):
+        self.module = module
+        self.lib = _native_sg.load()
+        self._packed = None
+        self._packed_key = None
+        self._packed_event = None
+        self._packed_stream = None
+        self._ws = {}
+
+    def _raw(self):
+        """(module, name) of every float tensor of the state_dict in its order, read through getattr on every call."""
+        m = self.module
+        return [getattr(sub, name) for sub, name in m._raw_slots]
+
+    def packed_weights(self, device):
+        raw = self._raw()
+        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in raw)
+        if self._packed is not None and key == self._packed_key:
+            cur = torch.cuda.current_stream(device)
+            if cur.cuda_stream != self._packed_stream:
+                cur.wait_event(self._packed_event)
+            return self._packed
+        if self._packed is not None:
+            torch.cuda.synchronize(self._packed.device)    # nobody may still read the blob dropped below
+        for p in raw:
+            if not p.is_cuda:
+                raise RuntimeError(f"onepose_amd.SuperGlue runs only on a ROCm GPU (a parameter is on {p.device}); "
+                                   "there is no CPU fallback -- move the module to the GPU")
+        keep = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in raw]
+        n_layers = self.module.n_layers
+        ptrs = (ctypes.c_void_p * len(keep))(*[k.data_ptr() for k in keep])
+        packed = torch.empty(self.lib.sg_packed_weights_bytes(n_layers) // 4, device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            _native_sg.check(self.lib.sg_pack_weights(ptrs, n_layers, packed.data_ptr(), _stream(device)), "sg_pack_weights")
+            self._packed_event = torch.cuda.Event()
+            self._packed_event.record(torch.cuda.current_stream(device))
+            self._packed_stream = torch.cuda.current_stream(device).cuda_stream
+        self._packed, self._packed_key = packed, key
+        return packed
+
+    def workspace(self, b, n0, n1, device):
+        key = (b, n0, n1, str(device), torch.cuda.current_stream(device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = self.lib.sg_workspace_bytes(b, n0, n1)
+            if nbytes == 0:
+                raise NativeError(f"sg_workspace_bytes({b}, {n0}, {n1}) refused the shape")
+            if len(self._ws) >= 6:
+                self._ws.clear()
+            ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
+            self._ws[key] = ws
+        return ws
+
+    @staticmethod
+    def outputs(b, n0, n1, device):
+        """(matches0 int64 [b,n0], matches1 int64 [b,n1], matching_scores0 [b,n0], matching_scores1 [b,n1])."""
+        return (torch.empty(b, n0, device=device, dtype=torch.int64), torch.empty(b, n1, device=device, dtype=torch.int64),
+                torch.empty(b, n0, device=device, dtype=torch.float32), torch.empty(b, n1, device=device, dtype=torch.float32))
+
+    @_on_device
+    def forward(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1, out=None, z_out=None):
+        """kpts [b,n,2], scores [b,n], desc [b,256,n] on one GPU; hw = (H, W) of each image.  Returns the four outputs."""
+        dev = kpts0.device
+        k0, s0, d0 = _check(kpts0, "keypoints0", dev), _check(scores0, "scores0", dev), _check(desc0, "descriptors0", dev)
+        k1, s1, d1 = _check(kpts1, "keypoints1", dev), _check(scores1, "scores1", dev), _check(desc1, "descriptors1", dev)
+        b, n0, n1 = k0.shape[0], k0.shape[1], k1.shape[1]
+        if d0.shape != (b, D, n0) or d1.shape != (b, D, n1) or s0.shape != (b, n0) or s1.shape != (b, n1) or k1.shape[0] != b:
+            raise ValueError("inconsistent shapes: keypoints [b,n,2], scores [b,n], descriptors [b,256,n] with one b")
+        cfg = self.module.config
+        ws = self.workspace(b, n0, n1, dev)
+        m0, m1, ms0, ms1 = out if out is not None else self.outputs(b, n0, n1, dev)
+        if z_out is not None and (z_out.shape != (b, n0 + 1, n1 + 1) or z_out.dtype != torch.float32 or not z_out.is_contiguous()):
+            raise ValueError("z_out must be a contiguous fp32 [b, n0+1, n1+1] tensor")
+        kinds = (ctypes.c_int32 * max(1, self.module.n_layers))(*self.module.layer_kinds)
+        _native_sg.check(self.lib.sg_forward(
+            self.packed_weights(dev).data_ptr(), self.module.n_layers, kinds, int(cfg["sinkhorn_iterations"]),
+            float(cfg["match_threshold"]), k0.data_ptr(), s0.data_ptr(), d0.data_ptr(), k1.data_ptr(), s1.data_ptr(), d1.data_ptr(),
+            b, n0, n1, int(hw0[0]), int(hw0[1]), int(hw1[0]), int(hw1[1]), m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(),
+            ms1.data_ptr(), z_out.data_ptr() if z_out is not None else None, ws.data_ptr(), ws.numel(), _stream(dev)), "sg_forward")
+        return m0, m1, ms0, ms1
+
+    # ---- stages (tests) ----
+    @_on_device
+    def keypoint_encode(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1):
+        dev = kpts0.device
+        t = [_check(x, "input", dev) for x in (kpts0, scores0, desc0, kpts1, scores1, desc1)]
+        b, n0, n1 = t[0].shape[0], t[0].shape[1], t[3].shape[1]
+        ws = self.workspace(b, n0, n1, dev)
+        o0, o1 = torch.empty_like(t[2]), torch.empty_like(t[5])
+        _native_sg.check(self.lib.sg_keypoint_encode(
+            self.packed_weights(dev).data_ptr(), self.module.n_layers, *[x.data_ptr() for x in t], b, n0, n1, int(hw0[0]),
+            int(hw0[1]), int(hw1[0]), int(hw1[1]), o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+            "sg_keypoint_encode")
+        return o0, o1
+
+    @_on_device
+    def layer(self, index, desc0, desc1):
+        dev = desc0.device
+        d0, d1 = _check(desc0, "desc0", dev), _check(desc1, "desc1", dev)
+        b, n0, n1 = d0.shape[0], d0.shape[2], d1.shape[2]
+        ws = self.workspace(b, n0, n1, dev)
+        o0, o1 = torch.empty_like(d0), torch.empty_like(d1)
+        _native_sg.check(self.lib.sg_layer(
+            self.packed_weights(dev).data_ptr(), self.module.n_layers, index, self.module.layer_kinds[index], d0.data_ptr(),
+            d1.data_ptr(), b, n0, n1, o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "sg_layer")
+        return o0, o1
+
+    @_on_device
+    def sinkhorn(self, scores, bin_score, iters):
+        dev = scores.device
+        sc = _check(scores, "scores", dev)
+        alpha = _check(torch.as_tensor(bin_score, dtype=torch.float32, device=dev).reshape(1), "bin_score", dev)
+        b, n0, n1 = sc.shape
+        ws = self.workspace(b, n0, n1, dev)
+        z = torch.empty(b, n0 + 1, n1 + 1, device=dev, dtype=torch.float32)
+        _native_sg.check(self.lib.sg_sinkhorn(sc.data_ptr(), alpha.data_ptr(), b, n0, n1, int(iters), z.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), _stream(dev)), "sg_sinkhorn")
+        return z
+
+    @_on_device
+    def match_tail(self, z, match_threshold):
+        dev = z.device
+        zz = _check(z, "z", dev)
+        b, n0, n1 = zz.shape[0], zz.shape[1] - 1, zz.shape[2] - 1
+        ws = self.workspace(b, n0, n1, dev)
+        m0, m1, s0, s1 = self.outputs(b, n0, n1, dev)
+        _native_sg.check(self.lib.sg_match_tail(zz.data_ptr(), b, n0, n1, float(match_threshold), m0.data_ptr(), m1.data_ptr(),
+                                                s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                         "sg_match_tail")
+        return m0, m1, s0, s1
+
+
+class SuperGlue(nn.Module):
+    """SuperGlue feature matching middle-end (reference :173-276) on HIP kernels, inference only."""
+
+    default_config = {
+        "descriptor_dim": 256,
+        "weights": "indoor",
+        "keypoint_encoder": [32, 64, 128, 256],
+        "GNN_layers": ["self", "cross"] * 9,
+        "sinkhorn_iterations": 100,
+        "match_threshold": 0.2,
+    }
+
+    def __init__(self, config=None):
+        super().__init__()
+        self.config = {**self.default_config, **(config or {})}
+        cfg = self.config
+        if cfg["descriptor_dim"] != D:
+            raise ValueError(f"onepose_amd.SuperGlue supports descriptor_dim={D} only (got {cfg['descriptor_dim']})")
+        if list(cfg["keypoint_encoder"]) != KENC_LAYERS:
+            raise ValueError(f"onepose_amd.SuperGlue supports keypoint_encoder={KENC_LAYERS} only (got {cfg['keypoint_encoder']})")
+        if cfg.get("num_heads", HEADS) != HEADS:
+            raise ValueError(f"onepose_amd.SuperGlue supports {HEADS} attention heads only")
+        names = list(cfg["GNN_layers"])
+        if any(n not in ("self", "cross") for n in names):
+            raise ValueError("GNN_layers entries must be 'self' or 'cross'")
+        if len(names) > 64:
+            raise ValueError("at most 64 GNN layers")
+        if int(cfg["sinkhorn_iterations"]) < 0:
+            raise ValueError("sinkhorn_iterations must be >= 0")
+        self.kenc = _KeypointEncoder()
+        self.gnn = _AttentionalGNN(names)
+        self.final_proj = nn.Conv1d(D, D, kernel_size=1, bias=True)
+        self.register_parameter("bin_score", nn.Parameter(torch.tensor(1.0)))
+        self.layer_kinds = [_native_sg.LAYER_CROSS if n == "cross" else _native_sg.LAYER_SELF for n in names]
+        self.n_layers = len(names)
+        self._raw_slots = []
+        for key, val in self.state_dict(keep_vars=True).items():
+            if key.endswith("num_batches_tracked"):
+                continue
+            path, _, name = key.rpartition(".")
+            self._raw_slots.append((self.get_submodule(path) if path else self, name))
+        assert len(self._raw_slots) == _native_sg.num_raw(self.n_layers)
+        self._engine = None
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            self._engine = SuperGlueEngine(self)
+        return self._engine
+
+    @torch.no_grad()
+    def forward(self, data):
+        """Run SuperGlue on a pair of keypoints and descriptors (reference :207-276)."""
+        if self.training:
+            raise RuntimeError("onepose_amd.SuperGlue is inference only (BatchNorm running statistics, no backward): call .eval()")
+        kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
+        if kpts0.shape[1] == 0 or kpts1.shape[1] == 0:   # no keypoints: nothing is launched (:221-231)
+            shape0, shape1 = kpts0.shape[:-1], kpts1.shape[:-1]
+            return {
+                "matches0": kpts0.new_full(shape0, -1, dtype=torch.int),
+                "matches1": kpts1.new_full(shape1, -1, dtype=torch.int),
+                "matching_scores0": kpts0.new_zeros(shape0),
+                "matching_scores1": kpts1.new_zeros(shape1),
+            }
+        if not kpts0.is_cuda:
+            raise RuntimeError(f"onepose_amd.SuperGlue runs only on a ROCm GPU (the inputs are on {kpts0.device}); "
+                               "there is no CPU fallback")
+        hw0, hw1 = data["image0"].shape[-2:], data["image1"].shape[-2:]
+        m0, m1, s0, s1 = self.engine.forward(kpts0, data["scores0"], data["descriptors0"], kpts1, data["scores1"],
+                                             data["descriptors1"], hw0, hw1)
+        return {"matches0": m0, "matches1": m1, "matching_scores0": s0, "matching_scores1": s1}

@@ -267,3 +267,78 @@ def write_annotation(dirname, anno):
     np.savez(os.path.join(dirname, "anno_3d_collect.npz"), keypoints3d=anno["keypoints3d"],
              descriptors3d=anno["collect_descriptors"], scores3d=anno["collect_scores"])
     np.save(os.path.join(dirname, "idxs.npy"), anno["idxs"])
+
+
+# ---- SuperGlue 2D-2D matcher (src/models/matchers/SuperGlue/superglue.py:173-205) ----
+SG_KENC = (3, 32, 64, 128, 256, 256)
+
+
+def _bn(rs, prefix, c, sd):
+    """BatchNorm1d in eval mode: random affine and running statistics with positive variance."""
+    sd[prefix + ".weight"] = rs.uniform(0.5, 1.5, size=(c,)).astype(np.float32)
+    sd[prefix + ".bias"] = rs.normal(0.0, 0.1, size=(c,)).astype(np.float32)
+    sd[prefix + ".running_mean"] = rs.normal(0.0, 0.1, size=(c,)).astype(np.float32)
+    sd[prefix + ".running_var"] = rs.uniform(0.5, 1.5, size=(c,)).astype(np.float32)
+    sd[prefix + ".num_batches_tracked"] = np.array(0, dtype=np.int64)
+
+
+def make_superglue_state_dict(seed=0, n_layers=18, delta_gain=0.3, kenc_gain=0.3, proj_gain=6.0):
+    """Random SuperGlue weights in the reference state_dict order.  The last conv of every residual branch (kenc.encoder.12,
+    gnn.layers.i.mlp.3) is scaled by kenc_gain / delta_gain so that activations stay O(1) through 18 residual layers; final_proj
+    by proj_gain so that the score matrix is peaked enough for mutual matches above the thresholds; nonzero bin_score."""
+    rs = np.random.RandomState(seed)
+    sd = {"bin_score": np.array(rs.uniform(0.5, 1.5), dtype=np.float32)}
+    j = 0
+    for i in range(5):
+        w, b = _conv(rs, SG_KENC[i + 1], SG_KENC[i])
+        if i == 4:
+            w, b = w * np.float32(kenc_gain), np.zeros_like(b)     # the reference zero-inits this bias (:77)
+        sd[f"kenc.encoder.{j}.weight"], sd[f"kenc.encoder.{j}.bias"] = w, b
+        if i < 4:
+            _bn(rs, f"kenc.encoder.{j + 1}", SG_KENC[i + 1], sd)
+        j += 3
+    for li in range(n_layers):
+        p = f"gnn.layers.{li}"
+        sd[f"{p}.attn.merge.weight"], sd[f"{p}.attn.merge.bias"] = _conv(rs, D, D)
+        for k in range(3):
+            sd[f"{p}.attn.proj.{k}.weight"], sd[f"{p}.attn.proj.{k}.bias"] = _conv(rs, D, D)
+        sd[f"{p}.mlp.0.weight"], sd[f"{p}.mlp.0.bias"] = _conv(rs, 2 * D, 2 * D)
+        _bn(rs, f"{p}.mlp.1", 2 * D, sd)
+        w, _ = _conv(rs, D, 2 * D)
+        sd[f"{p}.mlp.3.weight"], sd[f"{p}.mlp.3.bias"] = w * np.float32(delta_gain), np.zeros(D, np.float32)
+    w, b = _conv(rs, D, D)
+    sd["final_proj.weight"], sd["final_proj.bias"] = w * np.float32(proj_gain), b
+    return sd
+
+
+def make_superglue_passthrough_state_dict(seed=0, n_layers=18, proj_gain=16.0, bin_score=8.0):
+    """Every delta is zero (kenc.encoder.12 and every mlp.3 are zero) and final_proj is proj_gain * identity, so the scores are
+    proj_gain^2 / 16 * desc0^T desc1: with unit-norm inputs a planted pair (equal descriptors) scores 16, distractors ~ N(0, 1)."""
+    sd = make_superglue_state_dict(seed, n_layers)
+    for k in list(sd):
+        if k.startswith("kenc.encoder.12.") or (k.startswith("gnn.layers.") and ".mlp.3." in k):
+            sd[k] = np.zeros_like(sd[k])
+    sd["final_proj.weight"] = (np.eye(D, dtype=np.float32) * np.float32(proj_gain))[:, :, None]
+    sd["final_proj.bias"] = np.zeros(D, np.float32)
+    sd["bin_score"] = np.array(bin_score, dtype=np.float32)
+    return sd
+
+
+def make_superglue_inputs(b, n0, n1, h, w, seed=1, planted=None):
+    """Keypoints inside an h x w image, scores in (0, 1), unit-norm descriptors [b, 256, n].  planted = k: in each image
+    k random pairs (planted0[:, t], planted1[:, t]) share a descriptor, every other point is a random distractor."""
+    rs = np.random.RandomState(seed)
+    out = {}
+    for s, n in ((0, n0), (1, n1)):
+        out[f"keypoints{s}"] = np.stack([rs.uniform(0, w - 1, size=(b, n)), rs.uniform(0, h - 1, size=(b, n))], -1).astype(np.float32)
+        out[f"scores{s}"] = rs.uniform(0.01, 0.99, size=(b, n)).astype(np.float32)
+        out[f"descriptors{s}"] = _unit(rs.normal(size=(b, D, n)).astype(np.float32), 1)
+    out["image_size0"] = out["image_size1"] = np.array([h, w], dtype=np.int64)
+    if planted:
+        k = int(planted)
+        p0 = np.stack([rs.permutation(n0)[:k] for _ in range(b)])
+        p1 = np.stack([rs.permutation(n1)[:k] for _ in range(b)])
+        for i in range(b):
+            out["descriptors1"][i][:, p1[i]] = out["descriptors0"][i][:, p0[i]]
+        out["planted0"], out["planted1"] = p0.astype(np.int64), p1.astype(np.int64)
+    return out
