@@ -75,6 +75,13 @@ int sg_keypoint_encode(const float* packed, int n_layers,
 int sg_layer(const float* packed, int n_layers, int layer, int kind, const float* desc0, const float* desc1,
              int b, int n0, int n1, float* out0, float* out1, void* workspace, size_t workspace_bytes, sg_stream_t stream);
 
+/* Stage: the softmax attention of MultiHeadedAttention (:85-88, :100-106) on given projections, the kernel sg_layer
+ * and sg_forward run with the same launch shape: per batch item and head h (channels h*64 .. h*64+63),
+ * out[h*64+d][n] = sum_m softmax_m(sum_e q[h*64+e][n] k[h*64+e][m] / 8) v[h*64+d][m].
+ * Head-contiguous layout (the packed layout above): q [b][256][N], kv [b][512][M] (k rows 0..255, then v rows
+ * 256..511), out [b][256][N].  N, M >= 1; out must not alias q or kv. */
+int sg_attention(const float* q, const float* kv, int b, int N, int M, float* out, sg_stream_t stream);
+
 /* Stage: log_optimal_transport (:148-170) on given scores [b][n0][n1] (already divided by sqrt(256))
  * with the dustbin score *bin_score (device) -> z_out [b][n0+1][n1+1]. */
 int sg_sinkhorn(const float* scores, const float* bin_score, int b, int n0, int n1, int iters, float* z_out,

@@ -33,6 +33,7 @@ SYMBOLS = {
     "sg_keypoint_encode": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
                                    c_size_t, _P]),
     "sg_layer": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "sg_attention": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "sg_sinkhorn": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "sg_match_tail": (c_int, [_P, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
 }

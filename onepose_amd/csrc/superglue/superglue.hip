@@ -611,6 +611,12 @@ int run_kenc(const Ctx& c, const float* const kp[2], const float* const sc[2], c
     return gemm(c, g4, "kenc layer 4");
 }
 
+// one launch for both sides: grid (query blocks of the larger side, heads, 2 * b); blocks past a side's N return at once
+int launch_attention(const AttnArgs& aa, int nmax, hipStream_t st) {
+    hipLaunchKernelGGL(sg_attn_kernel, dim3((nmax + 127) / 128, SG_HEADS, 2 * aa.b), dim3(256), 0, st, aa);
+    return launch_status("attention");
+}
+
 int run_layer(const Ctx& c, int layer, int kind, const float* const in[2], float* const out[2]) {
     const float* W = c.w + layer_base(layer);
     // q from x, k / v from the source (pre-update descriptors of both sides)
@@ -630,8 +636,7 @@ int run_layer(const Ctx& c, int layer, int kind, const float* const in[2], float
         aa.side[s] = AttnSide{c.buf(c.L.q, CH_Q, s), 256L * c.n(s), c.buf(c.L.kv, CH_KV, s), 512L * c.n(src),
                               c.buf(c.L.msg, CH_MSG, s), 256L * c.n(s), c.n(s), c.n(src)};
     }
-    hipLaunchKernelGGL(sg_attn_kernel, dim3((c.L.nm + 127) / 128, SG_HEADS, 2 * c.L.b), dim3(256), 0, c.st, aa);
-    if (int rc = launch_status("attention")) return rc;
+    if (int rc = launch_attention(aa, c.L.nm, c.st)) return rc;
     GemmArgs gm{};
     gm.njobs = 2; gm.K = 256; gm.lda = 256;
     for (int s = 0; s < 2; ++s)
@@ -791,6 +796,19 @@ int sg_layer(const float* packed, int n_layers, int layer, int kind, const float
     const float* in[2] = {desc0, desc1};
     float* out[2] = {out0, out1};
     return run_layer(c, layer, kind, in, out);
+}
+
+int sg_attention(const float* q, const float* kv, int b, int N, int M, float* out, sg_stream_t stream) {
+    if (b < 1 || N < 1 || M < 1) return fail(-1, "b, N, M must be >= 1 (got %d, %d, %d)", b, N, M);
+    if (size_t(b) * 2 * D * std::max(N, M) > (size_t(1) << 31)) return fail(-1, "problem too large");
+    if (!q || !kv || !out) return fail(-1, "null argument");
+    if (out == q || out == kv) return fail(-1, "out must not alias q or kv");
+    // the forward's launch: side 1 repeats side 0 with no query blocks (N = 0 returns before any load or store)
+    AttnArgs aa{};
+    aa.b = b;
+    aa.side[0] = AttnSide{q, 256L * N, kv, 512L * M, out, 256L * N, N, M};
+    aa.side[1] = AttnSide{q, 256L * N, kv, 512L * M, out, 256L * N, 0, M};
+    return launch_attention(aa, N, reinterpret_cast<hipStream_t>(stream));
 }
 
 int sg_sinkhorn(const float* scores, const float* bin_score, int b, int n0, int n1, int iters, float* z_out, void* workspace,

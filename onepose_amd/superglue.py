@@ -181,6 +181,19 @@ class SuperGlueEngine:
         return o0, o1
 
     @_on_device
+    def attention(self, q, kv):
+        """Softmax attention of the layers' kernel on head-contiguous q [b,256,N] and kv [b,512,M] (k rows, then v rows);
+        returns [b,256,N]: per head h, out[h*64+d] = sum_m softmax_m(q_h . k_h[:, m] / 8) v[h*64+d, m]."""
+        dev = q.device
+        qq, kk = _check(q, "q", dev), _check(kv, "kv", dev)
+        if qq.dim() != 3 or kk.dim() != 3 or qq.shape[1] != D or kk.shape[1] != 2 * D or kk.shape[0] != qq.shape[0]:
+            raise ValueError("q must be [b,256,N] and kv [b,512,M] with one b")
+        b, n, m = qq.shape[0], qq.shape[2], kk.shape[2]
+        out = torch.empty_like(qq)
+        _native_sg.check(self.lib.sg_attention(qq.data_ptr(), kk.data_ptr(), b, n, m, out.data_ptr(), _stream(dev)), "sg_attention")
+        return out
+
+    @_on_device
     def sinkhorn(self, scores, bin_score, iters):
         dev = scores.device
         sc = _check(scores, "scores", dev)

@@ -282,10 +282,12 @@ def _bn(rs, prefix, c, sd):
     sd[prefix + ".num_batches_tracked"] = np.array(0, dtype=np.int64)
 
 
-def make_superglue_state_dict(seed=0, n_layers=18, delta_gain=0.3, kenc_gain=0.3, proj_gain=6.0):
+def make_superglue_state_dict(seed=0, n_layers=18, delta_gain=0.3, kenc_gain=0.3, proj_gain=6.0, attn_gain=1.0):
     """Random SuperGlue weights in the reference state_dict order.  The last conv of every residual branch (kenc.encoder.12,
     gnn.layers.i.mlp.3) is scaled by kenc_gain / delta_gain so that activations stay O(1) through 18 residual layers; final_proj
-    by proj_gain so that the score matrix is peaked enough for mutual matches above the thresholds; nonzero bin_score."""
+    by proj_gain so that the score matrix is peaked enough for mutual matches above the thresholds; nonzero bin_score.
+    attn_gain scales weight and bias of the q and k projections (attn.proj.0 / .1), so the attention logits scale by attn_gain^2:
+    at 1 a row of logits spans ~0.02 and the softmax is flat; about 30 gives spreads of ~10 and peaked rows."""
     rs = np.random.RandomState(seed)
     sd = {"bin_score": np.array(rs.uniform(0.5, 1.5), dtype=np.float32)}
     j = 0
@@ -301,7 +303,10 @@ def make_superglue_state_dict(seed=0, n_layers=18, delta_gain=0.3, kenc_gain=0.3
         p = f"gnn.layers.{li}"
         sd[f"{p}.attn.merge.weight"], sd[f"{p}.attn.merge.bias"] = _conv(rs, D, D)
         for k in range(3):
-            sd[f"{p}.attn.proj.{k}.weight"], sd[f"{p}.attn.proj.{k}.bias"] = _conv(rs, D, D)
+            w, b = _conv(rs, D, D)
+            if k < 2 and attn_gain != 1.0:
+                w, b = w * np.float32(attn_gain), b * np.float32(attn_gain)
+            sd[f"{p}.attn.proj.{k}.weight"], sd[f"{p}.attn.proj.{k}.bias"] = w, b
         sd[f"{p}.mlp.0.weight"], sd[f"{p}.mlp.0.bias"] = _conv(rs, 2 * D, 2 * D)
         _bn(rs, f"{p}.mlp.1", 2 * D, sd)
         w, _ = _conv(rs, D, 2 * D)
@@ -324,16 +329,20 @@ def make_superglue_passthrough_state_dict(seed=0, n_layers=18, proj_gain=16.0, b
     return sd
 
 
-def make_superglue_inputs(b, n0, n1, h, w, seed=1, planted=None):
-    """Keypoints inside an h x w image, scores in (0, 1), unit-norm descriptors [b, 256, n].  planted = k: in each image
-    k random pairs (planted0[:, t], planted1[:, t]) share a descriptor, every other point is a random distractor."""
+def make_superglue_inputs(b, n0, n1, h, w, seed=1, planted=None, h1=None, w1=None):
+    """Keypoints inside an h x w image (side 0) and an h1 x w1 image (side 1; default h x w), scores in (0, 1), unit-norm
+    descriptors [b, 256, n].  planted = k: in each image k random pairs (planted0[:, t], planted1[:, t]) share a descriptor,
+    every other point is a random distractor."""
     rs = np.random.RandomState(seed)
+    h1 = h if h1 is None else h1
+    w1 = w if w1 is None else w1
     out = {}
-    for s, n in ((0, n0), (1, n1)):
-        out[f"keypoints{s}"] = np.stack([rs.uniform(0, w - 1, size=(b, n)), rs.uniform(0, h - 1, size=(b, n))], -1).astype(np.float32)
+    for s, n, hh, ww in ((0, n0, h, w), (1, n1, h1, w1)):
+        out[f"keypoints{s}"] = np.stack([rs.uniform(0, ww - 1, size=(b, n)), rs.uniform(0, hh - 1, size=(b, n))], -1).astype(np.float32)
         out[f"scores{s}"] = rs.uniform(0.01, 0.99, size=(b, n)).astype(np.float32)
         out[f"descriptors{s}"] = _unit(rs.normal(size=(b, D, n)).astype(np.float32), 1)
-    out["image_size0"] = out["image_size1"] = np.array([h, w], dtype=np.int64)
+    out["image_size0"] = np.array([h, w], dtype=np.int64)
+    out["image_size1"] = np.array([h1, w1], dtype=np.int64)
     if planted:
         k = int(planted)
         p0 = np.stack([rs.permutation(n0)[:k] for _ in range(b)])

@@ -44,12 +44,20 @@ CASES = {
                      store="stats"),
     "stress": dict(w=dict(kind="rand", seed=12), inp=dict(b=1, n0=4096, n1=4096, h=512, w=512, seed=13), cfg=dict(OUTDOOR),
                    store="stats"),
+    # peaked attention (attn_gain scales the q / k projections: median row logit spread 9.7-13.9 in every layer), K/V tile tails
+    # (517 = 8 * 64 + 5, 300 = 2 * 128 + 44), per-side image sizes, planted pairs that pass threshold 0.2
+    "peaked": dict(w=dict(kind="rand", seed=50, attn_gain=30.0, proj_gain=20.0),
+                   inp=dict(b=1, n0=300, n1=517, h=512, w=512, h1=480, w1=640, seed=51, planted=100),
+                   cfg=dict(OUTDOOR, match_threshold=0.2), store="full"),
+    # default weights, b = 3, one query block plus one point / one K/V tile plus one source, per-side sizes, side 1 taller than wide
+    "sizes": dict(w=dict(kind="rand", seed=52), inp=dict(b=3, n0=129, n1=65, h=480, w=640, h1=700, w1=300, seed=53),
+                  cfg=dict(OUTDOOR, match_threshold=0.2), store="full"),
 }
 
 
 def weights(spec, n_layers):
     fn = synthetic.make_superglue_passthrough_state_dict if spec["kind"] == "passthrough" else synthetic.make_superglue_state_dict
-    return fn(spec["seed"], n_layers)
+    return fn(spec["seed"], n_layers, **{k: v for k, v in spec.items() if k not in ("kind", "seed")})
 
 
 def full_config(cfg):
@@ -63,9 +71,10 @@ def run_case(spec):
     model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
     inp = synthetic.make_superglue_inputs(**spec["inp"])
     b = spec["inp"]["b"]
-    h, w = spec["inp"]["h"], spec["inp"]["w"]
     data = {k: torch.from_numpy(inp[k]) for k in ("keypoints0", "keypoints1", "scores0", "scores1", "descriptors0", "descriptors1")}
-    data["image0"] = data["image1"] = torch.zeros(b, 1, h, w)
+    for s in (0, 1):      # each side's own image size: normalize_keypoints reads data["image<s>"].shape
+        h, w = (int(x) for x in inp[f"image_size{s}"])
+        data[f"image{s}"] = torch.zeros(b, 1, h, w)
     captured = {}
 
     # capture Z: the last log_optimal_transport output is what forward thresholds; recompute it from the scores the

@@ -27,7 +27,7 @@ def lib():
 
 def test_every_declared_symbol_is_exported_and_bound(lib):
     names = header_functions()
-    assert "sg_forward" in names and "sg_sinkhorn" in names
+    assert "sg_forward" in names and "sg_sinkhorn" in names and "sg_attention" in names
     raw = ctypes.CDLL(_native_sg.LIB_PATH)
     for n in names:
         assert hasattr(raw, n), n
@@ -44,6 +44,11 @@ def test_host_side_checks(lib):
     ws = ctypes.create_string_buffer(16)
     rc = lib.sg_match_tail(None, 1, 8, 8, 0.2, None, None, None, None, ctypes.addressof(ws), 16, None)
     assert rc == -2 and b"workspace" in lib.sg_last_error()
+    rc = lib.sg_attention(None, None, 1, 5, 0, None, None)
+    assert rc == -1 and b"M" in lib.sg_last_error()
+    buf = ctypes.create_string_buffer(16)
+    rc = lib.sg_attention(ctypes.addressof(buf), ctypes.addressof(buf), 1, 1, 1, ctypes.addressof(buf), None)
+    assert rc == -1 and b"alias" in lib.sg_last_error()
     kinds = (ctypes.c_int32 * 1)(7)
     big = lib.sg_workspace_bytes(1, 4, 4)
     buf = ctypes.create_string_buffer(big)

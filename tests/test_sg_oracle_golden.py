@@ -21,7 +21,7 @@ def case_inputs(spec):
     cfg = spec["cfg"]
     n_layers = len(cfg["GNN_layers"])
     fn = synthetic.make_superglue_passthrough_state_dict if spec["w"]["kind"] == "passthrough" else synthetic.make_superglue_state_dict
-    sd = fn(spec["w"]["seed"], n_layers)
+    sd = fn(spec["w"]["seed"], n_layers, **{k: v for k, v in spec["w"].items() if k not in ("kind", "seed")})
     inp = synthetic.make_superglue_inputs(**spec["inp"])
     return sd, inp, cfg
 
@@ -49,7 +49,7 @@ def compare(out, Z, gold, ztol=1e-4, stol=1e-5):
     np.testing.assert_allclose(out["matching_scores1"], gold["matching_scores1"], rtol=2e-6, atol=stol)
 
 
-CASES = ["tiny", "iters0", "iters1", "n1", "planted", "outdoor", "headline"]
+CASES = ["tiny", "iters0", "iters1", "n1", "planted", "outdoor", "headline", "peaked", "sizes"]
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -62,9 +62,17 @@ def test_oracle_matches_reference_golden(name):
 
 
 def test_planted_passthrough_recovers_every_pair():
-    spec = _meta()["cases"]["planted"]
+    _planted_pairs_recovered("planted")
+
+
+def test_peaked_recovers_every_planted_pair_above_threshold():
+    _planted_pairs_recovered("peaked")
+
+
+def _planted_pairs_recovered(name):
+    spec = _meta()["cases"][name]
     sd, inp, cfg = case_inputs(spec)
-    gold = dict(np.load(os.path.join(GOLD, "sg_planted.npz")))
+    gold = dict(np.load(os.path.join(GOLD, f"sg_{name}.npz")))
     m0 = gold["matches0"][0]
     p0, p1 = inp["planted0"][0], inp["planted1"][0]
     assert (m0[p0] == p1).all()
@@ -84,3 +92,80 @@ def test_match_tail_first_index_wins_on_ties():
     out = so.match_tail(Z, 0.0)
     assert out["matches0"][0].tolist() == [1, -1, -1]
     assert out["matches1"][0].tolist() == [-1, 0, -1, -1]
+
+
+def test_default_arguments_leave_synthetic_unchanged():
+    """attn_gain = 1 and h1 / w1 = None are the old functions: every pre-existing golden is regenerated from them."""
+    a, b = synthetic.make_superglue_state_dict(3, 2), synthetic.make_superglue_state_dict(3, 2, attn_gain=1.0)
+    assert all(a[k].tobytes() == b[k].tobytes() for k in a)
+    a = synthetic.make_superglue_inputs(2, 5, 7, 480, 640, seed=4)
+    b = synthetic.make_superglue_inputs(2, 5, 7, 480, 640, seed=4, h1=480, w1=640)
+    assert all(a[k].tobytes() == b[k].tobytes() for k in a)
+    c = synthetic.make_superglue_inputs(2, 5, 7, 480, 640, seed=4, h1=700, w1=300)
+    assert c["image_size0"].tolist() == [480, 640] and c["image_size1"].tolist() == [700, 300]
+    assert (c["keypoints1"][..., 0] <= 299).all() and (c["keypoints1"][..., 1] <= 699).all()
+    assert c["keypoints1"][..., 1].max() > 640
+
+
+# ---- the peaked golden bites: its softmax is far from uniform, and softmax bugs a tiled kernel can have move Z far past the GPU
+# ---- forward bounds (so.FORWARD_ZTOL / FORWARD_STOL) ----
+TILE = 64    # source points per K/V tile of sg_attn_kernel
+_SOFTMAX = so._softmax
+
+
+def _uniform(x, axis):
+    return np.full_like(x, 1.0 / x.shape[-1])
+
+
+def _tile_reversed(x, axis):
+    p = _SOFTMAX(x, axis)
+    out = p.copy()
+    for j0 in range(0, x.shape[-1], TILE):
+        out[..., j0:j0 + TILE] = p[..., j0:j0 + TILE][..., ::-1]
+    return out
+
+
+def _never_rescaled(x, axis):
+    """The online softmax with alpha = 1: each tile exponentiated against the running max up to that tile, the earlier
+    partial sums and outputs never rescaled when the max grows."""
+    e = np.empty_like(x)
+    run = np.full(x.shape[:-1] + (1,), -np.inf, x.dtype)
+    for j0 in range(0, x.shape[-1], TILE):
+        t = x[..., j0:j0 + TILE]
+        run = np.maximum(run, t.max(-1, keepdims=True))
+        e[..., j0:j0 + TILE] = np.exp(t - run)
+    return e / e.sum(-1, keepdims=True)
+
+
+@pytest.fixture(scope="module")
+def peaked():
+    spec = _meta()["cases"]["peaked"]
+    sd, inp, cfg = case_inputs(spec)
+    return sd, inp, cfg, dict(np.load(os.path.join(GOLD, "sg_peaked.npz")))
+
+
+def test_peaked_regime_every_layer(peaked, monkeypatch):
+    """Every attention call of the peaked golden (18 layers x 2 sides) has a median row logit spread >= 8."""
+    sd, inp, cfg, _ = peaked
+    spreads = []
+
+    def spy(x, axis):
+        spreads.append(float(np.median(x.max(axis) - x.min(axis))))
+        return _SOFTMAX(x, axis)
+    monkeypatch.setattr(so, "_softmax", spy)
+    so.forward(sd, inp, cfg, np.float32)
+    assert len(spreads) == 2 * len(cfg["GNN_layers"])
+    print(f"\npeaked: median row logit spread per call {min(spreads):.2f} .. {max(spreads):.2f}")
+    assert min(spreads) >= 8.0, spreads
+
+
+@pytest.mark.parametrize("mutant", [_uniform, _tile_reversed, _never_rescaled], ids=["uniform", "tile_reversed", "never_rescaled"])
+def test_peaked_golden_catches_softmax_mutants(peaked, monkeypatch, mutant):
+    sd, inp, cfg, gold = peaked
+    monkeypatch.setattr(so, "_softmax", mutant)
+    out, Z = so.forward(sd, inp, cfg, np.float32)
+    zerr = float(np.abs(Z - gold["Z"]).max())
+    serr = max(float(np.abs(out[k] - gold[k]).max() / max(1.0, float(np.abs(gold[k]).max())))
+               for k in ("matching_scores0", "matching_scores1"))
+    print(f"\n{mutant.__name__}: max|dZ| {zerr:.3e} ({zerr / so.FORWARD_ZTOL:.0f}x the bound), score err {serr:.3e}")
+    assert zerr >= 10 * so.FORWARD_ZTOL and serr >= 10 * so.FORWARD_STOL
