@@ -4,9 +4,9 @@
     python -m onepose_amd.build_ext [--force] [--remarks] [--profiling] [--tuning]
 
 The product libraries never read the environment.  ``--tuning`` builds SEPARATE libraries (``lib*_tuning.so``, never
-loaded by the package) with -DGATSSPG_TUNING / -DSPP_TUNING, whose alternative tile shapes are selected by
-GATSSPG_<KNOB> / SPP_<KNOB> environment variables (tools/ab_tuning.py); ``--profiling`` adds the timing-only ablation
-variants and the mlp0 timeline hook (tools/trace_mlp0.py) to such a separate library as well.
+loaded by the package) with -DGATSSPG_TUNING / -DSPP_TUNING, which read GATSSPG_<KNOB> / SPP_<KNOB> environment variables
+(tools/ab_tuning.py; the matcher's knobs are the shape thresholds between two product kernels); ``--profiling`` adds the
+mlp0 / split-loop timeline hooks (tools/trace_mlp0.py, tools/trace_sp.py) to such a separate library as well.
 """
 from __future__ import annotations
 
@@ -71,8 +71,8 @@ def tuning_path(lib):
 
 def build(force=False, remarks=False, verbose=True, profiling=False, tuning=False, syntax_only=False):
     """Compile every HIP source for gfx950 into onepose_amd/lib/lib{gatsspg,spp,pnp,superglue}_hip.so.
-    tuning / profiling builds go to lib*_tuning.so (environment knobs; profiling adds -DGATSSPG_PROFILING_BUILD: timing-only
-    ablation variants + the mlp0 timeline hook) -- the package never loads those.  syntax_only: front-end check only."""
+    tuning / profiling builds go to lib*_tuning.so (environment knobs; profiling adds -DGATSSPG_PROFILING_BUILD: the timeline
+    hooks) -- the package never loads those.  syntax_only: front-end check only."""
     os.makedirs(LIB_DIR, exist_ok=True)
     special = tuning or profiling
     for lib, srcs, deps in ((LIB_PATH, SOURCES, SOURCES + HEADERS), (SPP_LIB_PATH, SPP_SOURCES, SPP_SOURCES + SPP_HEADERS),

@@ -34,7 +34,7 @@ struct ColLayout {
     // every frame (default: the whole frame).  Lets the per-point kernels run on the query side or the 3D side only.
     int tw_first, tw_count;
     int side_mask;   // bit 0: 2D-side segments active, bit 1: 3D-side segments (segment-level reduction kernels)
-    int xgs;         // XCD granule of a launch's tile map, log2 of column tiles (xcd_tile_map_g; set by the launcher, 0 = one tile)
+    int xgs;         // XCD granule of the split kernels' tile map, log2 of column tiles (xcd_tile_map_g); always 0
 };
 
 __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

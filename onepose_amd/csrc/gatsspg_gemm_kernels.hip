@@ -32,7 +32,7 @@ constexpr int smem_floats_mainloop() { return (int)(smem_bytes<T, PREC>() / size
 //     (GATs_SuperGlue.py:96-99 projections, :71-72 feature map, :77-78 KV and key.sum)
 // =====================================================================================================
 using QkvTileW8 = GemmTile<128, QKV_BN, 4, 2, false>;     // both arithmetics: 8 waves, one 32x32 MFMA tile each (fp32: 38.0 vs 40.1 us on 4 waves)
-using QkvTileB = GemmTile<128, QKV_BN, 2, 2, false>;      // split-bf16 alternative (tuning builds): 4 waves, 64x32 per wave (31.2 vs 24.6 us)
+// (split-bf16 on 4 waves, 64x32 per wave: 31.2 vs 24.6 us; removed with the QKV_BTILE knob)
 
 // PREC = 0: exact fp32 MFMA.  PREC = 1: split-bf16 main loop on the pre-split weight planes Whi / Wlo.
 // (forcing 80 VGPRs so that three 8-wave workgroups fit a CU -- the 756 tiles of the headline shape then fit 768 slots in one
@@ -204,11 +204,10 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel
 //     partial (0 + x = x: same bits as reducing the partials again).
 constexpr int KVP4 = KVP / 4;
 static_assert(KVP % 4 == 0, "KV partials are summed as float4");
-// KVF_RS: row parts of M_t per d block.  2: two workgroups repeat the (cheap, parallel) reduction and each turns it into 256 rows of the
-// operator with its first 512 threads (264 workgroups, every CU busy).  1: one workgroup per d block, all 1024 threads in the operator
-// phase, every partial read once (136 workgroups, half the bytes).
-
-// abl (tuning builds only, wrong results, 0 in the product): bit 0 no FMA phase, bit 1 no operator stores, bit 2 no weight loads
+// KVF_RS: row parts of M_t per d block; the product runs 1: one workgroup per d block, all 1024 threads in the operator phase, every
+// partial read once.  (2, two workgroups per d block each repeating the reduction, lost: profiles/r04_ab_live_kv_final.txt; removed.)
+// abl: 0.  (The operator-phase ablations behind it are gone; the parameter and its branches stay because without them hipcc gives the
+// kernel 110 instead of 94 VGPRs.)
 template <int KVF_RS>
 __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict__ kvpart, const float* __restrict__ kv_src,
                                                         float* __restrict__ kvfin, const float* __restrict__ W0,
@@ -419,7 +418,7 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
 // =====================================================================================================
 // tiles (one InstanceNorm partial per 64-column tile whatever BN is)
 using Mlp0TileW8 = GemmTile<128, MLP0_BN, 4, 2, false>;       // all arithmetics: 8 waves, one 32x32 MFMA tile each (fp32: 43.1 vs 45.0 us on 4 waves)
-using Mlp0TileS = GemmTile<64, MLP0_BN, 2, 2, false, false, 2>;   // fp32, launches that leave CUs empty: 64x64, two K groups of 4 waves
+// (a 64x64 two-K-group fp32 tile for launches that leave CUs empty was never selected: SMALL_NT0 = 0; removed)
 // (round 2 also measured 128x128 tiles -- 16 waves fp32: kernel -3 %, frames/s in flight -0.8 %; 8 waves split-bf16: kernel -4 %,
 //  frames/s equal; the attention fold needs thread = (k group, column) on a 64-column tile, they are gone)
 
@@ -432,12 +431,11 @@ unsigned long long* g_trace = nullptr;
 static constexpr unsigned long long* g_trace = nullptr;
 #endif
 
-// ABL (profiling builds only, wrong results): main-loop ablations of gemm_mainloop_ex.  PREC as in qkv_kv_kernel.
+// PREC as in qkv_kv_kernel.
 // QF: quarter-fragment main loop (gemm_f32_mfma.h; fp32 arithmetic on the 8-wave tile only)
-// SF: the fused InstanceNorm reducer (stat_last_block) is compiled in.  It is a tuning alternative (GATSSPG_STAT_FUSED=1), never taken in
-//     the product -- but its 64 staging registers were what set the kernel's register count (118 of the 126), so the product
-//     instantiations leave it out (round 6: found in the ISA of the 96-register build, whose only spills sat in that dead branch).
-template <class T, int ABL = 0, int PREC = 0, int BT = 0, int QF = 0, int SF = 0>
+// SF: the fused InstanceNorm reducer (stat_last_block) is compiled in, never taken (statcnt = nullptr; the retired STAT_FUSED form).  Only
+//     the split-bf16 instantiations keep it, to keep their code (launch_mlp0_t); in fp32 its 64 staging registers set the count (118 of 126).
+template <class T, int PREC = 0, int BT = 0, int QF = 0, int SF = 0>
 __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void mlp0_kernel(const float* __restrict__ W0, const float* __restrict__ b0,
                                                    const unsigned short* __restrict__ Whi, const unsigned short* __restrict__ Wlo,
                                                    const unsigned short* __restrict__ Wl2,
@@ -480,15 +478,12 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
     }
     f32x16 acc[T::TM][T::TN];
     zero_acc(acc);
-    // ABL == 5 (profiling): every workgroup streams the SAME weight panel and the SAME column tile (cache-hot operands)
-    const float* Ah = ABL == 5 ? W0 : A;
-    const int ch0 = ABL == 5 ? 0 : c0;
     const TileSeg ts = tile_seg(L, c0, T::BN);   // segments start on multiples of 128 columns: a tile never straddles two
     // K slabs 0..7: the x half of W0 against the state; slabs 8..15: this segment's message operator against Qf
     const float* Am = mop_seg(Mop, ts.seg) + (size_t)rt * T::BM * MOP_LD;
     static_assert(MOP_LD == 512, "the message operator shares the row stride of W0");
-    auto al = [&](int kt) { return kt < 8 ? Ah + kt * BK : Am + (kt - 8) * BK; };
-    auto bl = [&](int kt) { return (kt < 8 ? Z + (size_t)kt * BK * ld : Qbuf + (size_t)(kt - 8) * BK * ld) + ch0; };
+    auto al = [&](int kt) { return kt < 8 ? A + kt * BK : Am + (kt - 8) * BK; };
+    auto bl = [&](int kt) { return (kt < 8 ? Z + (size_t)kt * BK * ld : Qbuf + (size_t)(kt - 8) * BK * ld) + c0; };
     AttnFoldHooks hooks;
     hooks.init(ksumT + (size_t)ts.seg * H * DH, smem + smem_floats_mainloop<T, PREC>(), wn);
     if constexpr (PREC == 1 || PREC >= 3) {
@@ -509,7 +504,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
             },
             BK, bl, ld, &hooks);
     } else {
-        gemm_mainloop<T, decltype(al), decltype(bl), (ABL == 5 ? 0 : ABL), IdentityCol, AttnFoldHooks, QF>(acc, smem, 512 / BK, al, 512, bl, ld,
+        gemm_mainloop<T, decltype(al), decltype(bl), 0, IdentityCol, AttnFoldHooks, QF>(acc, smem, 512 / BK, al, 512, bl, ld,
                                                                                                           IdentityCol(), &hooks);
     }
     acc[0][0] = hooks.kept;
@@ -653,11 +648,11 @@ __global__ __launch_bounds__(1024) void stat_final_kernel(const float* __restric
 //     residual + bias:  Z = (Z + b3) + W3 relu((u - mean) * rstd)      (GATs_SuperGlue.py:126-128, :59,64)
 // =====================================================================================================
 using Mlp3TileTallW8 = GemmTile<128, 64, 4, 2, false>;   // both arithmetics: 128x64 on 8 waves, 252 workgroups (fp32: 21.3 vs 24.6 us, 938 vs 914 frames/s one at a time)
-using Mlp3Tile = GemmTile<64, 64, 2, 2, false>;          // alternative (tuning builds): 64x64 on 4 waves, 504 workgroups
+// (64x64 on 4 waves, 504 workgroups: 24.6 vs 21.3 us, the figures above; removed with the MLP3_TILE knob)
 using Mlp3TileS = GemmTile<64, 64, 2, 2, false, false, 2>;   // fp32, launches that leave CUs empty: 64x64, two K groups of 4 waves
 
 // DS: the output tile leaves straight from the accumulators (store_tile_regs; plain 128 x 64 / 64 x 64 tiles, not the K-split one)
-template <class T, int ABL = 0, int PREC = 0, int DS = 0, int QF = 0>
+template <class T, int PREC = 0, int DS = 0>
 __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void mlp3_kernel(const float* __restrict__ W3, const float* __restrict__ b3,
                                                    const unsigned short* __restrict__ Whi, const unsigned short* __restrict__ Wlo,
                                                    const unsigned short* __restrict__ Wl2,
@@ -716,7 +711,7 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void mlp3_kernel(c
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = fmaxf((v[q] - ms.x) * ms.y, 0.f);
         };
-        gemm_mainloop_ex<T, decltype(al), decltype(bl), decltype(xm), decltype(xr), decltype(bx), true, ABL, IdentityCol, NoHooks, QF>(
+        gemm_mainloop_ex<T, decltype(al), decltype(bl), decltype(xm), decltype(xr), decltype(bx), true>(
             acc, smem, 512 / BK, al, 512, bl, ld, xm, xr, bx);
     }
     ksplit_reduce<T>(acc, smem);
@@ -829,7 +824,7 @@ __global__ __launch_bounds__(FinalTile::THREADS) void final_proj_norm_kernel(con
 //     A = point-major query descriptors MDT (row-major [n][256]), B = channel-major 3D descriptors MD.
 // =====================================================================================================
 using ScoreTileW8 = GemmTile<SC_BM, SC_BN, 4, 2, false>;        // default: 128x64 on 8 waves: 880 tiles at 1000/7000 = 1.7 rounds of the 512 slots
-using ScoreTileSq = GemmTile<SC_BM, 2 * SC_BN, 2, 4, false>;    // alternative (tuning builds): 128x128 on 8 waves, 440 tiles = one round
+// (128x128 on 8 waves, 440 tiles = one round: never the default, removed with the SCORE_TILE knob; partial sums stay per 128x64 tile)
 // Both one-round shapes measured SLOWER than 1.7 rounds of 128x64: 128x128 48.4 vs 45.3 us (event-timed), 256x64 (90 KB of LDS,
 // one workgroup per CU) 52.7 vs 46.4 us; three 128x64 workgroups per CU (80 VGPRs) unchanged.
 
@@ -1049,10 +1044,20 @@ void allow_big_lds() {
     }
 }
 
-// fp32 kernels (8-wave tiles): output tiles straight from the accumulators.  bit 0: the Q tiles of qkv_kv, bit 1: mlp3.  Tuning builds read
-// GATSSPG_FP32_DIRECT per launch (tools/ab_live.py); the product takes the default.
-constexpr int FP32_DIRECT_DEFAULT = 3;
-[[maybe_unused]] static int fp32_direct() { return tuning_knob("FP32_DIRECT", FP32_DIRECT_DEFAULT); }
+// Shape thresholds between two product kernels: named defaults here, read from the environment only by a tuning build (tuning_knob).
+// fp32 qkv_kv / mlp0: launches of more than DIET_MIN_TILES 64-column tiles take the register-diet forms -- quarter fragments + bias through an
+// LDS table: mlp0 94 VGPRs (from 126), qkv_kv 80 (from 98), zero scratch, bit-identical results -- smaller launches the two-half fragment loop.
+// Interleaved A/Bs in one process (profiles/r06b_ab_live_register_diet_*.txt, r06c_*): headline in flight +0.5 % / +0.8 % (two boxes), one at
+// a time -0.2 ... +0.1 %; 8 frames per step +0.8 % both ways; 500 x 2000 -1 ... -2 % in flight (hence the threshold).
+constexpr int DIET_MIN_TILES = 64;
+// fp32 mlp3: launches that leave CUs empty (few columns: OnePose's own 500 x 2000 operating point) are bound by ONE workgroup's dependent MFMA
+// chain, not by the matrix pipes: up to SMALL_NT3 64-column tiles take the 64x64 tile with the K loop split over two wave groups.
+constexpr int SMALL_NT3 = 64;
+static int diet_min_tiles() { return tuning_knob("DIET_MIN_TILES", DIET_MIN_TILES); }
+// (removed alternatives of the fp32 kernels, each measured and lost: the Q / mlp3 tiles staged through LDS instead of stored from the
+//  accumulators, -0.5 % per frame; the bias table without quarter fragments, -0.2 % in flight; quarter fragments without the table; mlp3's
+//  quarter-fragment form, 2 % slower one frame at a time (profiles/r06b_*, r06c_*); the fp32 arithmetic on the LDS-DMA loop, 8 % slower
+//  per frame (profiles/r04_ab_live_fp32_dma.txt))
 
 template <class T, int PREC, int BT = 0, int DS = 0, int QF = 0>
 static void launch_qkv_t(const float* Wqkv, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s,
@@ -1065,131 +1070,53 @@ static void launch_qkv_t(const float* Wqkv, const float* bqkv, const unsigned sh
                    w.Q, w.kvpart, w.L);
 }
 
-// fp16 modes run on the LDS-DMA loop only (their planes carry the pack-time scale that only those kernels undo).  The bf16 modes stay
-// on the first form: A/B-timed on one box (profiles/r04_split_loop_ab.txt), mlp0 bf16x3 25.0 (first form) vs 25.2 us, 1866 vs 1842
-// frames/s in flight; bf16x6 34.4 vs 40.9 us, 1397 vs 1285 -- the three-plane stage makes the DMA loop 1.5x the LDS traffic.  Tuning
-// builds switch them with GATSSPG_SPLIT_LOOP_BF16X3 / _BF16X6 = 1.
-bool stat_fused() {
-    // measured (profiles/r04_stat_fused_ab.txt, one box, three alternations): the fused form makes mlp0 5.3 us longer (partial-store
-    // acknowledgement -> ticket atomic -> agent-scope loads of the partials: three dependent round trips through the memory side for
-    // the last workgroup) and saves the 4.8 us launch: 1.001 vs 0.983 ms per frame at the headline shape, 1231 vs 1232 frames/s in
-    // flight; +1.7 % in flight at 500 x 2000.  The separate launch stays the default; tuning builds: GATSSPG_STAT_FUSED=1.
-    return tuning_knob("STAT_FUSED", 0) != 0;   // (read per launch: tools/ab_live.py)
-}
-
-bool split_loop_glds(int prec) {
-    const int b3 = tuning_knob("SPLIT_LOOP_BF16X3", 0), b6 = tuning_knob("SPLIT_LOOP_BF16X6", 0);   // (read per launch: tools/ab_live.py)
-    return prec >= 3 || (prec == 1 && b3 != 0) || (prec == 2 && b6 != 0);
-}
-
-// fp32 arithmetic on the LDS-DMA loop (tuning builds: GATSSPG_FP32_DMA, bit 0 qkv_kv, 1 mlp0, 2 mlp3); shapes whose launches leave CUs
-// empty keep the K-split tiles of the register-staged loop
-// fp32 qkv_kv / mlp0 (8-wave tiles): bias through an LDS table filled by half an LDS-DMA piece at kernel entry (read_bias16) instead of per-lane loads
-// (tuning builds; measured -0.2 % in flight / -0.7 % one at a time at the headline shape: the split loop's gain from its table came with 38 fewer
-//  registers per wave, which this loop does not get)
-[[maybe_unused]] static int fp32_bias_table() { return tuning_knob("FP32_BIAS_TABLE", 0); }
-// register diet of the fp32 mlp0 kernel (tuning builds, read per launch): 0 = the two-half fragment loop, 1 = quarter fragments,
-// 2 = quarter fragments + bias through the LDS table
-// Product default (-1 = by shape): launches of more than DIET_MIN_TILES 64-column tiles take the dieted kernels -- quarter fragments + bias
-// table: mlp0 94 VGPRs (from 126), qkv_kv 80 (from 98), zero scratch, bit-identical results -- smaller launches the two-half loop.
-// Interleaved A/Bs in one process (profiles/r06b_ab_live_register_diet_*.txt, r06c_*): headline in flight +0.5 % / +0.8 % (two boxes), one at
-// a time -0.2 ... +0.1 %; 8 frames per step +0.8 % both ways; 500 x 2000 -1 ... -2 % in flight (hence the threshold).  mlp3's quarter-fragment
-// form (76 VGPRs) is 2 % slower one frame at a time: tuning builds only.
-constexpr int DIET_MIN_TILES = 64;
-[[maybe_unused]] static int mlp0_diet() { return tuning_knob("MLP0_DIET", -1); }
-[[maybe_unused]] static int qkv_diet() { return tuning_knob("QKV_DIET", -1); }
-[[maybe_unused]] static int mlp3_diet() { return tuning_knob("MLP3_DIET", 0); }
-static int fp32_dma(const Workspace& w) {
-    const int m = tuning_knob("FP32_DMA", 0);
-    return (w.prec == 0 && active_tiles(w.L) > 64) ? m : 0;
-}
-
+// The fp16 modes run on the LDS-DMA loop (their planes carry the pack-time scale that only those kernels undo); the bf16 modes stay on the
+// first form.  (The bf16 modes on the LDS-DMA loop, A/B-timed on one box, profiles/r04_split_loop_ab.txt: bf16x3 1866 vs 1842 frames/s in
+// flight, bf16x6 1397 vs 1285 -- the three-plane stage makes the DMA loop 1.5x the LDS traffic; removed.)
 void launch_qkv_kv(const float* Wqkv, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s,
                    ProfileHook* hk) {
-    if (fp32_dma(w) & 1) return launch_qkv_kv_dma(Wqkv, bqkv, w, s, hk);
-    if (split_loop_glds(w.prec)) {
+    if (w.prec >= 3) {
         // Wqkv is the first member of the layer's AttnW block: its scales sit at AttnW::SC from there
         launch_qkv_kv_sp(Wqkv - AttnW::WQKV + AttnW::SC, bqkv, wb, w, s, hk);
         return;
     }
-    static const int tq = tuning_knob("QKV_BTILE", 0);   // tuning builds: 1 = split-bf16 on the 4-wave tile
-    if (w.prec == 1 && tq == 1) launch_qkv_t<QkvTileB, 1>(Wqkv, bqkv, wb, w, s, hk);
-    else if (w.prec == 1) launch_qkv_t<QkvTileW8, 1>(Wqkv, bqkv, wb, w, s, hk);
+    if (w.prec == 1) launch_qkv_t<QkvTileW8, 1>(Wqkv, bqkv, wb, w, s, hk);
     else if (w.prec == 2) launch_qkv_t<QkvTileW8, 2>(Wqkv, bqkv, wb, w, s, hk);
-#ifdef GATSSPG_TUNING
-    else if (qkv_diet() == 1) launch_qkv_t<QkvTileW8, 0, 0, (FP32_DIRECT_DEFAULT & 1), 1>(Wqkv, bqkv, wb, w, s, hk);   // quarter fragments
-    else if (qkv_diet() == 0 && fp32_bias_table()) launch_qkv_t<QkvTileW8, 0, 1>(Wqkv, bqkv, wb, w, s, hk);
-    else if (qkv_diet() == 0 && !(fp32_direct() & 1)) launch_qkv_t<QkvTileW8, 0>(Wqkv, bqkv, wb, w, s, hk);
-    else if (qkv_diet() == 0) launch_qkv_t<QkvTileW8, 0, 0, (FP32_DIRECT_DEFAULT & 1)>(Wqkv, bqkv, wb, w, s, hk);
-    else if (qkv_diet() == 2 || active_tiles(w.L) > DIET_MIN_TILES)
-        launch_qkv_t<QkvTileW8, 0, 1, (FP32_DIRECT_DEFAULT & 1), 1>(Wqkv, bqkv, wb, w, s, hk);   // quarter fragments + bias table (80 VGPRs)
-#else
-    else if (active_tiles(w.L) > DIET_MIN_TILES) launch_qkv_t<QkvTileW8, 0, 1, (FP32_DIRECT_DEFAULT & 1), 1>(Wqkv, bqkv, wb, w, s, hk);
-#endif
-#ifdef GATSSPG_TUNING
-    else if (!(fp32_direct() & 1)) launch_qkv_t<QkvTileW8, 0>(Wqkv, bqkv, wb, w, s, hk);
-#endif
-    else launch_qkv_t<QkvTileW8, 0, 0, (FP32_DIRECT_DEFAULT & 1)>(Wqkv, bqkv, wb, w, s, hk);   // small launches: the two-half fragment loop
+    else if (active_tiles(w.L) > diet_min_tiles()) launch_qkv_t<QkvTileW8, 0, 1, 1, 1>(Wqkv, bqkv, wb, w, s, hk);   // quarter fragments + bias table (80 VGPRs)
+    else launch_qkv_t<QkvTileW8, 0, 0, 1>(Wqkv, bqkv, wb, w, s, hk);   // small launches: the two-half fragment loop
 }
 
 void launch_kv_final(const float* W0, const Workspace& w, int cross, const float* kv_src, hipStream_t s, ProfileHook* hk) {
-    static const int abl = tuning_knob("KVF_ABL", 0);   // tuning builds: timing-only ablations of the operator phase
-    // one workgroup per d block by default since round 4: every partial read once (interleaved A/B, profiles/r04_ab_live_kv_final.txt: kernel
-    // 11.4 -> 10.5 us event-timed, +0.7 ... +1.6 % frames/s in flight at the three shapes, bit-identical results); KVF_RS=2: the two-row-half form
-    // (round 6, second experiment: the projection SPLIT in two launches -- first the four [K_h ; V_h] row tiles (504 workgroups: one round of
-    //  the 512 resident slots), then ONE grid holding the two Q row tiles and kv_final's workgroups in the narrow 512-thread form -- so that the
-    //  reduction + message operator runs beside the Q tiles instead of in front of mlp.0.  Bit-identical.  Event-timed at the headline shape:
-    //  27.5 + 21.6 us against 39.2 + 11.8 us for the classic pair, frame 0.9948 vs 0.9942 ms, 1264 vs 1266 frames/s in flight; 500 x 2000:
-    //  0.626 vs 0.567 ms.  One Q tile per CU is a single workgroup's dependent chain (17 us for 8 slabs), not a matrix-pipe load: what the
-    //  hidden kv_final saves the lonely Q tiles give back.  With kv_final's workgroups FIRST in the grid they took both slots of half the
-    //  CUs and the Q tiles paired up on the rest: 1.046 ms.  profiles/r06e_*, r06f_*; removed.)
-    // (round 6: a narrow form -- two d rows per workgroup, 264 workgroups of 512 threads so that every CU pulls partials -- was built, verified
-    //  bit-identical and A/B-timed: 11.85 vs 11.22 us event-timed, 994.8 vs 1001.1 frames/s one at a time; the reduction is not bound by
-    //  what one CU can have in flight.  profiles/r06c_ab_live_kvf_narrow_*.txt; removed)
-    if (tuning_knob("KVF_RS", 1) == 1) {
-        GATSSPG_LAUNCH(hk, KID_KV_FINAL, s, kv_final_kernel<1>, dim3(17, w.nseg * H), dim3(1024), 0, s, w.kvpart, kv_src, w.kvfin, W0, w.Mop, w.Mpl,
-                       w.ksumT, w.zsc, w.statcnt, W0 - AttnW::W0 + AttnW::SC, w.L, cross, w.prec, abl);
-        return;
-    }
-    GATSSPG_LAUNCH(hk, KID_KV_FINAL, s, kv_final_kernel<2>, dim3(33, w.nseg * H), dim3(1024), 0, s, w.kvpart, kv_src, w.kvfin,
-                   W0, w.Mop, w.Mpl, w.ksumT, w.zsc, w.statcnt, W0 - AttnW::W0 + AttnW::SC, w.L, cross, w.prec, abl);
+    // one workgroup per d block since round 4: every partial read once (interleaved A/B, profiles/r04_ab_live_kv_final.txt: kernel
+    // 11.4 -> 10.5 us event-timed, +0.7 ... +1.6 % frames/s in flight at the three shapes, bit-identical results; the two-row-part form is removed).
+    // (round 6: the projection split in two launches so that kv_final runs beside the Q tiles -- 1264 vs 1266 frames/s in flight,
+    //  profiles/r06e_*, r06f_* -- and a narrow 512-thread form -- 11.85 vs 11.22 us, profiles/r06c_ab_live_kvf_narrow_*.txt -- both removed)
+    GATSSPG_LAUNCH(hk, KID_KV_FINAL, s, kv_final_kernel<1>, dim3(17, w.nseg * H), dim3(1024), 0, s, w.kvpart, kv_src, w.kvfin, W0, w.Mop, w.Mpl,
+                   w.ksumT, w.zsc, w.statcnt, W0 - AttnW::W0 + AttnW::SC, w.L, cross, w.prec, 0);
 }
 
-template <class T, int ABL, int PREC, int BT = 0, int QF = 0, int SF = 0>
-static void launch_mlp0_body(const float* W0, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s,
-                             ProfileHook* hk);
-template <class T, int ABL, int PREC, int BT = 0, int QF = 0>
+// SF: the fused InstanceNorm reducer (stat_last_block) compiled in as a branch that never runs (statcnt = nullptr).  The split-bf16
+// instantiations keep it: their register allocation sits at the 128 cap, and without the dead branch the six-term kernel picked up a
+// 12-byte spill -- they stay exactly the round-5 kernels.  (Finishing the statistics in the last workgroups instead of the stat_final launch:
+// 1231 vs 1232 frames/s in flight, 5.3 us longer mlp0 for the 4.8 us launch it saves, profiles/r04_stat_fused_ab.txt; removed.)
+template <class T, int PREC, int BT = 0, int QF = 0>
 static void launch_mlp0_t(const float* W0, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s,
                           ProfileHook* hk) {
-    // fp32: the reducer is compiled in only where it can run (tuning builds with GATSSPG_STAT_FUSED=1).  The split-bf16 instantiations keep it
-    // (never taken: statcnt stays nullptr): their register allocation sits at the 128 cap, and without the dead branch the six-term kernel
-    // picked up a 12-byte spill -- they stay exactly the round-5 kernels.
-    if constexpr (PREC != 0) {
-        launch_mlp0_body<T, ABL, PREC, BT, QF, 1>(W0, b0, wb, w, s, hk);
-    } else {
-#ifdef GATSSPG_TUNING
-        if (stat_fused()) return launch_mlp0_body<T, ABL, PREC, BT, QF, 1>(W0, b0, wb, w, s, hk);
-#endif
-        launch_mlp0_body<T, ABL, PREC, BT, QF, 0>(W0, b0, wb, w, s, hk);
-    }
-}
-template <class T, int ABL, int PREC, int BT, int QF, int SF>
-static void launch_mlp0_body(const float* W0, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s,
-                             ProfileHook* hk) {
-    allow_big_lds<mlp0_kernel<T, ABL, PREC, BT, QF, SF>>();
+    constexpr int SF = PREC != 0;
+    allow_big_lds<mlp0_kernel<T, PREC, BT, QF, SF>>();
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
-    GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, ABL, PREC, BT, QF, SF>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS),
+    GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, PREC, BT, QF, SF>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS),
                    (smem_bytes<T, PREC>() + sizeof(float) * AttnFoldHooks::ZP_FLOATS + 512 * BT), s, W0, b0,
                    wb ? wb + (PREC >= 3 ? AttnWB::W0_H16 : AttnWB::W0_HI) : nullptr, wb ? wb + (PREC >= 3 ? AttnWB::W0_L16 : AttnWB::W0_LO) : nullptr,
                    wb ? wb + AttnWB::W0_LO2 : nullptr, w.Z, w.Q, w.Mop, w.Mpl, w.ksumT, w.U,
-                   w.statpart, w.stats, (SF && stat_fused()) ? w.statcnt : nullptr, w.L, g_trace);
+                   w.statpart, w.stats, nullptr, w.L, g_trace);
 }
-template <class T, int ABL, int PREC, int DS = 0, int QF = 0>
+template <class T, int PREC, int DS = 0>
 static void launch_mlp3_t(const float* W3, const float* b3, const unsigned short* wb, const Workspace& w, hipStream_t s,
                           ProfileHook* hk) {
-    allow_big_lds<mlp3_kernel<T, ABL, PREC, DS, QF>>();
+    allow_big_lds<mlp3_kernel<T, PREC, DS>>();
     const int NT = active_tiles(w.L) / (T::BN / 64);
-    GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, ABL, PREC, DS, QF>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS),
+    GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, PREC, DS>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS),
                    (smem_bytes<T, PREC>()), s, W3, b3, wb ? wb + (PREC >= 3 ? AttnWB::W3_H16 : AttnWB::W3_HI) : nullptr,
                    wb ? wb + (PREC >= 3 ? AttnWB::W3_L16 : AttnWB::W3_LO) : nullptr, wb ? wb + AttnWB::W3_LO2 : nullptr, w.U,
                    w.stats, w.Z, w.L);
@@ -1197,58 +1124,23 @@ static void launch_mlp3_t(const float* W3, const float* b3, const unsigned short
 
 void launch_mlp(const float* W0, const float* b0, const float* W3, const float* b3, const unsigned short* wb, const Workspace& w,
                 hipStream_t s, ProfileHook* hk) {
-    // MLP0_TILE / MLP3_TILE / MLP0_BTILE select the alternative (equally correct) tile shapes in tuning builds; the ablation
-    // variants (wrong results, timing only) exist only in a -DGATSSPG_PROFILING_BUILD library.
-    static const int t0 = tuning_knob("MLP0_TILE", 0), t3 = tuning_knob("MLP3_TILE", 1);
-    // Launches that leave CUs empty (few columns: OnePose's own 500 x 2000 operating point) are bound by ONE workgroup's
-    // dependent MFMA chain, not by the matrix pipes: they take the 64x64 tile with the K loop split over two wave groups
-    // (4x / 2x the workgroups, half the chain per wave).  SMALL_NT = largest number of 64-column tiles that still does.
-    static const int small_nt0 = tuning_knob("SMALL_NT0", 0), small_nt3 = tuning_knob("SMALL_NT3", 64);
-    const bool small0 = w.prec == 0 && active_tiles(w.L) <= small_nt0, small3 = w.prec == 0 && active_tiles(w.L) <= small_nt3;
-    (void)t0;
-    const bool sp = split_loop_glds(w.prec);
+    // (profiling ablations of the fp32 main loop -- no global loads, no LDS writes, cache-hot panels, L1-hot loads, the loop cut to its
+    //  fixed cost -- were timed in round 5, profiles/r05d_trace_mlp0_*; removed)
+    static const int small_nt3 = tuning_knob("SMALL_NT3", SMALL_NT3);
+    const bool sp = w.prec >= 3;
     const float* sc = W0 - AttnW::W0 + AttnW::SC;
-    const int dma = fp32_dma(w);
-    if (dma & 2) launch_mlp0_dma(W0, b0, w, s, hk);
-    else if (sp) launch_mlp0_sp(sc, b0, wb, w, s, hk);
-    else if (small0 && t0 == 0) launch_mlp0_t<Mlp0TileS, 0, 0>(W0, b0, wb, w, s, hk);
-    else if (w.prec == 1) launch_mlp0_t<Mlp0TileW8, 0, 1>(W0, b0, wb, w, s, hk);
-    else if (w.prec == 2) launch_mlp0_t<Mlp0TileW8, 0, 2>(W0, b0, wb, w, s, hk);
-#ifdef GATSSPG_PROFILING_BUILD
-    else if (t0 == 11) launch_mlp0_t<Mlp0TileW8, 1, 0>(W0, b0, wb, w, s, hk);   // no global loads in the loop
-    else if (t0 == 12) launch_mlp0_t<Mlp0TileW8, 2, 0>(W0, b0, wb, w, s, hk);   // no loads, no LDS writes
-    else if (t0 == 15) launch_mlp0_t<Mlp0TileW8, 5, 0>(W0, b0, wb, w, s, hk);   // all workgroups stream the same (cache-hot) panels
-    else if (t0 == 16) launch_mlp0_t<Mlp0TileW8, 6, 0>(W0, b0, wb, w, s, hk);   // every load L1-hot
-#endif
-#ifdef GATSSPG_TUNING
-    else if (mlp0_diet() == 1) launch_mlp0_t<Mlp0TileW8, 0, 0, 0, 1>(W0, b0, wb, w, s, hk);   // quarter fragments, bias in registers (110 VGPRs)
-    else if (mlp0_diet() == 0 && fp32_bias_table()) launch_mlp0_t<Mlp0TileW8, 0, 0, 1>(W0, b0, wb, w, s, hk);
-    else if (mlp0_diet() == 0) launch_mlp0_t<Mlp0TileW8, 0, 0>(W0, b0, wb, w, s, hk);
-    else if (mlp0_diet() == 2 || active_tiles(w.L) > DIET_MIN_TILES) launch_mlp0_t<Mlp0TileW8, 0, 0, 1, 1>(W0, b0, wb, w, s, hk);
-#else
-    else if (active_tiles(w.L) > DIET_MIN_TILES) launch_mlp0_t<Mlp0TileW8, 0, 0, 1, 1>(W0, b0, wb, w, s, hk);   // quarter fragments + bias table (94 VGPRs)
-#endif
-    else launch_mlp0_t<Mlp0TileW8, 0, 0>(W0, b0, wb, w, s, hk);   // small launches: the two-half fragment loop (126 VGPRs)
-    // the InstanceNorm reducer is a launch of its own (stat_final_kernel: measured faster one frame at a time than finishing the statistics
-    // inside the mlp.0 launch by its last workgroups -- stat_last_block; that form is GATSSPG_STAT_FUSED=1 in tuning builds)
-    if (sp && !(dma & 2) && sp_ut_on(w.prec))
-        GATSSPG_LAUNCH(hk, KID_STAT_FINAL, s, stat_final_kernel<32>, dim3(w.nseg, 16), dim3(1024), 0, s, w.statpart, w.stats, w.L);
-    else if (!stat_fused()) GATSSPG_LAUNCH(hk, KID_STAT_FINAL, s, stat_final_kernel<MLP0_BN>, dim3(w.nseg, 8), dim3(1024), 0, s, w.statpart, w.stats, w.L);
-    if (dma & 4) launch_mlp3_dma(W3, b3, w, s, hk);
-    else if (sp) launch_mlp3_sp(sc, b3, wb, w, s, hk);
-    else if (small3 && t3 == 1) launch_mlp3_t<Mlp3TileS, 0, 0>(W3, b3, wb, w, s, hk);
-    else if (w.prec == 1 && t3 == 0) launch_mlp3_t<Mlp3Tile, 0, 1>(W3, b3, wb, w, s, hk);
-    else if (w.prec == 1) launch_mlp3_t<Mlp3TileTallW8, 0, 1>(W3, b3, wb, w, s, hk);
-    else if (w.prec == 2) launch_mlp3_t<Mlp3TileTallW8, 0, 2>(W3, b3, wb, w, s, hk);
-#ifdef GATSSPG_PROFILING_BUILD
-    else if (t3 == 13) launch_mlp3_t<Mlp3Tile, 3, 0>(W3, b3, wb, w, s, hk);   // steady-state loop cut: fixed cost only
-#endif
-#ifdef GATSSPG_TUNING
-    else if (t3 == 1 && mlp3_diet() == 1) launch_mlp3_t<Mlp3TileTallW8, 0, 0, ((FP32_DIRECT_DEFAULT >> 1) & 1), 1>(W3, b3, wb, w, s, hk);   // quarter fragments
-    else if (t3 == 1 && !(fp32_direct() & 2)) launch_mlp3_t<Mlp3TileTallW8, 0, 0>(W3, b3, wb, w, s, hk);
-#endif
-    else if (t3 == 1) launch_mlp3_t<Mlp3TileTallW8, 0, 0, ((FP32_DIRECT_DEFAULT >> 1) & 1)>(W3, b3, wb, w, s, hk);
-    else launch_mlp3_t<Mlp3Tile, 0, 0>(W3, b3, wb, w, s, hk);
+    if (sp) launch_mlp0_sp(sc, b0, wb, w, s, hk);
+    else if (w.prec == 1) launch_mlp0_t<Mlp0TileW8, 1>(W0, b0, wb, w, s, hk);
+    else if (w.prec == 2) launch_mlp0_t<Mlp0TileW8, 2>(W0, b0, wb, w, s, hk);
+    else if (active_tiles(w.L) > diet_min_tiles()) launch_mlp0_t<Mlp0TileW8, 0, 1, 1>(W0, b0, wb, w, s, hk);   // quarter fragments + bias table (94 VGPRs)
+    else launch_mlp0_t<Mlp0TileW8, 0>(W0, b0, wb, w, s, hk);   // small launches: the two-half fragment loop (126 VGPRs)
+    // the InstanceNorm reducer is a launch of its own (see launch_mlp0_t)
+    GATSSPG_LAUNCH(hk, KID_STAT_FINAL, s, stat_final_kernel<MLP0_BN>, dim3(w.nseg, 8), dim3(1024), 0, s, w.statpart, w.stats, w.L);
+    if (sp) launch_mlp3_sp(sc, b3, wb, w, s, hk);
+    else if (w.prec == 1) launch_mlp3_t<Mlp3TileTallW8, 1>(W3, b3, wb, w, s, hk);
+    else if (w.prec == 2) launch_mlp3_t<Mlp3TileTallW8, 2>(W3, b3, wb, w, s, hk);
+    else if (active_tiles(w.L) <= small_nt3) launch_mlp3_t<Mlp3TileS, 0>(W3, b3, wb, w, s, hk);
+    else launch_mlp3_t<Mlp3TileTallW8, 0, 1>(W3, b3, wb, w, s, hk);
 }
 
 void launch_final_proj_norm(const float* Wf, const float* bf, const Workspace& w, hipStream_t s, ProfileHook* hk) {
@@ -1257,12 +1149,8 @@ void launch_final_proj_norm(const float* Wf, const float* bf, const Workspace& w
                    (smem_bytes<FinalTile>()), s, Wf, bf, w.Z, w.MD, w.MDT, w.MDTp, score_on_split_loop(w.prec, 0) ? w.prec : 0, w.L);
 }
 
-static bool score_square() {
-    static const int t = tuning_knob("SCORE_TILE", 0);   // 0 (default): 128x64; 1 (tuning builds): 128x128
-    return t == 1;
-}
 int score_tile_rows() { return SC_BM; }
-int score_tile_cols() { return score_square() ? ScoreTileSq::BN : ScoreTileW8::BN; }
+int score_tile_cols() { return ScoreTileW8::BN; }
 
 template <class T, bool RAW>
 static void launch_score_t(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk) {
@@ -1272,21 +1160,14 @@ static void launch_score_t(const Workspace& w, float* conf, float scale, hipStre
                    (smem_bytes<T>()), s, w.MDT, w.MD, conf, w.rowpart, w.colpart, w.L, scale);
 }
 
-static bool score_square();
 // The fp32-class split modes (bf16x6: operands split exactly; fp16x4: the exact product of 22-bit operands) also run the score
 // contraction on the 16-bit pipe; the three-term modes keep the fp32 MFMA here (their 2^-16 / dropped-term error would sit directly on
-// the logits of the dual softmax).  The max-subtracting path (tiny scale factors) stays fp32 as well.
-bool score_on_split_loop(int prec, int shifted) {
-    const int on = tuning_knob("SCORE_SPLIT", 1);   // (read per launch: tools/ab_live.py)
-    return on != 0 && !shifted && (prec == 2 || prec == 4) && !score_square();   // (its partial sums are per 64-column tile)
-}
+// the logits of the dual softmax).  The max-subtracting path (tiny scale factors) stays fp32 as well.  (profiles/r04_score_split_ab.txt)
+bool score_on_split_loop(int prec, int shifted) { return !shifted && (prec == 2 || prec == 4); }
 
 void launch_score_exp(const Workspace& w, float* conf, float scale, int shifted, hipStream_t s, ProfileHook* hk) {
     if (score_on_split_loop(w.prec, shifted)) return launch_score_exp_sp(w, conf, scale, s, hk);
-    const bool sq = score_square();
-    if (shifted && sq) launch_score_t<ScoreTileSq, true>(w, conf, scale, s, hk);
-    else if (shifted) launch_score_t<ScoreTileW8, true>(w, conf, scale, s, hk);
-    else if (sq) launch_score_t<ScoreTileSq, false>(w, conf, scale, s, hk);
+    if (shifted) launch_score_t<ScoreTileW8, true>(w, conf, scale, s, hk);
     else launch_score_t<ScoreTileW8, false>(w, conf, scale, s, hk);
 }
 

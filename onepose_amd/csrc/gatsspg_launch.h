@@ -35,7 +35,8 @@ inline void hook_after(ProfileHook* h, int kid, hipStream_t s) {
 
 // Tuning knobs.  The product library has NO environment lookups: every knob is its compiled-in default.  A library built
 // with -DGATSSPG_TUNING (python -m onepose_amd.build_ext --tuning -> libgatsspg_hip_tuning.so, never loaded by the
-// package) reads GATSSPG_<NAME> from the environment once, for A/B runs of alternative tile shapes (tools/ab_tuning.py).
+// package) reads GATSSPG_<NAME> from the environment: only the shape thresholds that choose between two product kernels
+// (DIET_MIN_TILES, SMALL_NT3, SP_MLP0_WIDE_MIN / _MAX, SP_NST2).  Compile-time alternatives are A/B-timed as two builds (tools/ab_libs.py).
 int tuning_knob(const char* name, int dflt);
 
 // gatsspg_gemm_kernels.hip
@@ -60,18 +61,6 @@ void launch_mlp3_sp(const float* sc, const float* b3, const unsigned short* pack
 bool score_on_split_loop(int prec, int shifted);
 void launch_score_exp_sp(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk = nullptr);
 constexpr int SCORE_SPLIT_SCALE_LOG2 = 10;   // unit-norm descriptors (|x| <= 1) are multiplied by 2^10 before the fp16 split
-// the fp32 arithmetic (exact v_mfma_f32_32x32x2_f32) on the LDS-DMA loop: same kernels, MODE 0, the fp32 operators as the A operand
-void launch_qkv_kv_dma(const float* Wqkv, const float* bqkv, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
-void launch_mlp0_dma(const float* W0, const float* b0, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
-void launch_mlp3_dma(const float* W3, const float* b3, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
-// true if the split-precision launch goes to the kernels above (fp16 modes: always; bf16 modes: unless a tuning build says otherwise)
-bool split_loop_glds(int prec);
-// true (tuning builds, GATSSPG_STAT_FUSED=1): the InstanceNorm statistics are finished inside the mlp.0 launch by its last workgroups
-// (stat_last_block); the product path is the separate stat_final launch (measured faster one frame at a time: DESIGN.md 14e)
-bool stat_fused();
-// true: mlp.0 of the split loop writes U point-major (U^T [ld][512]) with InstanceNorm partials per 32-point strip and mlp.3 reads it as
-// a transposed B operand (fp16 modes; gatsspg_split_kernels.hip).  stat_final then merges 32-column partials.
-bool sp_ut_on(int prec);
 void launch_final_proj_norm(const float* Wf, const float* bf, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
 // shifted = 0: E = exp(S) into conf + row/col sum partials (|S| <= 80); 1: raw scores S into conf (max-subtracting path)
 void launch_score_exp(const Workspace& w, float* conf, float scale, int shifted, hipStream_t s, ProfileHook* hk = nullptr);

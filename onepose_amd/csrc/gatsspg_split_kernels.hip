@@ -58,9 +58,6 @@ __device__ __forceinline__ void load_bias16(const float* b, int row0, int wm, in
 // =====================================================================================================
 template <int MODE>
 using QkvSpTile = SpTile<128, 2, 2, 2, MODE>;
-// the exact fp32 MFMA on the same loop (MODE 0): 128 x 64 on 8 waves of 32 x 32 like the fp32 kernels of gatsspg_gemm_kernels.hip (two
-// workgroups per CU, <= 128 registers), three stages of 24 KiB
-using Fp32SpTile = SpTile<128, 4, 2, 3, 0>;
 
 // A plain output tile straight from the accumulators: in the 32 x 32 C layout a lane's 16 values of one product sit in ONE column
 // (lane & 31) and 16 rows, so each dword store instruction covers two rows x 32 consecutive columns = two full 128-byte lines --
@@ -79,8 +76,9 @@ __device__ __forceinline__ void store_tile_direct(const f32x16 (&acc)[T::TM][T::
         }
 }
 
-template <class T, int SCHED = 0, int EPI = 0>
-__global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : 3)) void qkv_kv_sp_kernel(const float* __restrict__ sc, const float* __restrict__ bqkv,
+// fp16 modes on the slot schedule (SCHED 4); the bias through an LDS table, the Q tiles stored straight from the accumulators
+template <class T>
+__global__ __launch_bounds__(T::THREADS, 3) void qkv_kv_sp_kernel(const float* __restrict__ sc, const float* __restrict__ bqkv,
                                                                 const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                                 const unsigned short* __restrict__ P2, const float* __restrict__ Z,
                                                                 float* __restrict__ Qbuf, float* __restrict__ kvpart, ColLayout L) {
@@ -93,38 +91,30 @@ __global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : 3)) void qkv_kv_sp_kernel
     const int c0 = ct * T::BN, ld = L.ld;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
-    constexpr bool BIAS_TAB = (EPI & 2) != 0;   // bias through an LDS table behind the ring (T::BM floats)
     static_assert(T::BM == 128, "one half piece of bias values");
-    float* btab = reinterpret_cast<float*>(smem_c + T::RING_BYTES);
+    float* btab = reinterpret_cast<float*>(smem_c + T::RING_BYTES);   // bias table behind the ring (T::BM floats)
     float bias[T::TM][16];
-    if constexpr (!BIAS_TAB) load_bias16<T>(bqkv, rt * 128, wm, half, bias);
     const float inv = T::F16 ? 1.f / (sc[0] * T::ACT_SCALE) : 1.f;
     f32x16 acc[T::TM][T::TN];
     const size_t ro = (size_t)rt * 128 * BK;
-    // 16-bit modes: slab-major planes; fp32 (MODE 0): P0 is the row-major fp32 operator [768][256] itself
-    auto apl = [&](int kt, int pl) -> const void* {
-        if constexpr (T::F32) return reinterpret_cast<const float*>(P0) + (size_t)rt * 128 * D + kt * BK;
-        else return (pl == 0 ? P0 : pl == 1 ? P1 : P2) + ro + (size_t)kt * 768 * BK;
-    };
+    // slab-major planes
+    auto apl = [&](int kt, int pl) -> const void* { return (pl == 0 ? P0 : pl == 1 ? P1 : P2) + ro + (size_t)kt * 768 * BK; };
     auto bsl = [&](int kt) { return Z + (size_t)kt * BK * ld + c0; };
     SpPlainHooks<true> hooks;
     SpNoBx nobx;
     auto pre = [&]() {
-        if constexpr (BIAS_TAB) {
-            if (wave == 0 && lane < 32) glds16(bqkv + rt * 128 + 4 * lane, btab);   // 128 floats: half a piece
-        }
+        if (wave == 0 && lane < 32) glds16(bqkv + rt * 128 + 4 * lane, btab);   // 128 floats: half a piece
     };
-    gemm_mainloop_sp<T, D / BK, decltype(apl), decltype(bsl), SpPlainHooks<true>, SpNoBx, 0, SCHED, decltype(pre)>(
-        reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld, hooks, nobx, nullptr, pre, false, T::F32 ? D * 4 : 64);
-    if constexpr (BIAS_TAB) read_bias16<T>(btab, wm, half, bias);
+    gemm_mainloop_sp<T, D / BK, decltype(apl), decltype(bsl), SpPlainHooks<true>, SpNoBx, 4, decltype(pre)>(
+        reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld, hooks, nobx, nullptr, pre, false, 64);
+    read_bias16<T>(btab, wm, half, bias);
 
     if (rt < 2) {
 #pragma unroll
         for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][0][r] = elu1_select(fmaf(acc[tm][0][r], inv, bias[tm][r])) + 1.f;
-        if constexpr (EPI & 1) store_tile_direct<T>(acc, Qbuf + (size_t)rt * 128 * ld + c0, ld, [](int, float v) { return v; });
-        else store_tile_via_lds<T>(acc, smem, Qbuf + (size_t)rt * 128 * ld + c0, ld, [](int, float v) { return v; });
+        store_tile_direct<T>(acc, Qbuf + (size_t)rt * 128 * ld + c0, ld, [](int, float v) { return v; });
         return;
     }
     // ---- K_h / V_h tile -> LDS -> KV partial (second MFMA pass, fp32: exact like the fp32 kernel's)
@@ -213,10 +203,7 @@ __global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : 3)) void qkv_kv_sp_kernel
 //     added over the head's four halves in a fixed order, the two lane halves combined by one exchange -- per-lane in exactly the
 //     32x32 C layout the fold needs, no LDS round trip.
 // =====================================================================================================
-// UT (transposed accumulators, SP_OPT_SWAP of the main loop: lane = channel, register r = point mfma_row(r, half) of the wave's 32-point
-// strip): the denominator of point p is still summed by lane l31 = p (the raw B values a lane holds are those of ITS point), so a fold
-// takes the factors of its registers' points from one rank-1 fp32 MFMA (z x 1: the accumulator layout of the tile itself).
-template <int TM, bool UT = false>
+template <int TM>
 struct AttnFoldSp {
     static constexpr bool ENABLED = true;
     static constexpr int SPLIT = 8;
@@ -251,25 +238,10 @@ struct AttnFoldSp {
         const float o = __shfl_xor(d, 32);
         d = half ? o + d : d + o;   // lane half 0's partial first on both halves
         const float z = zfac[HD] / (d + 1e-6f);
-        if constexpr (!UT) {
 #pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
+        for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) kept[tm][r] = fmaf(z, hacc[HD & 1][tm][r], kept[tm][r]);
-        } else {
-            // register r of a lane holds point mfma_row(r, half) of the strip; the factor of point p sits in lane p.  ONE fp32 MFMA hands
-            // every lane the 16 factors of its registers' points: D[i][j] = sum_k A[i][k] B[k][j] with A[i][0] = z_i, B[0][j] = 1 (k = 1
-            // operands zero) = z_i for every column j, in the accumulator layout of the tile itself (exact: z * 1 + 0 * 0).  64 cycles of
-            // matrix pipe per head and wave instead of 2 v_readlane + 2 v_mov + 1 v_cndmask per register (measured: +1.4 % per frame).
-            f32x16 zm;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) zm[r] = 0.f;
-            zm = __builtin_amdgcn_mfma_f32_32x32x2f32(half ? 0.f : z, half ? 0.f : 1.f, zm, 0, 0, 0);
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) kept[tm][r] = fmaf(zm[r], hacc[HD & 1][tm][r], kept[tm][r]);
-        }
+            for (int r = 0; r < 16; ++r) kept[tm][r] = fmaf(z, hacc[HD & 1][tm][r], kept[tm][r]);
     }
     // head h - 1 is folded beside the first products of head h (its own products were issued a whole slab earlier)
     template <int I, int TM_>
@@ -282,15 +254,10 @@ template <int MODE>
 using Mlp0SpTileW = SpTile<128, 2, 4, 3, MODE>;   // 128 x 128 on 8 waves: 252 workgroups at the headline shape, one per CU, 96 KiB ring
 template <int MODE>
 using Mlp0SpTileN = SpTile<128, 2, 2, 3, MODE>;   // 128 x 64 on 4 waves: twice the workgroups (small shapes), two per CU
-template <int MODE>
-using Mlp0SpTileN2 = SpTile<128, 2, 2, 2, MODE>;  // the same on a two-stage ring (49 KiB): three workgroups per CU when the registers allow (<= 168)
-template <int MODE>
-using Mlp0SpTileW4 = SpTile<128, 2, 4, 4, MODE>;  // the 8-wave tile on a FOUR-stage ring (128 KiB): a slab has two and a half steps to land
-template <int MODE>
-using Mlp0SpTileT = SpTile<128, 1, 4, 3, MODE>;   // 128 x 128 on 4 waves, 128 x 32 per wave (one wave per SIMD, every B value split once)
 
-template <class T, int ABL = 0, int SCHED = 0, int EPI = 0>
-__global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : T::TM == 4 ? 1 : (T::WAVES == 4 && T::NST == 2) ? 3 : 2)) void mlp0_sp_kernel(const float* __restrict__ sc, const float* __restrict__ b0,
+// fp16 modes on the slot schedule (SCHED 4); the bias through an LDS table
+template <class T>
+__global__ __launch_bounds__(T::THREADS, (T::TM == 4 ? 1 : (T::WAVES == 4 && T::NST == 2) ? 3 : 2)) void mlp0_sp_kernel(const float* __restrict__ sc, const float* __restrict__ b0,
                                                               const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                               const unsigned short* __restrict__ P2, const float* __restrict__ Z,
                                                               const float* __restrict__ Qbuf, const unsigned short* __restrict__ Mpl,
@@ -317,33 +284,19 @@ __global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : T::TM == 4 ? 1 : (T::WAVE
     // (filled by ONE LDS-DMA piece in front of the first slab requests: no register hop, no wait of its own)
     // requested before the main loop (behind it the two dependent round trips would sit on the critical path: measured 3.9 k cycles of
     // a 39 k-cycle kernel); hipcc parks some of the 32 values in scratch across the loop, which costs two scratch instructions each
-    constexpr bool BIAS_TAB = (EPI & 2) != 0;   // bias through a second LDS table (T::BM floats behind the ksum table)
     static_assert(T::BM == 128, "one half piece of bias values");
-    float* btab = tab + 256;
+    float* btab = tab + 256;   // bias: a second LDS table (T::BM floats behind the ksum table)
     float bias[T::TM][16];
-    if constexpr (!BIAS_TAB) load_bias16<T>(b0, rt * T::BM, wm, half, bias);
     const float inv = T::F16 ? 1.f / (sc[1] * T::ACT_SCALE) : 1.f;
     f32x16 acc[T::TM][T::TN];
     const size_t ro = (size_t)rt * T::BM * BK;   // slab-major planes: (m, k) at ((k / 32) * 512 + m) * 32 + k % 32
     const unsigned short* Mh = Mpl + (size_t)ts.seg * 3 * MPL_PLANE + ro;
-    // 16-bit modes: slab-major planes of W0 (x half) and of the segment's message operator; fp32 (MODE 0): P0 = the fp32 [512][512] operator,
-    // Mpl = the fp32 operator block Mop (the segment's M_t at mop_seg(), row stride MOP_LD = 512 like W0)
+    // slab-major planes of W0 (x half) and of the segment's message operator
     auto apl = [&](int kt, int pl) -> const void* {
-        if constexpr (T::F32) {
-            const float* W0f = reinterpret_cast<const float*>(P0) + (size_t)rt * T::BM * 512;
-            const float* Mf = mop_seg(reinterpret_cast<const float*>(Mpl), ts.seg) + (size_t)rt * T::BM * MOP_LD;
-            return kt < 8 ? W0f + kt * BK : Mf + (kt - 8) * BK;
-        } else {
-            return kt < 8 ? (pl == 0 ? P0 : pl == 1 ? P1 : P2) + ro + (size_t)kt * 512 * BK
-                          : Mh + (size_t)pl * MPL_PLANE + (size_t)(kt - 8) * 512 * BK;
-        }
+        return kt < 8 ? (pl == 0 ? P0 : pl == 1 ? P1 : P2) + ro + (size_t)kt * 512 * BK : Mh + (size_t)pl * MPL_PLANE + (size_t)(kt - 8) * 512 * BK;
     };
     auto bsl = [&](int kt) { return (kt < 8 ? Z + (size_t)kt * BK * ld : Qbuf + (size_t)(kt - 8) * BK * ld) + c0; };
-    // EPI bit 3 (UT): transposed accumulators -- U leaves POINT-major (U^T [ld][512]: mlp3_sp reads 8 consecutive channels of a point
-    // with two 16-byte LDS reads) straight from the registers, and the InstanceNorm partials are summed inside a lane (one per 32-point
-    // strip of a wave): no staging tile, no barrier, no statistics walk behind the loop (round-4 trace: 9 k of a wave's 39.5 k cycles)
-    constexpr bool UT = (EPI & 8) != 0;
-    AttnFoldSp<T::TM, UT> hooks;
+    AttnFoldSp<T::TM> hooks;
     hooks.ks = tab; hooks.half = half;
     {
         const float4 zf = *reinterpret_cast<const float4*>(zsc + ts.seg * H);
@@ -352,75 +305,13 @@ __global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : T::TM == 4 ? 1 : (T::WAVE
     SpNoBx nobx;
     auto pre = [&]() {
         if (wave == 0) glds16(ksumT + (size_t)ts.seg * H * DH + 4 * lane, tab);   // [4][64] floats = 1 KiB
-        if constexpr (BIAS_TAB) {
-            if (wave == 1 && lane < 32) glds16(b0 + rt * T::BM + 4 * lane, btab);   // 128 floats: half a piece
-        }
+        if (wave == 1 && lane < 32) glds16(b0 + rt * T::BM + 4 * lane, btab);   // 128 floats: half a piece
     };
-    gemm_mainloop_sp<T, 512 / BK, decltype(apl), decltype(bsl), AttnFoldSp<T::TM, UT>, SpNoBx, ABL, SCHED, decltype(pre), (UT ? SP_OPT_SWAP : 0)>(
-        reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld, hooks, nobx, &tr, pre, SP_TRACE_ON(trace), T::F32 ? 512 * 4 : 64);
+    gemm_mainloop_sp<T, 512 / BK, decltype(apl), decltype(bsl), AttnFoldSp<T::TM>, SpNoBx, 4, decltype(pre)>(
+        reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld, hooks, nobx, &tr, pre, SP_TRACE_ON(trace), 64);
     if (SP_TRACE_ON(trace)) tr.t[9] = __builtin_readcyclecounter();    // behind the loop's last barrier
     hooks.template fold<3>(reinterpret_cast<f32x16(&)[T::TM]>(acc));
-    if constexpr (ABL & 32) {   // timing only: no epilogue at all (one store keeps the accumulators alive)
-        if (acc[0][0][0] == 123.456f) U[0] = acc[T::TM - 1][0][5];
-        return;
-    }
-    if constexpr (UT) {
-        static_assert(BIAS_TAB, "the transposed epilogue reads its bias (one value per lane and 32-channel block) from the LDS table");
-        // lane = channel ch[tm] of the workgroup's 128, register r = point pt0 + mfma_row(r, half) of this wave's 32-point strip
-        const int pt0 = wn * 32;
-        const int vw = min(max(ts.valid - pt0, 0), 32);   // real points of the strip
-        float* Ut = U + (size_t)(c0 + pt0) * 512 + rt * T::BM;
-        const size_t t32 = (size_t)(c0 + pt0) / 32;
-#pragma unroll
-        for (int tm = 0; tm < T::TM; ++tm) {
-            const int ch = (wm * T::TM + tm) * 32 + l31;
-            const float bch = btab[ch];
-            float u[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) u[r] = fmaf(acc[tm][0][r], inv, bch);
-            // a store instruction = two points x 32 consecutive channels = two full 128-byte lines of U^T
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if constexpr (ABL & 16) { if (u[r] == 123.456f) U[0] = u[r]; }
-                else Ut[(size_t)mfma_row(r, half) * 512 + ch] = u[r];
-            }
-            // (sum, pivot-shifted centred sum of squares) of the strip's real points: mlp0_kernel's partial on a 32-point tile, summed in
-            // the lane, the two lane halves combined by one exchange (half 0 first on both)
-            const float pivot = __shfl(u[0], l31);   // point pt0 (register 0 of lane half 0)
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float d = mfma_row(r, half) < vw ? u[r] - pivot : 0.f;
-                s1 += d;
-                s2 = fmaf(d, d, s2);
-            }
-            const float o1 = __shfl_xor(s1, 32), o2 = __shfl_xor(s2, 32);
-            s1 = half ? o1 + s1 : s1 + o1;
-            s2 = half ? o2 + s2 : s2 + o2;
-            if (half == 0) {
-                const float nv = (float)vw;
-                statpart[(t32 * 2 + 0) * 512 + rt * T::BM + ch] = nv * pivot + s1;
-                statpart[(t32 * 2 + 1) * 512 + rt * T::BM + ch] = nv > 0.f ? s2 - s1 * s1 / nv : 0.f;
-            }
-        }
-        if (SP_TRACE_ON(trace)) { tr.t[10] = tr.t[11] = tr.t[12] = __builtin_readcyclecounter(); }
-        (void)statcnt; (void)stats;
-        if (SP_TRACE_ON(trace) && lane == 0) {
-            unsigned long long* rr = trace + ((size_t)blockIdx.x * T::WAVES + wave) * 24;
-            rr[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-            rr[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-            rr[2] = t_entry;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) rr[3 + k] = tr.t[k];
-            rr[12] = __builtin_readcyclecounter();
-            rr[13] = rt; rr[14] = ct; rr[15] = wave;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rr[16 + k] = tr.t[9 + k];
-            rr[20] = w_entry; rr[21] = wall_clock64();
-        }
-        return;
-    }
-    if constexpr (BIAS_TAB) read_bias16<T>(btab, wm, half, bias);
+    read_bias16<T>(btab, wm, half, bias);
 
     // staging tile [BM][BN + 4]: the row stride (4 banks) keeps the scalar writes from the MFMA layout, the 16-byte row reads of the
     // store pass AND (with the walk skew below) the statistics reads free of bank conflicts (the [BN + 1] form of the fp32 kernel costs
@@ -450,8 +341,8 @@ __global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : T::TM == 4 ? 1 : (T::WAVE
         // the LPR lanes of a row start a multiple of 32 banks apart and rows are 4 banks apart: lane (row, q) starts its walk
         // q + LPR * ((row >> 3) mod (4 / LPR)) columns into its range, so that the 32 lanes of a read (32 / LPR rows) cover the 32 banks once
         static_assert(TS % 32 == 4, "walk skew of the statistics reads");
-        constexpr bool SKEWED = CPL == 32 && (LPR == 4 || LPR == 2);   // (the one-wave-per-SIMD tuning tile walks 64 columns per lane: unskewed)
-        const int skew = SKEWED ? q + (LPR == 2 ? 2 * ((row >> 3) & 1) : 0) : 0;
+        static_assert(CPL == 32 && (LPR == 4 || LPR == 2), "walk skew of the statistics reads");
+        const int skew = q + (LPR == 2 ? 2 * ((row >> 3) & 1) : 0);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int m0 = 0; m0 < CPL; ++m0) {
@@ -479,27 +370,17 @@ __global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : T::TM == 4 ? 1 : (T::WAVE
         for (int idx = tid; idx < T::BM * (T::BN / 4); idx += T::THREADS) {
             const int row = idx / (T::BN / 4), c4 = (idx % (T::BN / 4)) * 4;
             const vf4 v = *reinterpret_cast<const vf4*>(Tl + row * TS + c4);
-            if constexpr (ABL & 16) {   // timing only: no global stores of the tile
-                if (v[0] == 123.456f) U[0] = v[1];
-            } else {
-                *reinterpret_cast<vf4*>(U + (size_t)(rt * T::BM + row) * ld + c0 + c4) = v;
-            }
+            *reinterpret_cast<vf4*>(U + (size_t)(rt * T::BM + row) * ld + c0 + c4) = v;
         }
     };
-    if constexpr (EPI & 1) {   // (stat_final launch only) the tile's stores drain while the statistics are summed
-        tile_stores();
-        asm volatile("" ::: "memory");
-        tile_statistics();
-    } else {
-        // the partial stores go first; the tile's own stores follow them and may still be in flight when the ticket is drawn
-        tile_statistics();
-        asm volatile("" ::: "memory");
-        tile_stores();
-    }
+    // the partial stores go first; the tile's own stores follow them
+    tile_statistics();
+    asm volatile("" ::: "memory");
+    tile_stores();
     if (SP_TRACE_ON(trace)) tr.t[12] = __builtin_readcyclecounter();   // tile stores issued
     constexpr int TILE_STORES = T::BM * (T::BN / 4) / T::THREADS;   // per thread, behind its partial stores
     static_assert(T::BM * (T::BN / 4) % T::THREADS == 0, "whole stores per thread");
-    if (statcnt) stat_last_block<T, TILE_STORES>(statpart, stats, statcnt, L, ts, rt, smem);   // (nullptr: tuning builds with the stat_final launch)
+    if (statcnt) stat_last_block<T, TILE_STORES>(statpart, stats, statcnt, L, ts, rt, smem);   // (never taken, statcnt = nullptr: kept so that the kernel's code is unchanged)
     if (SP_TRACE_ON(trace) && lane == 0) {   // 24 x u64 per wave: [hw_id, xcc_id, t_entry, t[0..8], t_end, rt, ct, wave, t[9..12], wall clock at entry / exit]
         unsigned long long* r = trace + ((size_t)blockIdx.x * T::WAVES + wave) * 24;
         r[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
@@ -540,8 +421,9 @@ struct InstNormBx {
     __device__ __forceinline__ float apply(float v, float2 ms) const { return fmaxf((v - ms.x) * ms.y, 0.f); }
 };
 
-template <class T, int SCHED = 0, int EPI = 0>
-__global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : T::NST == 2 ? 3 : 2)) void mlp3_sp_kernel(const float* __restrict__ sc, const float* __restrict__ b3,
+// fp16 modes on the slot schedule (SCHED 4); the tile stored straight from the accumulators
+template <class T>
+__global__ __launch_bounds__(T::THREADS, (T::NST == 2 ? 3 : 2)) void mlp3_sp_kernel(const float* __restrict__ sc, const float* __restrict__ b3,
                                                               const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                               const unsigned short* __restrict__ P2, const float* __restrict__ U,
                                                               const float* __restrict__ stats, float* __restrict__ Z, ColLayout L) {
@@ -576,23 +458,17 @@ __global__ __launch_bounds__(T::THREADS, (T::F32 ? 4 : T::NST == 2 ? 3 : 2)) voi
             }
     }
     const size_t ro = (size_t)rt * T::BM * BK;
-    auto apl = [&](int kt, int pl) -> const void* {
-        if constexpr (T::F32) return reinterpret_cast<const float*>(P0) + (size_t)rt * T::BM * 512 + kt * BK;   // fp32 W3 [256][512]
-        else return (pl == 0 ? P0 : pl == 1 ? P1 : P2) + ro + (size_t)kt * 256 * BK;
-    };
-    // EPI bit 3 (BT): U arrives point-major (U^T [ld][512], written by mlp0_sp's transposed epilogue): SP_OPT_BT of the main loop
-    constexpr bool BT = (EPI & 8) != 0;
-    auto bsl = [&](int kt) { return BT ? U + (size_t)c0 * 512 + kt * BK : U + (size_t)kt * BK * ld + c0; };
+    auto apl = [&](int kt, int pl) -> const void* { return (pl == 0 ? P0 : pl == 1 ? P1 : P2) + ro + (size_t)kt * 256 * BK; };
+    auto bsl = [&](int kt) { return U + (size_t)kt * BK * ld + c0; };
     SpPlainHooks<false> hooks;
     InstNormBx bx;
     bx.tab = tab;
     auto pre = [&]() {
         if (wave < 4) glds16(stats + (size_t)ts.seg * 2 * 512 + wave * 256 + 4 * lane, tab + wave * 256);
     };
-    gemm_mainloop_sp<T, 512 / BK, decltype(apl), decltype(bsl), SpPlainHooks<false>, InstNormBx, 0, SCHED, decltype(pre), (BT ? SP_OPT_BT : 0)>(
-        reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, BT ? 512 : ld, hooks, bx, nullptr, pre, false, T::F32 ? 512 * 4 : 64);
-    if constexpr (EPI & 1) store_tile_direct<T>(acc, Z + (size_t)rt * T::BM * ld + c0, ld, [inv](int, float v) { return v * inv; });
-    else store_tile_via_lds<T>(acc, smem, Z + (size_t)rt * T::BM * ld + c0, ld, [inv](int, float v) { return v * inv; });
+    gemm_mainloop_sp<T, 512 / BK, decltype(apl), decltype(bsl), SpPlainHooks<false>, InstNormBx, 4, decltype(pre)>(
+        reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld, hooks, bx, nullptr, pre, false, 64);
+    store_tile_direct<T>(acc, Z + (size_t)rt * T::BM * ld + c0, ld, [inv](int, float v) { return v * inv; });
 }
 
 // =====================================================================================================
@@ -627,7 +503,7 @@ __global__ __launch_bounds__(T::THREADS, 3) void score_exp_sp_kernel(const unsig
     SpPlainHooks<true> hooks;
     SpNoBx nobx;
     constexpr int SS = T::F16 ? 4 : 0;   // fp16x4: the slot schedule (gemm_split_glds.h); bf16x6: the plain one
-    gemm_mainloop_sp<T, D / BK, decltype(apl), decltype(bsl), SpPlainHooks<true>, SpNoBx, 0, SS>(reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld,
+    gemm_mainloop_sp<T, D / BK, decltype(apl), decltype(bsl), SpPlainHooks<true>, SpNoBx, SS>(reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld,
                                                                                                 hooks, nobx);
     const float inv = T::F16 ? 1.f / (T::ACT_SCALE * T::ACT_SCALE) : 1.f;   // both operands carry the scale
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -704,271 +580,86 @@ void launch_score_exp_sp(const Workspace& w, float* conf, float scale, hipStream
     else launch_score_sp_t<4>(w, conf, scale, s, hk);
 }
 
-struct PlaneSet {
-    const unsigned short *p0, *p1, *p2;
-};
-static PlaneSet planes(const unsigned short* wb, int prec, size_t hi, size_t lo, size_t lo2, size_t h16, size_t l16) {
-    if (prec >= 3) return {wb + h16, wb + l16, wb + l16};
-    return {wb + hi, wb + lo, wb + lo2};
-}
+// The product runs the fp16 modes on the slot schedule (SCHED 4, gemm_split_glds.h) with the bias through an LDS table and the Q / mlp3 tiles
+// stored straight from the accumulators, and the bf16x6 score contraction on the plain schedule (SCHED 0).  Removed alternatives, each
+// measured and lost: schedules 0 / 2 / 3 for the three GEMMs (profiles/r04_ab_live_schedules.txt, r04_ab_live_slot_schedule.txt: 2 is 1.0-1.4 %
+// faster per frame than 0, 3 another 1.0-1.6 %, 4 another 0.4 %), the ping-pong schedule, staged tile stores (r04_ab_live_direct_store.txt:
+// -0.5 % per frame), per-lane bias loads (r04_ab_live_bias_table.txt), the four-stage ring and the two-stage / one-wave-per-SIMD mlp0 tiles
+// (r04_ab_live_footprints.txt, r04_trace_sp_trace_*.txt), the main-loop ablations (r04_split_loop_ablations.txt), the bf16 modes and the
+// fp32 arithmetic on this loop (r04_split_loop_ab.txt, r04_ab_live_fp32_dma.txt).
 
-// schedule of the split loop in the fp16 modes (gemm_split_glds.h): 4 (default) = the slot schedule -- every MFMA of a step carries its share of the
-// step's VALU work, DMA requests and LDS reads, fenced slot by slot; 3 = the same with the next slab's reads in two bursts; 2 = DMA requests spread over
-// the step, split work left to hipcc's grouping; 0 = DMA requests in one burst behind the barrier; 1 = ping-pong wave groups.
-// The PRODUCT library instantiates only what it runs: the fp16 modes on schedule 4 with direct stores (and the score kernel).  Every alternative --
-// other schedules, staged stores, ring depths, the bf16 modes and the exact fp32 arithmetic on this loop, the timing ablations -- is compiled into the
-// tuning build only (TUNING_BUILD), where the knobs below are read from the environment per launch (tools/ab_live.py flips them inside one process).
-#ifdef GATSSPG_TUNING
-constexpr bool TUNING_BUILD = true;
-#else
-constexpr bool TUNING_BUILD = false;
-#endif
-constexpr int SP_SCHED_DEFAULT = 4;          // profiles/r04_ab_live_*.txt: 2 is 1.0-1.4 % faster per frame than 0, 3 another 1.0-1.6 %, 4 another 0.4 %
-constexpr int SP_DIRECT_STORE_DEFAULT = 3;   // bit 0 the Q tiles of qkv_kv, bit 1 mlp3 leave straight from the accumulators (+0.5 % per frame); bit 2 = mlp0's
-                                             // tile stores in front of its statistics (neutral)
-static int sp_direct_store() { return tuning_knob("SP_DIRECT_STORE", SP_DIRECT_STORE_DEFAULT); }
-static int sp_sched() { return tuning_knob("SP_SCHED", SP_SCHED_DEFAULT); }
-// 1: qkv_kv / mlp0 read their bias from an LDS table filled by one LDS-DMA piece (no global loads in front of the first slab requests); 0: per-lane
-// 16-byte global loads before the loop (schedule 4 only; the other schedules keep the loads)
-static int sp_bias_table() { return tuning_knob("SP_BIAS_TABLE", 1); }
-// fp16 modes, TUNING BUILDS ONLY (GATSSPG_SP_UT=1): mlp.0 leaves U point-major from TRANSPOSED accumulators (swapped MFMA operands: no staging tile,
-// no barrier, InstanceNorm partials summed inside a lane per 32-point strip) and mlp.3 reads it as a transposed B operand (two 16-byte LDS reads
-// per k16 half instead of eight 4-byte ones).  Built, parity-green (zero arg-max flips, the same conf error) and measured in round 5
-// (profiles/r05c_ab_live_ut_xcd_direct.txt, settings interleaved in one process): mlp0 23.5 vs 23.8 us event-timed, mlp3 16.7 vs 16.9 -- but
-// 0.693 vs 0.688 ms per frame and 1908 vs 1925 frames/s in flight: the transposed fold needs the per-point factor in 16 registers (one rank-1
-// fp32 MFMA per head), the kernel holds 237-243 registers instead of 192 (no other frame's wave fits beside it) and stat_final merges twice the
-// partials.  The product library runs the channel-major pair; the alternative schedules / tiles / ablations exist in that form only.
-bool sp_ut_on(int prec) {
-    if constexpr (!TUNING_BUILD) return false;
-    if (prec < 3) return false;
-    const int nst2 = tuning_knob("SP_NST2", -1);
-    if (sp_sched() != 4 || !sp_bias_table() || (sp_direct_store() & 2) == 0 || tuning_knob("SP_ABL", 0) != 0 || (nst2 > 0 && (nst2 & 1)) || stat_fused())
-        return false;
-    return tuning_knob("SP_UT", 0) != 0;
-}
-
-// mlp0's tile choice (launch_mlp0_sp_m) and, from it, the XCD granule of the 64-column kernels beside it: with the 128-column mlp0 tile an XCD
-// can own PAIRS of 64-column tiles in qkv_kv / mlp3 as well, so that a column range stays on the XCD (= the L2) that produced it across
-// mlp3 -> qkv_kv -> mlp0 -> mlp3.  Measured (profiles/r05c_ab_live_ut_xcd_direct.txt, interleaved in one process): no effect (0.6927 vs 0.6928 ms per
-// frame, 1912 vs 1908 frames/s in flight) -- the operands of these launches are not waiting for a remote L2.  Off; GATSSPG_SP_XCD_PAIR=1 in tuning builds.
+// mlp0's tile choice: the 128-column tile (8 waves, one workgroup per CU) moves two thirds of the operand bytes per product through L2: taken
+// when its 4 x tiles workgroups make ONE round of the 256 CUs and fill at least three quarters of it (the headline shape: 252); with fewer the
+// 64-column tile (4 waves, two workgroups per CU, twice as many) fills the chip better, with more than one round its co-resident pairs overlap
+// one workgroup's store tail with the other's loop (fp16x4, 8 frames per step: 173 vs 185 us per launch)
+constexpr int SP_MLP0_WIDE_MIN = 48, SP_MLP0_WIDE_MAX = 64;
 static bool mlp0_sp_wide(const ColLayout& L) {
-    const int wide_min = tuning_knob("SP_MLP0_WIDE_MIN", 48), wide_max = tuning_knob("SP_MLP0_WIDE_MAX", 64);
+    const int wide_min = tuning_knob("SP_MLP0_WIDE_MIN", SP_MLP0_WIDE_MIN), wide_max = tuning_knob("SP_MLP0_WIDE_MAX", SP_MLP0_WIDE_MAX);
     return active_tiles(L) / 2 >= wide_min && active_tiles(L) / 2 <= wide_max;
 }
-static ColLayout sp_paired_layout(const ColLayout& L0, int prec) {
-    ColLayout L = L0;
-    L.xgs = (prec >= 3 && mlp0_sp_wide(L0) && tuning_knob("SP_XCD_PAIR", 0) != 0) ? 1 : 0;
-    return L;
-}
+// (mlp.0 leaving U point-major from transposed accumulators, read by mlp.3 as a transposed B operand: 1908 vs 1925 frames/s in flight, 237-243
+//  registers instead of 192; and XCD-paired column tiles beside the 128-column mlp0 tile: no effect, 1912 vs 1908.  profiles/r05c_ab_live_ut_xcd_direct.txt;
+//  both removed.  ColLayout::xgs stays 0: the kernels still read it, so that their code is unchanged.)
 
-template <class T, int SCHED, int EPI>
-static void launch_qkv_sp_v(const float* sc, const float* bqkv, const PlaneSet& p, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    allow_big_lds_sp<qkv_kv_sp_kernel<T, SCHED, EPI>>();
-    const ColLayout L = sp_paired_layout(w.L, T::MODE);
-    GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_sp_kernel<T, SCHED, EPI>), dim3(xcd_grid_g(6, active_tiles(L), L.xgs)), dim3(T::THREADS), (size_t)T::RING_BYTES + 1024, s,
-                   sc, bqkv, p.p0, p.p1, p.p2, w.Z, w.Q, w.kvpart, L);
-}
+struct PlaneSet {
+    const unsigned short *p0, *p1;
+};
+static PlaneSet planes(const unsigned short* wb, size_t h16, size_t l16) { return {wb + h16, wb + l16}; }
+
 template <int MODE>
 static void launch_qkv_sp_t(const float* sc, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     using T = QkvSpTile<MODE>;
-    const PlaneSet p = planes(wb, MODE, AttnWB::QKV_HI, AttnWB::QKV_LO, AttnWB::QKV_LO2, AttnWB::QKV_H16, AttnWB::QKV_L16);
-    if constexpr (MODE >= 3) {
-        if constexpr (TUNING_BUILD) {
-            const bool direct = sp_direct_store() & 1;
-            switch (sp_sched()) {
-                case 4:
-                    if (!direct) return launch_qkv_sp_v<T, 4, 0>(sc, bqkv, p, w, s, hk);
-                    if (!sp_bias_table()) return launch_qkv_sp_v<T, 4, 1>(sc, bqkv, p, w, s, hk);
-                    break;
-                case 3: return launch_qkv_sp_v<T, 3, 1>(sc, bqkv, p, w, s, hk);
-                case 2: return direct ? launch_qkv_sp_v<T, 2, 1>(sc, bqkv, p, w, s, hk) : launch_qkv_sp_v<T, 2, 0>(sc, bqkv, p, w, s, hk);
-                default: return launch_qkv_sp_v<T, 0, 0>(sc, bqkv, p, w, s, hk);
-            }
-        }
-        launch_qkv_sp_v<T, SP_SCHED_DEFAULT, 3>(sc, bqkv, p, w, s, hk);   // direct Q stores, bias through its LDS table
-    } else {
-        launch_qkv_sp_v<T, 0, 0>(sc, bqkv, p, w, s, hk);   // bf16 modes (tuning builds: GATSSPG_SPLIT_LOOP_BF16X3 / _BF16X6)
-    }
+    const PlaneSet p = planes(wb, AttnWB::QKV_H16, AttnWB::QKV_L16);
+    allow_big_lds_sp<qkv_kv_sp_kernel<T>>();
+    GATSSPG_LAUNCH(hk, KID_QKV_KV, s, qkv_kv_sp_kernel<T>, dim3(xcd_grid(6, active_tiles(w.L))), dim3(T::THREADS), (size_t)T::RING_BYTES + 1024, s,
+                   sc, bqkv, p.p0, p.p1, p.p1, w.Z, w.Q, w.kvpart, w.L);
 }
 void launch_qkv_kv_sp(const float* sc, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    switch (w.prec) {
-#ifdef GATSSPG_TUNING
-        case 1: launch_qkv_sp_t<1>(sc, bqkv, wb, w, s, hk); break;
-        case 2: launch_qkv_sp_t<2>(sc, bqkv, wb, w, s, hk); break;
-#endif
-        case 3: launch_qkv_sp_t<3>(sc, bqkv, wb, w, s, hk); break;
-        default: launch_qkv_sp_t<4>(sc, bqkv, wb, w, s, hk); break;
-    }
-}
-// fp32 (MODE 0) on this loop: the operators are the fp32 matrices themselves.  Tuning builds only (GATSSPG_FP32_DMA; measured 8 % slower per frame
-// than the register-staged fp32 loop of gemm_f32_mfma.h): the product library never calls these.
-void launch_qkv_kv_dma(const float* Wqkv, const float* bqkv, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-#ifdef GATSSPG_TUNING
-    using T = Fp32SpTile;
-    allow_big_lds_sp<qkv_kv_sp_kernel<T, 2>>();
-    GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_sp_kernel<T, 2>), dim3(xcd_grid(6, active_tiles(w.L))), dim3(T::THREADS), (size_t)T::RING_BYTES + 1024, s, Wqkv,
-                   bqkv, reinterpret_cast<const unsigned short*>(Wqkv), nullptr, nullptr, w.Z, w.Q, w.kvpart, w.L);
-#else
-    (void)Wqkv; (void)bqkv; (void)w; (void)s; (void)hk;
-#endif
-}
-void launch_mlp0_dma(const float* W0, const float* b0, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-#ifdef GATSSPG_TUNING
-    using T = Fp32SpTile;
-    allow_big_lds_sp<mlp0_sp_kernel<T, 0, 2>>();
-    GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_sp_kernel<T, 0, 2>), dim3(xcd_grid(512 / T::BM, active_tiles(w.L))), dim3(T::THREADS),
-                   (size_t)T::RING_BYTES + 2048, s, W0, b0, reinterpret_cast<const unsigned short*>(W0), nullptr, nullptr, w.Z, w.Q,
-                   reinterpret_cast<const unsigned short*>(w.Mop), w.ksumT, w.zsc, w.U, w.statpart, w.stats, stat_fused() ? w.statcnt : nullptr, w.L, g_trace);
-#else
-    (void)W0; (void)b0; (void)w; (void)s; (void)hk;
-#endif
-}
-void launch_mlp3_dma(const float* W3, const float* b3, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-#ifdef GATSSPG_TUNING
-    using T = Fp32SpTile;
-    allow_big_lds_sp<mlp3_sp_kernel<T, 2>>();
-    GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_sp_kernel<T, 2>), dim3(xcd_grid(256 / T::BM, active_tiles(w.L))), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s,
-                   W3, b3, reinterpret_cast<const unsigned short*>(W3), nullptr, nullptr, w.U, w.stats, w.Z, w.L);
-#else
-    (void)W3; (void)b3; (void)w; (void)s; (void)hk;
-#endif
+    if (w.prec == 3) launch_qkv_sp_t<3>(sc, bqkv, wb, w, s, hk);
+    else launch_qkv_sp_t<4>(sc, bqkv, wb, w, s, hk);
 }
 
-template <class T, int ABL = 0, int SCHED = 0, int EPI = 0>
+template <class T>
 static void launch_mlp0_sp_t(const float* sc, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    const PlaneSet p = planes(wb, T::MODE, AttnWB::W0_HI, AttnWB::W0_LO, AttnWB::W0_LO2, AttnWB::W0_H16, AttnWB::W0_L16);
+    const PlaneSet p = planes(wb, AttnWB::W0_H16, AttnWB::W0_L16);
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
-    allow_big_lds_sp<mlp0_sp_kernel<T, ABL, SCHED, EPI>>();
-    GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_sp_kernel<T, ABL, SCHED, EPI>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 2048, s, sc, b0,
-                   p.p0, p.p1, p.p2, w.Z, w.Q, w.Mpl, w.ksumT, w.zsc, w.U, w.statpart, w.stats, (!(EPI & 1) && stat_fused()) ? w.statcnt : nullptr, w.L, g_trace);
+    allow_big_lds_sp<mlp0_sp_kernel<T>>();
+    GATSSPG_LAUNCH(hk, KID_MLP0, s, mlp0_sp_kernel<T>, dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 2048, s, sc, b0,
+                   p.p0, p.p1, p.p1, w.Z, w.Q, w.Mpl, w.ksumT, w.zsc, w.U, w.statpart, w.stats, nullptr, w.L, g_trace);
 }
 template <int MODE>
 static void launch_mlp0_sp_m(const float* sc, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    // the 128-column tile (8 waves, one workgroup per CU) moves two thirds of the operand bytes per product through L2: taken when
-    // its 4 x tiles workgroups make ONE round of the 256 CUs and fill at least three quarters of it (the headline shape: 252); with
-    // fewer the 64-column tile (4 waves, two workgroups per CU, twice as many) fills the chip better, with more than one round its
-    // co-resident pairs overlap one workgroup's store tail with the other's loop (fp16x4, 8 frames per step: 173 vs 185 us per launch)
-    const bool wide = mlp0_sp_wide(w.L);
-    if constexpr (TUNING_BUILD) {
-        if constexpr (MODE == 4) {   // timing-only ablations of the main loop (wrong results) and the alternative tiles
-            switch (tuning_knob("SP_ABL", 0)) {
-                case 1: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 1>(sc, b0, wb, w, s, hk);     // no DMA after the prologue
-                case 2: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 2>(sc, b0, wb, w, s, hk);     // no MFMAs
-                case 4: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 4>(sc, b0, wb, w, s, hk);     // no split VALU
-                case 8: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 8>(sc, b0, wb, w, s, hk);     // no fragment reads
-                case 14: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 14>(sc, b0, wb, w, s, hk);   // DMA + barriers only
-                case 13: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 13>(sc, b0, wb, w, s, hk);   // MFMAs + barriers only
-                case 15: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 15>(sc, b0, wb, w, s, hk);   // barriers only (+ prologue, epilogue)
-                case 9: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 9>(sc, b0, wb, w, s, hk);     // no DMA, no reads: MFMAs + split
-                case 31: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 31>(sc, b0, wb, w, s, hk);   // skeleton without the tile's global stores
-                case 63: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 63>(sc, b0, wb, w, s, hk);   // skeleton without any epilogue
-                case 16: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 16>(sc, b0, wb, w, s, hk);   // full loop, no global stores of the tile
-                case 48: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 48>(sc, b0, wb, w, s, hk);   // full loop, no epilogue
-                case 100: return launch_mlp0_sp_t<Mlp0SpTileT<MODE>, 0>(sc, b0, wb, w, s, hk);   // (not an ablation) the one-wave-per-SIMD tile
-                case 101: return launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 0, 1>(sc, b0, wb, w, s, hk);   // (not an ablation) the ping-pong schedule
-                case 102: return launch_mlp0_sp_t<Mlp0SpTileN<MODE>, 0, 1>(sc, b0, wb, w, s, hk);   // ping-pong on the 4-wave tile (groups on different SIMDs)
-                default: break;
-            }
-            const int nst2 = tuning_knob("SP_NST2", -1);
-            if (nst2 > 0 && (nst2 & 1)) return launch_mlp0_sp_t<Mlp0SpTileN2<MODE>, 0, 2>(sc, b0, wb, w, s, hk);   // two-stage ring, three workgroups per CU
-        }
-        if constexpr (MODE >= 3) {
-            switch (sp_sched()) {
-                case 4:
-                    if (sp_bias_table()) break;
-                    return wide ? launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 0, 4>(sc, b0, wb, w, s, hk) : launch_mlp0_sp_t<Mlp0SpTileN<MODE>, 0, 4>(sc, b0, wb, w, s, hk);
-                case 3:
-                    if (wide && (tuning_knob("SP_NST4", 0) & 1)) return launch_mlp0_sp_t<Mlp0SpTileW4<MODE>, 0, 3>(sc, b0, wb, w, s, hk);   // four-stage ring
-                    return wide ? launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 0, 3>(sc, b0, wb, w, s, hk) : launch_mlp0_sp_t<Mlp0SpTileN<MODE>, 0, 3>(sc, b0, wb, w, s, hk);
-                case 2:
-                    if ((sp_direct_store() & 4) && !stat_fused())   // tile stores in front of the statistics
-                        return wide ? launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 0, 2, 1>(sc, b0, wb, w, s, hk) : launch_mlp0_sp_t<Mlp0SpTileN<MODE>, 0, 2, 1>(sc, b0, wb, w, s, hk);
-                    return wide ? launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 0, 2>(sc, b0, wb, w, s, hk) : launch_mlp0_sp_t<Mlp0SpTileN<MODE>, 0, 2>(sc, b0, wb, w, s, hk);
-                default:
-                    return wide ? launch_mlp0_sp_t<Mlp0SpTileW<MODE>>(sc, b0, wb, w, s, hk) : launch_mlp0_sp_t<Mlp0SpTileN<MODE>>(sc, b0, wb, w, s, hk);
-            }
-        }
-    }
-    if constexpr (MODE >= 3) {
-        if constexpr (TUNING_BUILD) {
-            if (sp_ut_on(MODE)) {   // EPI 2 | 8: bias through its LDS table, transposed accumulators -> U^T + in-lane statistics
-                if (wide) launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 0, SP_SCHED_DEFAULT, 10>(sc, b0, wb, w, s, hk);
-                else launch_mlp0_sp_t<Mlp0SpTileN<MODE>, 0, SP_SCHED_DEFAULT, 10>(sc, b0, wb, w, s, hk);
-                return;
-            }
-        }
-        if (wide) launch_mlp0_sp_t<Mlp0SpTileW<MODE>, 0, SP_SCHED_DEFAULT, 2>(sc, b0, wb, w, s, hk);   // (EPI 2: bias through its LDS table)
-        else launch_mlp0_sp_t<Mlp0SpTileN<MODE>, 0, SP_SCHED_DEFAULT, 2>(sc, b0, wb, w, s, hk);
-    } else {   // bf16 modes (tuning builds)
-        if (wide) launch_mlp0_sp_t<Mlp0SpTileW<MODE>>(sc, b0, wb, w, s, hk);
-        else launch_mlp0_sp_t<Mlp0SpTileN<MODE>>(sc, b0, wb, w, s, hk);
-    }
+    if (mlp0_sp_wide(w.L)) launch_mlp0_sp_t<Mlp0SpTileW<MODE>>(sc, b0, wb, w, s, hk);
+    else launch_mlp0_sp_t<Mlp0SpTileN<MODE>>(sc, b0, wb, w, s, hk);
 }
 void launch_mlp0_sp(const float* sc, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    switch (w.prec) {
-#ifdef GATSSPG_TUNING
-        case 1: launch_mlp0_sp_m<1>(sc, b0, wb, w, s, hk); break;
-        case 2: launch_mlp0_sp_m<2>(sc, b0, wb, w, s, hk); break;
-#endif
-        case 3: launch_mlp0_sp_m<3>(sc, b0, wb, w, s, hk); break;
-        default: launch_mlp0_sp_m<4>(sc, b0, wb, w, s, hk); break;
-    }
+    if (w.prec == 3) launch_mlp0_sp_m<3>(sc, b0, wb, w, s, hk);
+    else launch_mlp0_sp_m<4>(sc, b0, wb, w, s, hk);
 }
 
-template <class T, int SCHED, int EPI>
-static void launch_mlp3_sp_v(const float* sc, const float* b3, const PlaneSet& p, int NT, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    allow_big_lds_sp<mlp3_sp_kernel<T, SCHED, EPI>>();
-    const ColLayout L = sp_paired_layout(w.L, T::MODE);
-    GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_sp_kernel<T, SCHED, EPI>), dim3(xcd_grid_g(256 / T::BM, NT, L.xgs)), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s, sc, b3,
-                   p.p0, p.p1, p.p2, w.U, w.stats, w.Z, L);
-}
-// the schedule / store variants of one mlp3 tile (tuning builds); false = take the default
 template <class T>
-static bool launch_mlp3_sp_alt(const float* sc, const float* b3, const PlaneSet& p, int NT, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    const bool direct = sp_direct_store() & 2;
-    switch (sp_sched()) {
-        case 4: if (direct) return false; launch_mlp3_sp_v<T, 4, 0>(sc, b3, p, NT, w, s, hk); return true;
-        case 3: launch_mlp3_sp_v<T, 3, 1>(sc, b3, p, NT, w, s, hk); return true;
-        case 2: if (direct) launch_mlp3_sp_v<T, 2, 1>(sc, b3, p, NT, w, s, hk); else launch_mlp3_sp_v<T, 2, 0>(sc, b3, p, NT, w, s, hk); return true;
-        default: launch_mlp3_sp_v<T, 0, 0>(sc, b3, p, NT, w, s, hk); return true;
-    }
+static void launch_mlp3_sp_v(const float* sc, const float* b3, const PlaneSet& p, int NT, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    allow_big_lds_sp<mlp3_sp_kernel<T>>();
+    GATSSPG_LAUNCH(hk, KID_MLP3, s, mlp3_sp_kernel<T>, dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s, sc, b3,
+                   p.p0, p.p1, p.p1, w.U, w.stats, w.Z, w.L);
 }
 template <int MODE>
 static void launch_mlp3_sp_t(const float* sc, const float* b3, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     using T = Mlp3SpTile<MODE>;
-    const PlaneSet p = planes(wb, MODE, AttnWB::W3_HI, AttnWB::W3_LO, AttnWB::W3_LO2, AttnWB::W3_H16, AttnWB::W3_L16);
+    using T2 = Mlp3SpTile2<MODE>;
+    const PlaneSet p = planes(wb, AttnWB::W3_H16, AttnWB::W3_L16);
     const int NT = active_tiles(w.L) / (T::BN / 64);
-    if constexpr (MODE >= 3) {
-        // more than one round of the three-stage ring's two workgroups per CU (batched frames, N_3D = 20000): the two-stage ring's three
-        // per CU turn 1.46 rounds into one at 8 frames per step (fp16x4-b8: 0.565 vs 0.571 ms per frame, profiles/r04_ab_live_b8_tiles.txt)
-        using T2 = Mlp3SpTile2<MODE>;
-        const int nst2 = tuning_knob("SP_NST2", -1);
-        const bool two_stage = nst2 >= 0 ? (nst2 & 2) != 0 : (256 / T2::BM) * NT > 512;
-        if constexpr (TUNING_BUILD) {
-            if (two_stage ? launch_mlp3_sp_alt<T2>(sc, b3, p, NT, w, s, hk) : launch_mlp3_sp_alt<T>(sc, b3, p, NT, w, s, hk)) return;
-        }
-        if constexpr (TUNING_BUILD) {
-            if (sp_ut_on(MODE)) {   // EPI 1 | 8: direct stores, U read point-major
-                if (two_stage) launch_mlp3_sp_v<T2, SP_SCHED_DEFAULT, 9>(sc, b3, p, NT, w, s, hk);
-                else launch_mlp3_sp_v<T, SP_SCHED_DEFAULT, 9>(sc, b3, p, NT, w, s, hk);
-                return;
-            }
-        }
-        if (two_stage) launch_mlp3_sp_v<T2, SP_SCHED_DEFAULT, 1>(sc, b3, p, NT, w, s, hk);
-        else launch_mlp3_sp_v<T, SP_SCHED_DEFAULT, 1>(sc, b3, p, NT, w, s, hk);
-    } else {
-        launch_mlp3_sp_v<T, 0, 0>(sc, b3, p, NT, w, s, hk);   // bf16 modes (tuning builds)
-    }
+    // more than one round of the three-stage ring's two workgroups per CU (batched frames, N_3D = 20000): the two-stage ring's three
+    // per CU turn 1.46 rounds into one at 8 frames per step (fp16x4-b8: 0.565 vs 0.571 ms per frame, profiles/r04_ab_live_b8_tiles.txt).
+    // Tuning builds: GATSSPG_SP_NST2 >= 0 forces the choice (bit 1 = two-stage ring).
+    const int nst2 = tuning_knob("SP_NST2", -1);
+    const bool two_stage = nst2 >= 0 ? (nst2 & 2) != 0 : (256 / T2::BM) * NT > 512;
+    if (two_stage) launch_mlp3_sp_v<T2>(sc, b3, p, NT, w, s, hk);
+    else launch_mlp3_sp_v<T>(sc, b3, p, NT, w, s, hk);
 }
 void launch_mlp3_sp(const float* sc, const float* b3, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    switch (w.prec) {
-#ifdef GATSSPG_TUNING
-        case 1: launch_mlp3_sp_t<1>(sc, b3, wb, w, s, hk); break;
-        case 2: launch_mlp3_sp_t<2>(sc, b3, wb, w, s, hk); break;
-#endif
-        case 3: launch_mlp3_sp_t<3>(sc, b3, wb, w, s, hk); break;
-        default: launch_mlp3_sp_t<4>(sc, b3, wb, w, s, hk); break;
-    }
+    if (w.prec == 3) launch_mlp3_sp_t<3>(sc, b3, wb, w, s, hk);
+    else launch_mlp3_sp_t<4>(sc, b3, wb, w, s, hk);
 }
 
 }  // namespace gatsspg

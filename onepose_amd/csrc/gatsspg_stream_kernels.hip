@@ -206,15 +206,7 @@ __global__ __launch_bounds__(256, 7) void gats_leaf8x4_kernel(const float* __res
         v[p] = *reinterpret_cast<const float4*>(Lf + (size_t)ch * lrow + 4 * c4l);
         u1r[p] = CACHED_LOGITS ? 0.f : u1[ch];
     }
-#ifdef GATSSPG_PROFILING_BUILD
-    if (raw_out == 2) {   // read-only probe (profiling builds, wrong results): the leaf stream alone, one 4-byte store per thread
-        float acc = 0.f;
-#pragma unroll
-        for (int p = 0; p < 8; ++p) acc += (v[p].x + v[p].y) + (v[p].z + v[p].w);
-        if (acc == 1.2345e30f) dst[tid] = acc;
-        return;
-    }
-#endif
+    // (a read-only probe of the leaf stream alone, profiling builds: profiles/r02_gats_leaf_stream_probe.txt; removed)
     {
         // s3[i] = sum over the 256 channels of h[ch][i] * u2[ch]: 4 values per lane are reduced over the 64 lanes with 7
         // shuffles (two halving exchanges leave one value per lane -- point (lane & 1) * 2 + ((lane >> 1) & 1) -- then a
@@ -414,10 +406,7 @@ void launch_gats_leaf_logits(const float* u1_first, int u1_stride, int nlayers, 
 
 void launch_gats(const float* u1, const float* u2, const float* leaves, int num_leaf, int flags, float* dst,
                  const Workspace& w, hipStream_t s, ProfileHook* hk, const float* h3, const float* dq, const float* cl) {
-    int raw_out = (flags & GATSSPG_FLAG_WITH_LINEAR_TRANSFORM) ? 1 : 0;
-#ifdef GATSSPG_PROFILING_BUILD
-    if (tuning_knob("GATS_PROBE", 0) && !h3) raw_out = 2;   // time the leaf stream alone
-#endif
+    const int raw_out = (flags & GATSSPG_FLAG_WITH_LINEAR_TRANSFORM) ? 1 : 0;
     if (num_leaf == 8) {
         const int nt = (w.L.n2 + 3) / 4;
         const int extra = h3 ? GATS_COPY_BLOCKS : 0;

@@ -1083,8 +1083,8 @@ __device__ __forceinline__ bool xcd_tile_map(int MT, int NT, int& rt, int& ct) {
     return ct < NT;
 }
 inline int xcd_grid(int MT, int NT) { return 8 * MT * ((NT + 7) / 8); }
-// The same with an XCD owning GROUPS of 2^gs consecutive column tiles: kernels whose column tiles are half as wide as a neighbour kernel's
-// (qkv_kv / mlp3 on 64 columns beside mlp0_sp on 128) then keep a column range on the XCD whose L2 its producer wrote it into.
+// The same with an XCD owning GROUPS of 2^gs consecutive column tiles (the split kernels read gs from ColLayout::xgs, always 0 since the
+// paired layout was removed: no effect, profiles/r05c_ab_live_ut_xcd_direct.txt).
 __device__ __forceinline__ bool xcd_tile_map_g(int MT, int NT, int gs, int& rt, int& ct) {
     const int g = blockIdx.x;
     const int xcd = g & 7, slot = g >> 3;
@@ -1093,7 +1093,6 @@ __device__ __forceinline__ bool xcd_tile_map_g(int MT, int NT, int gs, int& rt, 
     ct = ((((cs >> gs) << 3) + xcd) << gs) + (cs & ((1 << gs) - 1));
     return ct < NT;
 }
-inline int xcd_grid_g(int MT, int NT, int gs) { return (8 * MT * (((NT + (8 << gs) - 1) / (8 << gs)))) << gs; }
 
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 // same values, branch-free: both sides are evaluated and selected (epilogues that apply elu to 16-32 accumulator values per

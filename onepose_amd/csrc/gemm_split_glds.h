@@ -58,17 +58,17 @@ __device__ __forceinline__ void wait_dma_barrier_if(int on) {
 
 constexpr int FP16_ACT_SCALE_LOG2 = 4;   // activations are multiplied by 2^4 before the fp16 split (exact), range +-8188
 
-// MODE = Workspace::prec: 1 bf16x3, 2 bf16x6, 3 fp16x3, 4 fp16x4; 0 = the exact fp32 MFMA (v_mfma_f32_32x32x2_f32) on the same loop: the A
-// operand is then the fp32 row-major matrix itself (128-byte LDS rows, chunk c of row r at c ^ ((r >> 1) & 7)), B is fed to the MFMAs unsplit.
+// MODE = Workspace::prec: 2 bf16x6 (the score contraction), 3 fp16x3, 4 fp16x4.  (The exact fp32 MFMA on this loop, MODE 0, was 8 % slower
+// per frame than the register-staged fp32 loop: profiles/r04_ab_live_fp32_dma.txt; removed.)
 // ASL: log2 of the power of two the B operand (activations) is multiplied by before an fp16 split (ignored by the bf16 modes)
 template <int BM_, int WM_, int WN_, int NST_, int MODE_, int ASL_ = FP16_ACT_SCALE_LOG2>
 struct SpTile {
     static constexpr int BM = BM_, WM = WM_, WN = WN_, NST = NST_, MODE = MODE_;
     static constexpr int TM = BM / WM / 32, TN = 1, BN = 32 * WN;
     static constexpr int WAVES = WM * WN, WAVES_MN = WAVES, THREADS = 64 * WAVES, KS = 1;
-    static constexpr bool F16 = MODE >= 3, F32 = MODE == 0;
-    static constexpr int PA = F32 ? 1 : MODE == 2 ? 3 : 2;        // planes per operand (16-bit terms; fp32: the matrix itself)
-    static constexpr int ROW_BYTES = F32 ? 128 : 64;              // one LDS row = 32 k of one matrix row
+    static constexpr bool F16 = MODE >= 3;
+    static constexpr int PA = MODE == 2 ? 3 : 2;                  // planes per operand (16-bit terms)
+    static constexpr int ROW_BYTES = 64;                          // one LDS row = 32 k of one matrix row
     static constexpr int A_PLANE_BYTES = BM * ROW_BYTES;          // [BM][32], unpadded, swizzled
     static constexpr int A_BYTES = PA * A_PLANE_BYTES;
     static constexpr int B_BYTES = BK * BN * 4;                   // raw fp32 [32][BN]
@@ -129,19 +129,17 @@ __device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&out)[MODE =
 }
 
 // the term products of one 32x32x16 block, small terms first (gemm_f32_mfma.h); FRESH: the first one starts from zero.
-// SWAP: the two fragments trade places in the instruction (the MFMA's A and B operand registers have the same shape: 8 consecutive
-// k of row / column lane & 31) -- the block comes out TRANSPOSED in the accumulators, lane = row of the a[] fragment, same bits.
-template <int MODE, bool FRESH, bool SWAP = false>
+template <int MODE, bool FRESH>
 __device__ __forceinline__ void mfma_terms(f32x16& c, const bf16x8 (&a)[MODE == 2 ? 3 : 2], const bf16x8 (&b)[MODE == 2 ? 3 : 2]) {
     f32x16 z;
 #pragma unroll
     for (int r = 0; r < 16; ++r) z[r] = 0.f;
     auto f16 = [](bf16x8 x, bf16x8 y, f32x16 acc) {
         const f16x8 hx = __builtin_bit_cast(f16x8, x), hy = __builtin_bit_cast(f16x8, y);
-        return SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_f16(hy, hx, acc, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_f16(hx, hy, acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(hx, hy, acc, 0, 0, 0);
     };
     auto b16 = [](bf16x8 x, bf16x8 y, f32x16 acc) {
-        return SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(y, x, acc, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc, 0, 0, 0);
     };
     if constexpr (MODE >= 3) {
         if constexpr (MODE == 4) {
@@ -199,31 +197,18 @@ constexpr int SP_TRACE_STEP = 5;
 // a_pl(kt, plane): 16-bit plane pointer of A slab kt at the tile's first row, slab-major (row stride 32 elements = 64 bytes);
 // b_slab(kt): fp32 pointer &B[kt * 32][col0], row stride ldb.  smem: T::RING_BYTES, 16-byte aligned.  All NST stages are free
 // again when the function returns (it ends on a barrier behind the last fragment read).
-// ABL (tuning builds only, WRONG results, timing only): bit 0 no DMA requests after the prologue, bit 1 no MFMAs, bit 2 no split VALU,
-// bit 3 no fragment reads
-// SCHED 0: every wave runs the schedule below (barrier between the two k16 halves, fragments read half a step ahead).
-// SCHED 1 ("ping-pong"): the waves of a workgroup form two groups (first / second half of the wave ids: with eight waves the pairs
-//   that share a SIMD); every wave runs  m(0) c(0) m(1) c(1) ...  with m(I) = DMA requests of slab I + NST - 1 and ALL fragment reads
-//   of slab I, c(I) = splits + products of slab I, and ONE barrier per slab -- the early group behind c(I), the late group behind
-//   m(I).  Between two barriers each wave does one m and one c, the groups in opposite order: while one wave of a SIMD multiplies,
-//   its partner requests and reads, and only half of the workgroup loads the CU's DMA / LDS paths at a time.
+// SCHED 0: every wave runs the schedule at the end (barrier between the two k16 halves, fragments read half a step ahead): bf16x6.
+// SCHED 4: the slot schedule (fp16 modes).  (Schedules 1 -- ping-pong wave groups --, 2 and 3 and the main-loop ablations were measured
+// and removed: profiles/r04_ab_live_schedules.txt, r04_ab_live_slot_schedule.txt, r04_split_loop_ablations.txt.)
 // pre(): called once, right BEFORE the DMA requests of the first NST slabs -- the place for LDS-DMA fills of small per-workgroup tables
 // (glds16 pieces: being older than every slab piece they are covered by the first counted wait and published by the first barrier; a
 // table filled through registers would stall the wave on its load in front of the first slab requests).
 struct SpNoPre {
     __device__ __forceinline__ void operator()() const {}
 };
-// OPT bit 0 (SP_OPT_SWAP): the MFMA operands trade places -- the accumulators hold the TRANSPOSED tile: lane = row (wm TM + tm) 32 + l31 of
-//   the A operand, register r = column wn 32 + mfma_row(r, half) of the B operand (mlp.0 writes U^T point-major straight from them and
-//   sums the InstanceNorm statistics inside a lane).  The products and their order are unchanged: the same bits, transposed.
-// OPT bit 1 (SP_OPT_BT): the B operand is given TRANSPOSED in memory, B^T [column][k] fp32 with row stride ldb (floats): b_slab(kt) =
-//   &BT[col0][32 kt].  Its slab arrives as 128-byte LDS rows (one per column, chunk c of row r at c ^ ((r >> 1) & 7): the fp32 A rows of
-//   MODE 0) and a lane reads its 8 consecutive k with TWO 16-byte reads instead of eight 4-byte ones.
-constexpr int SP_OPT_SWAP = 1, SP_OPT_BT = 2;
-template <class T, int KT, class APlane, class BSlab, class Hooks, class BX, int ABL = 0, int SCHED = 0, class Pre = SpNoPre, int OPT = 0>
+template <class T, int KT, class APlane, class BSlab, class Hooks, class BX, int SCHED = 0, class Pre = SpNoPre>
 __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* smem, APlane a_pl, BSlab b_slab, int ldb, Hooks& hooks,
                                                  BX& bx, SpTrace* tr_ = nullptr, Pre pre = Pre(), bool tron = false, int lda_bytes = 64) {
-    constexpr bool SWAP = (OPT & SP_OPT_SWAP) != 0, BT = (OPT & SP_OPT_BT) != 0;
     // lda_bytes: row stride of an A slab in bytes (slab-major 16-bit planes: 64; a row-major fp32 matrix: 4 x its leading dimension)
     // (profiling builds: the stamps go into the caller's SpTrace through a reference and a separate on/off flag -- a conditional pointer
     //  keeps the object in scratch memory and costs the traced kernel 50 spilled registers)
@@ -240,18 +225,13 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
     // ---- LDS-DMA pieces: piece q of a slab = 1 KiB of its LDS image; lane i supplies bytes [16 i, 16 i + 16) of it.
     // A piece: 16 rows x 64 B of one plane; LDS chunk position i & 3 of row i >> 2 holds source chunk (i & 3) ^ ((row >> 2) & 3),
     // and (row >> 2) & 3 = (i >> 4) & 3 because pieces start on multiples of 16 rows.
-    // (fp32 rows are 128 bytes: a piece is 8 rows, the swizzle (row >> 1) & 7 = (4 (piece & 1)) | (lane >> 4): the lane part below, the
-    //  piece-parity part -- bit 2 of the chunk index = byte 64 -- is XORed in per piece)
-    constexpr int CPR = T::ROW_BYTES / 16;   // 16-byte chunks per row (4 or 8)
-    constexpr int RPQ = 64 / CPR;            // rows per piece (16 or 8)
+    constexpr int CPR = T::ROW_BYTES / 16;   // 16-byte chunks per row
+    constexpr int RPQ = 64 / CPR;            // rows per piece
     const unsigned a_lane_row = (unsigned)(lane / CPR), a_lane_chunk = (unsigned)((lane % CPR) ^ ((lane >> 4) & 3));
     const unsigned a_lane = a_lane_row * (unsigned)lda_bytes + a_lane_chunk * 16;
     constexpr int LPR = BN / 4;        // lanes per k row of a B piece (16 B each)
     constexpr int KPP = 64 / LPR;      // k rows per B piece
-    // (BT: a piece is 8 columns x 128 B of B^T; lane i supplies LDS chunk position i & 7 of row i >> 3, which holds source chunk
-    //  (i & 7) ^ ((row >> 1) & 7), (row >> 1) & 7 = 4 (piece & 1) | (i >> 4) inside an 8-row piece: the piece-parity bit is XORed in per piece)
-    const unsigned b_lane = BT ? (unsigned)((lane >> 3) * ldb * 4 + (((lane & 7) ^ ((lane >> 4) & 3)) * 16))
-                               : (unsigned)(((lane / LPR) * ldb + (lane % LPR) * 4) * 4);
+    const unsigned b_lane = (unsigned)(((lane / LPR) * ldb + (lane % LPR) * 4) * 4);
     constexpr int RPP = T::BM / RPQ;   // A pieces per plane
     // pieces [j0, j1) of this wave's G pieces of slab kt
     auto issue_pieces = [&](int kt, int stage, int j0, int j1) {
@@ -264,88 +244,48 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
             if (is_a) {
                 const int plane = (RPP % T::WAVES == 0) ? (j * T::WAVES) / RPP : q / RPP;
                 const int qi = q % RPP;
-                const unsigned flip = T::F32 ? (unsigned)(qi & 1) * 64u : 0u;
-                glds16(reinterpret_cast<const char*>(a_pl(kt, plane)) + (size_t)(qi * RPQ) * lda_bytes + (a_lane ^ flip),
+                glds16(reinterpret_cast<const char*>(a_pl(kt, plane)) + (size_t)(qi * RPQ) * lda_bytes + a_lane,
                        st + plane * T::A_PLANE_BYTES + qi * 1024);
             } else {
                 const int qb = q - T::NA;
-                if constexpr (BT)
-                    glds16(reinterpret_cast<const char*>(b_slab(kt)) + (size_t)(qb * 8) * ldb * 4 + (b_lane ^ ((unsigned)(qb & 1) * 64u)),
-                           st + T::A_BYTES + qb * 1024);
-                else
-                    glds16(reinterpret_cast<const char*>(b_slab(kt)) + (size_t)(qb * KPP) * ldb * 4 + b_lane, st + T::A_BYTES + qb * 1024);
+                glds16(reinterpret_cast<const char*>(b_slab(kt)) + (size_t)(qb * KPP) * ldb * 4 + b_lane, st + T::A_BYTES + qb * 1024);
             }
         }
     };
     auto issue = [&](int kt, int stage) { issue_pieces(kt, stage, 0, G); };
 
     // ---- fragment read offsets (bytes inside a stage)
-    // 16-bit planes: a lane's 8 k of (k16 half P) are ONE chunk; fp32: two consecutive chunks (NCH = 2)
-    constexpr int NCH = T::F32 ? 2 : 1;
-    int a_off[TM][2][NCH];
+    // a lane's 8 k of (k16 half P) are ONE chunk
+    int a_off[TM][2];
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
         const int row = (wm * TM + tm) * 32 + l31;
-        const int x = T::F32 ? (row >> 1) & 7 : (row >> 2) & 3;
+        const int x = (row >> 2) & 3;
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int e = 0; e < NCH; ++e) a_off[tm][s][e] = row * T::ROW_BYTES + ((((2 * s + half) * NCH + e) ^ x) * 16);
+        for (int s = 0; s < 2; ++s) a_off[tm][s] = row * T::ROW_BYTES + (((2 * s + half) ^ x) * 16);
     }
     const int b_off = T::A_BYTES + ((8 * half) * BN + wn * 32 + l31) * 4;
-    int bt_off[2][2];   // BT: [k16 half][16-byte chunk] of the lane's column row
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int row = wn * 32 + l31;
-            bt_off[s][e] = T::A_BYTES + row * 128 + ((((2 * s + half) * 2 + e) ^ ((row >> 1) & 7)) * 16);
-        }
 
-    bf16x8 Af[2][TM][PA * NCH];   // [k16 half][tm][plane] (fp32: the lane's 8 k as two 16-byte chunks)
+    bf16x8 Af[2][TM][PA];     // [k16 half][tm][plane]
     float Br[2][8];           // raw B values of the k16 half
     float2 Bx[2][8];          // their per-row aux pairs (BX::ON)
     bf16x8 Bf[2][PA];         // split B planes
-    float Bv[2][8];           // fp32 mode: the (transformed) B values themselves
 
     auto read_b = [&](int stage, int slab, auto Pc) {
         constexpr int P = decltype(Pc)::value;
         const char* st = smem + stage * T::STAGE_BYTES;
-        if constexpr (ABL & 8) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(Br[P][j]));
-            return;
-        }
-        if constexpr (BT) {
-            const vf4 lo = *reinterpret_cast<const vf4*>(st + bt_off[P][0]), hi = *reinterpret_cast<const vf4*>(st + bt_off[P][1]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Br[P][j] = lo[j];
-                Br[P][4 + j] = hi[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) Br[P][j] = *reinterpret_cast<const float*>(st + b_off + (P * 16 + j) * BN * 4);
-        }
+        for (int j = 0; j < 8; ++j) Br[P][j] = *reinterpret_cast<const float*>(st + b_off + (P * 16 + j) * BN * 4);
         if constexpr (BX::ON) bx.fetch(slab * BK + P * 16 + 8 * half, Bx[P]);
     };
     auto read_a = [&](int stage, auto Pc) {
         constexpr int P = decltype(Pc)::value;
         const char* st = smem + stage * T::STAGE_BYTES;
-        if constexpr (ABL & 8) {
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                for (int pl = 0; pl < PA * NCH; ++pl) asm volatile("" : "+v"(Af[P][tm][pl]));
-            return;
-        }
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
             for (int pl = 0; pl < PA; ++pl)
-#pragma unroll
-                for (int e = 0; e < NCH; ++e)
-                    Af[P][tm][pl * NCH + e] = *reinterpret_cast<const bf16x8*>(st + pl * T::A_PLANE_BYTES + a_off[tm][P][e]);
+                Af[P][tm][pl] = *reinterpret_cast<const bf16x8*>(st + pl * T::A_PLANE_BYTES + a_off[tm][P]);
     };
     auto split_part = [&](auto Ic, auto Pc) {
         constexpr int I = decltype(Ic)::value, P = decltype(Pc)::value;
@@ -353,60 +293,19 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = Br[P][j];
         if constexpr (Hooks::ENABLED) hooks.template bvals<I, P>(v);
-        if constexpr ((ABL & 4) && !T::F32) {
-#pragma unroll
-            for (int pl = 0; pl < PA; ++pl)
-                Bf[P][pl] = __builtin_bit_cast(bf16x8, ((vf4){v[pl], v[pl + 2], v[pl + 4], v[7 - pl]}));
-            return;
-        }
         if constexpr (BX::ON) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = bx.apply(v[j], Bx[P][j]);
         }
-        if constexpr (T::F32) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) Bv[P][j] = v[j];
-        } else {
-            split8<MODE>(v, Bf[P], T::ACT_SCALE);   // fp16 modes: scaled inside the split; bf16 modes: ACT_SCALE = 1
-        }
+        split8<MODE>(v, Bf[P], T::ACT_SCALE);   // fp16 modes: scaled inside the split; bf16 modes: ACT_SCALE = 1
     };
     auto mfma_part = [&](auto Ic, auto Pc, int tm0, int tm1) {
         constexpr int I = decltype(Ic)::value, P = decltype(Pc)::value;
         f32x16(&dst)[TM] = hooks.template target<I, TM>(acc);
-        if constexpr (ABL & 2) {
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-                if (tm >= tm0 && tm < tm1) {
-#pragma unroll
-                    for (int pl = 0; pl < PA; ++pl) asm volatile("" ::"v"(Af[P][tm][pl]), "v"(Bf[P][pl]));
-                    if constexpr (Hooks::template fresh<I, P>()) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) dst[tm][r] = 0.f;
-                    }
-                }
-            return;
-        }
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
             if (tm >= tm0 && tm < tm1) {
-                if constexpr (T::F32) {
-                    // eight exact fp32 products: lane half h multiplies k = 16 P + 8 h + j (the same k assignment for A and B)
-                    const vf4 a0 = __builtin_bit_cast(vf4, Af[P][tm][0]), a1 = __builtin_bit_cast(vf4, Af[P][tm][1]);
-                    f32x16 c = dst[tm];
-                    if constexpr (Hooks::template fresh<I, P>()) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) c[r] = 0.f;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        c = SWAP ? __builtin_amdgcn_mfma_f32_32x32x2f32(Bv[P][j], a0[j], c, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], Bv[P][j], c, 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        c = SWAP ? __builtin_amdgcn_mfma_f32_32x32x2f32(Bv[P][4 + j], a1[j], c, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], Bv[P][4 + j], c, 0, 0, 0);
-                    dst[tm] = c;
-                } else {
-                    mfma_terms<MODE, Hooks::template fresh<I, P>(), SWAP>(dst[tm], Af[P][tm], Bf[P]);
-                }
+                mfma_terms<MODE, Hooks::template fresh<I, P>()>(dst[tm], Af[P][tm], Bf[P]);
             }
     };
 
@@ -428,112 +327,8 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
     pre();
     static_for<0, NST>([&](auto Ic) { issue(decltype(Ic)::value, decltype(Ic)::value); });
     wait_dma_barrier<(NST - 1) * G>();
-    if constexpr (SCHED == 1) {
-        const int late = wave >= T::WAVES / 2 ? 1 : 0;   // wave-uniform (wave is an SGPR value)
-        stamp(-1, 0);
-        static_for<0, KT>([&](auto Ic) {
-            constexpr int I = decltype(Ic)::value;
-            // barrier #I lets slab I + 1 be read: this wave's pieces of the slabs requested after it may stay in flight
-            constexpr int LATER = I + 1 < KT ? (I + NST - 1 < KT - 1 ? I + NST - 1 : KT - 1) - (I + 1) : 0;
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 1);
-            // ---- m(I)
-            if constexpr (I >= 1 && I + NST - 1 < KT && !(ABL & 1)) issue(I + NST - 1, (I - 1) % NST);   // the stage slab I - 1 left
-            read_b(I % NST, I, IC<0>{});
-            read_a(I % NST, IC<0>{});
-            read_b(I % NST, I, IC<1>{});
-            read_a(I % NST, IC<1>{});
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 2);
-            wait_dma_barrier_if<LATER * G>(late);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 3);
-            // ---- c(I)
-            split_part(Ic, IC<0>{});
-            mfma_part(Ic, IC<0>{}, 0, TM);
-            split_part(Ic, IC<1>{});
-            if constexpr (Hooks::ENABLED) hooks.template in_step<I, TM>(acc);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 4);
-            mfma_part(Ic, IC<1>{}, 0, TM);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 5);
-            wait_dma_barrier_if<LATER * G>(late ^ 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) { stamp(I, 6); stamp(I, 7); }
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        stamp(-1, 8);
-        wait_dma_barrier<0>();   // every wave is done with the ring: the epilogue may re-use it
-        return;
-    }
-    if constexpr (SCHED == 2) {
-        // SCHED 0 with the DMA requests of a step SPREAD over it instead of issued in one burst behind the barrier (where all waves of
-        // the workgroup hit the CU's DMA path at once: ~140 cycles per piece in the trace): slot 0 behind the barrier, slot 1 between
-        // the two halves of products (I, P1), slot 2 behind them, slot 3 (three-stage rings only: the slab has a whole further step to
-        // land) inside the next step's first product group.  The raw B values of (I + 1, P1) are read between the halves as well.
-        constexpr int NSLOT = NST >= 3 ? 4 : 3;
-        constexpr int E0 = (G + NSLOT - 1) / NSLOT, E1 = E0 + (G - E0 + NSLOT - 2) / (NSLOT - 1);
-        constexpr int E2 = NSLOT == 3 ? G : E1 + (G - E1 + 1) / 2;
-        read_b(0, 0, IC<0>{});
-        read_b(0, 0, IC<1>{});
-        read_a(0, IC<0>{});
-        read_a(0, IC<1>{});
-        split_part(IC<0>{}, IC<0>{});
-        stamp(-1, 0);
-        static_for<0, KT>([&](auto Ic) {
-            constexpr int I = decltype(Ic)::value;
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 1);
-            mfma_part(Ic, IC<0>{}, 0, TM / 2);
-            if constexpr (E2 < G && I >= 1 && I - 1 + NST < KT && !(ABL & 1)) {   // slot 3 of the slab requested in step I - 1
-                __builtin_amdgcn_sched_barrier(0);
-                issue_pieces(I - 1 + NST, (I - 1) % NST, E2, G);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            mfma_part(Ic, IC<0>{}, TM / 2, TM);
-            split_part(Ic, IC<1>{});
-            if constexpr (Hooks::ENABLED) hooks.template in_step<I, TM>(acc);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 2);
-            if constexpr (I + 1 < KT) {
-                constexpr int LATER = (I + NST - 1 < KT - 1 ? I + NST - 1 : KT - 1) - (I + 1);
-                wait_dma_barrier<LATER * G>();
-                if constexpr (I == SP_TRACE_STEP) stamp(I, 3);
-                if constexpr (I + NST < KT && !(ABL & 1)) issue_pieces(I + NST, I % NST, 0, E0);
-                read_b((I + 1) % NST, I + 1, IC<0>{});
-                read_a((I + 1) % NST, IC<0>{});
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 4);
-            mfma_part(Ic, IC<1>{}, 0, TM / 2);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I + 1 < KT) {
-                if constexpr (I + NST < KT && !(ABL & 1)) issue_pieces(I + NST, I % NST, E0, E1);
-                read_b((I + 1) % NST, I + 1, IC<1>{});
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 5);
-            mfma_part(Ic, IC<1>{}, TM / 2, TM);
-            if constexpr (I + 1 < KT) split_part(IC<I + 1>{}, IC<0>{});
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (I == SP_TRACE_STEP) stamp(I, 6);
-            if constexpr (I + 1 < KT) {
-                if constexpr (I + NST < KT && !(ABL & 1)) issue_pieces(I + NST, I % NST, E1, E2);
-                read_a((I + 1) % NST, IC<1>{});
-            }
-            if constexpr (I == SP_TRACE_STEP) {
-                __builtin_amdgcn_sched_barrier(0);
-                stamp(I, 7);
-            }
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        stamp(-1, 8);
-        wait_dma_barrier<0>();
-        return;
-    }
-    if constexpr (SCHED == 3 || SCHED == 4) {
-        // SCHED 2's data flow with the VALU work of a step pinned UNDER its MFMAs, one slot per MFMA (tools/microbench/mfma_valu_overlap.hip:
+    if constexpr (SCHED == 4) {
+        // The DMA requests of a step spread over it, with the VALU work of a step pinned UNDER its MFMAs, one slot per MFMA (tools/microbench/mfma_valu_overlap.hip:
         // a wave that follows every 32-cycle MFMA with up to ~5 VALU instructions runs at the matrix pipe's rate, alone or with a partner
         // wave on its SIMD; 16 MFMAs followed by 80 VALU cost the sum -- and the per-step barrier keeps the two waves of a SIMD in phase, so
         // a partner cannot fill the gap).  hipcc left to itself keeps the four term products of an accumulator back to back and packs a
@@ -541,9 +336,8 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
         //   products (I, P0) m = 0 .. HM-1 : pair q of split (I, P1) under m = q HM/4 (hooks: the raw-value dot under m = 0, the head fold under m = HM/2)
         //   counted wait + barrier(I)
         //   products (I, P1) m = 0 .. HM-1 : DMA pieces + reads of slab I + 1 under m = 0, HM/4, HM-2; pair q of split (I + 1, P0) under m = HM-4+q
-        static_assert(!T::F32 && MODE >= 3, "the slot schedule is written for the two-plane fp16 modes");
+        static_assert(MODE >= 3, "the slot schedule is written for the two-plane fp16 modes");
         constexpr int NT = MODE == 4 ? 4 : 3, HM = TM * NT, QA = HM / 4, S0 = HM - 4, PP = 1;
-        constexpr bool SPREAD = SCHED == 4;   // the reads of slab I + 1 one group per slot instead of two groups under product 1 of (I, P1)
         static_assert(QA >= 1 && S0 >= 0, "four pairs per half step");
         constexpr int NSLOT = NST >= 3 ? 4 : 3;
         constexpr int E0 = (G + NSLOT - 1) / NSLOT, E1 = E0 + (G - E0 + NSLOT - 2) / (NSLOT - 1);
@@ -561,9 +355,9 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
                 f32x16 z;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) z[r] = 0.f;
-                dst[tm] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, z, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, z, 0, 0, 0);
+                dst[tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, z, 0, 0, 0);
             } else {
-                dst[tm] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, dst[tm], 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, dst[tm], 0, 0, 0);
+                dst[tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, dst[tm], 0, 0, 0);
             }
         };
         auto pair = [&](auto Pc, auto Qc) {
@@ -600,7 +394,7 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
                         pair(IC<1>{}, IC<2 * (M / (2 * QA)) + 1>{});
                     }
                 }
-                if constexpr (M == 1 && E2 < G && I >= 1 && I - 1 + NST < KT && !(ABL & 1)) issue_pieces(I - 1 + NST, (I - 1) % NST, E2, G);
+                if constexpr (M == 1 && E2 < G && I >= 1 && I - 1 + NST < KT) issue_pieces(I - 1 + NST, (I - 1) % NST, E2, G);
                 if constexpr (M == HM / 2 && Hooks::ENABLED) hooks.template in_step<I, TM>(acc);
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -618,15 +412,13 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
                 if constexpr (I + 1 < KT) {
                     if constexpr (M == 0) {
                         read_b((I + 1) % NST, I + 1, IC<0>{});
-                        if constexpr (!SPREAD) read_a((I + 1) % NST, IC<0>{});
-                        if constexpr (I + NST < KT && !(ABL & 1)) issue_pieces(I + NST, I % NST, 0, E0);
+                        if constexpr (I + NST < KT) issue_pieces(I + NST, I % NST, 0, E0);
                     }
-                    if constexpr (SPREAD && M == 1) read_a((I + 1) % NST, IC<0>{});
-                    if constexpr (M == (SPREAD ? 2 : QA)) {
-                        if constexpr (I + NST < KT && !(ABL & 1)) issue_pieces(I + NST, I % NST, E0, E1);
-                        if constexpr (!SPREAD) read_b((I + 1) % NST, I + 1, IC<1>{});
+                    if constexpr (M == 1) read_a((I + 1) % NST, IC<0>{});   // the reads of slab I + 1: one group per slot
+                    if constexpr (M == 2) {
+                        if constexpr (I + NST < KT) issue_pieces(I + NST, I % NST, E0, E1);
                     }
-                    if constexpr (SPREAD && M == 3) read_b((I + 1) % NST, I + 1, IC<1>{});
+                    if constexpr (M == 3) read_b((I + 1) % NST, I + 1, IC<1>{});
                 }
                 one(Ic, IC<1>{}, Mc);
                 if constexpr (I + 1 < KT) {
@@ -637,7 +429,7 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
                         pair(IC<0>{}, IC<M - S0>{});
                         pair(IC<0>{}, IC<M - S0 + 1>{});
                     }
-                    if constexpr (M == HM - 2 && I + NST < KT && !(ABL & 1)) issue_pieces(I + NST, I % NST, E1, E2);
+                    if constexpr (M == HM - 2 && I + NST < KT) issue_pieces(I + NST, I % NST, E1, E2);
                     if constexpr (M == HM - 1) read_a((I + 1) % NST, IC<1>{});
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -669,7 +461,7 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
             constexpr int LATER = (I + NST - 1 < KT - 1 ? I + NST - 1 : KT - 1) - (I + 1);
             wait_dma_barrier<LATER * G>();
             if constexpr (I == SP_TRACE_STEP) stamp(I, 3);
-            if constexpr (I + NST < KT && !(ABL & 1)) issue(I + NST, I % NST);
+            if constexpr (I + NST < KT) issue(I + NST, I % NST);
             read_b((I + 1) % NST, I + 1, IC<0>{});
             read_b((I + 1) % NST, I + 1, IC<1>{});
             read_a((I + 1) % NST, IC<0>{});

@@ -2,10 +2,11 @@
 differ by up to 40 % on identical binaries and drift with load, so separate bench.py processes cannot resolve a few per cent.
 
     python -m onepose_amd.build_ext --tuning
-    python tools/ab_live.py [--config fp16x4] [--kernel mlp0] [--rounds 8] [--steps 30] "" SP_SCHED=2 SP_MLP0_WIDE_MIN=100000 ...
+    python tools/ab_live.py [--config fp16x4] [--kernel mlp0] [--rounds 8] [--steps 30] "" SP_NST2=2 SP_MLP0_WIDE_MIN=100000 ...
 
 Each setting is a comma-separated list of KNOB=VALUE (GATSSPG_ prefix added here, "" = defaults); only knobs that the library reads per
-launch can be flipped this way (SP_SCHED, SP_ABL, SP_MLP0_WIDE_MIN / _MAX, STAT_FUSED, SCORE_SPLIT, SPLIT_LOOP_BF16X3 / _BF16X6).
+launch can be flipped this way (DIET_MIN_TILES, SP_MLP0_WIDE_MIN / _MAX, SP_NST2: the shape thresholds between two product kernels;
+compile-time alternatives are A/B-timed as two builds with tools/ab_libs.py).
 Per setting: median over the rounds of (a) the event-timed kernel (one launch per forward), (b) milliseconds per frame one frame at a time,
 (c) frames/s with --slots (4) frames in flight.
 """

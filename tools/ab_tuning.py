@@ -1,7 +1,7 @@
 """A/B runs of the tuning-build knobs on the GPU box: one bench.py process per setting, same inputs, same protocol.
 
     python -m onepose_amd.build_ext --tuning            # lib*_tuning.so (the package never loads these)
-    python tools/ab_tuning.py [--config headline] [--kernel mlp3] [--extractor] "" MLP3_TILE=1 MLP0_BTILE=1,MLP3_TILE=1 ...
+    python tools/ab_tuning.py [--config headline] [--kernel mlp3] [--extractor] "" SMALL_NT3=0 DIET_MIN_TILES=0,SMALL_NT3=0 ...
 
 Each argument is a comma-separated list of KNOB=VALUE (GATSSPG_ / SPP_ prefix added here; "" = the defaults).  Prints, per
 setting: frames/s with 3 frames in flight, one-frame-at-a-time frames/s, the event-timed kernel and the parity number of the

@@ -27,7 +27,7 @@ lib.gatsspg_debug_set_trace(None)   # (host-side: launches enqueued from here on
 torch.cuda.synchronize()
 t = buf.cpu().numpy().reshape(G, 8)
 t = t[t[:, 5] != 0]
-print("MLP0_TILE", os.environ.get("GATSSPG_MLP0_TILE"), "| other frames in flight during the traced launch:", NBG)
+print("other frames in flight during the traced launch:", NBG)
 # the buffer holds the LAST mlp0 launch of the frame (every launch overwrites it)
 t0 = t[:, 2].min()
 ent, loop, end = (t[:, 2] - t0) / 100.0, (t[:, 4] - t0) / 100.0, (t[:, 5] - t0) / 100.0
