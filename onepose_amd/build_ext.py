@@ -1,5 +1,5 @@
-"""Build libgatsspg_hip.so (matcher), libspp_hip.so (SuperPoint extractor), libpnp_hip.so (RANSAC-EPnP) and libsuperglue_hip.so
-(SuperGlue 2D-2D matcher) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libgatsspg_hip.so (matcher), libspp_hip.so (SuperPoint extractor), libpnp_hip.so (RANSAC-EPnP), libsuperglue_hip.so
+(SuperGlue 2D-2D matcher) and libdet_hip.so (2D object detector tail) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m onepose_amd.build_ext [--force] [--remarks] [--profiling] [--tuning]
 
@@ -30,6 +30,10 @@ PNP_HEADERS = [os.path.join("..", "..", "include", "pnp.h")]
 SG_LIB_PATH = os.path.join(LIB_DIR, "libsuperglue_hip.so")
 SG_SOURCES = [os.path.join("superglue", "superglue.hip")]
 SG_HEADERS = [os.path.join("..", "..", "include", "superglue", "superglue.h")]
+# the detector tail likewise: csrc/detector/ and include/detector/
+DET_LIB_PATH = os.path.join(LIB_DIR, "libdet_hip.so")
+DET_SOURCES = [os.path.join("detector", "detector.hip")]
+DET_HEADERS = [os.path.join("..", "..", "include", "detector", "detector.h")]
 
 
 def _hipcc():
@@ -48,7 +52,8 @@ def _stale(lib, deps):
 
 def is_stale():
     return (_stale(LIB_PATH, SOURCES + HEADERS) or _stale(SPP_LIB_PATH, SPP_SOURCES + SPP_HEADERS)
-            or _stale(PNP_LIB_PATH, PNP_SOURCES + PNP_HEADERS) or _stale(SG_LIB_PATH, SG_SOURCES + SG_HEADERS))
+            or _stale(PNP_LIB_PATH, PNP_SOURCES + PNP_HEADERS) or _stale(SG_LIB_PATH, SG_SOURCES + SG_HEADERS)
+            or _stale(DET_LIB_PATH, DET_SOURCES + DET_HEADERS))
 
 
 def source_hash():
@@ -70,14 +75,15 @@ def tuning_path(lib):
 
 
 def build(force=False, remarks=False, verbose=True, profiling=False, tuning=False, syntax_only=False):
-    """Compile every HIP source for gfx950 into onepose_amd/lib/lib{gatsspg,spp,pnp,superglue}_hip.so.
+    """Compile every HIP source for gfx950 into onepose_amd/lib/lib{gatsspg,spp,pnp,superglue,det}_hip.so.
     tuning / profiling builds go to lib*_tuning.so (environment knobs; profiling adds -DGATSSPG_PROFILING_BUILD: the timeline
     hooks) -- the package never loads those.  syntax_only: front-end check only."""
     os.makedirs(LIB_DIR, exist_ok=True)
     special = tuning or profiling
     for lib, srcs, deps in ((LIB_PATH, SOURCES, SOURCES + HEADERS), (SPP_LIB_PATH, SPP_SOURCES, SPP_SOURCES + SPP_HEADERS),
-                            (PNP_LIB_PATH, PNP_SOURCES, PNP_SOURCES + PNP_HEADERS), (SG_LIB_PATH, SG_SOURCES, SG_SOURCES + SG_HEADERS)):
-        if special and lib in (PNP_LIB_PATH, SG_LIB_PATH):     # no tuning knobs
+                            (PNP_LIB_PATH, PNP_SOURCES, PNP_SOURCES + PNP_HEADERS), (SG_LIB_PATH, SG_SOURCES, SG_SOURCES + SG_HEADERS),
+                            (DET_LIB_PATH, DET_SOURCES, DET_SOURCES + DET_HEADERS)):
+        if special and lib in (PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH):     # no tuning knobs
             continue
         out = tuning_path(lib) if special else lib
         if not force and not syntax_only and not _stale(out, deps):
