@@ -6,9 +6,9 @@ fallback: if the shared object is missing, ``load()`` raises.
 from __future__ import annotations
 
 import ctypes
-import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_void_p
 
+from ._binding import NativeError, bind  # noqa: F401
 from .build_ext import LIB_PATH
 
 NUM_GATS, NUM_ATTN = 4, 8
@@ -73,31 +73,4 @@ SYMBOLS = {
 }
 
 _lib = None
-
-
-class NativeError(RuntimeError):
-    pass
-
-
-def load():
-    """dlopen the HIP library and bind every entry point.  Raises if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NativeError(
-            f"{LIB_PATH} is missing: the GATsSPG HIP extension has not been built "
-            "(run `python -m onepose_amd.build_ext`; needs hipcc).  There is no CPU / PyTorch fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().gatsspg_last_error()
-        raise NativeError(f"{what} failed: {msg.decode() if msg else 'unknown error'}")
+load, check = bind(globals(), "GATsSPG", "gatsspg")

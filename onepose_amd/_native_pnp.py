@@ -1,11 +1,9 @@
 """ctypes binding of libpnp_hip.so (C ABI declared in include/pnp.h).  No fallback: a missing library raises."""
 from __future__ import annotations
 
-import ctypes
-import os
 from ctypes import POINTER, c_char_p, c_double, c_int, c_size_t, c_uint64, c_void_p
 
-from ._native import NativeError
+from ._binding import bind
 from .build_ext import PNP_LIB_PATH as LIB_PATH
 
 # name -> (restype, argtypes); every symbol include/pnp.h declares
@@ -21,26 +19,4 @@ SYMBOLS = {
 }
 
 _lib = None
-
-
-def load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NativeError(
-            f"{LIB_PATH} is missing: the PnP HIP extension has not been built "
-            "(run `python -m onepose_amd.build_ext`; needs hipcc).  There is no CPU / PyTorch fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().pnp_last_error()
-        raise NativeError(f"{what} failed: {msg.decode() if msg else 'unknown error'}")
+load, check = bind(globals(), "PnP", "pnp")

@@ -6,10 +6,9 @@ object is missing, ``load()`` raises.
 from __future__ import annotations
 
 import ctypes
-import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_void_p
 
-from ._native import NativeError
+from ._binding import bind
 from .build_ext import SPP_LIB_PATH as LIB_PATH
 
 NUM_LAYERS = 12
@@ -46,27 +45,4 @@ SYMBOLS = {
 }
 
 _lib = None
-
-
-def load():
-    """dlopen the HIP library and bind every entry point.  Raises if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NativeError(
-            f"{LIB_PATH} is missing: the SuperPoint HIP extension has not been built "
-            "(run `python -m onepose_amd.build_ext`; needs hipcc).  There is no CPU / PyTorch fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().spp_last_error()
-        raise NativeError(f"{what} failed: {msg.decode() if msg else 'unknown error'}")
+load, check = bind(globals(), "SuperPoint", "spp")

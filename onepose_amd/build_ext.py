@@ -17,23 +17,39 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
-LIB_PATH = os.path.join(LIB_DIR, "libgatsspg_hip.so")
-SOURCES = ["gatsspg_gemm_kernels.hip", "gatsspg_split_kernels.hip", "gatsspg_stream_kernels.hip", "gatsspg_capi.hip"]
-HEADERS = ["gatsspg_common.h", "gatsspg_launch.h", "gemm_f32_mfma.h", "gemm_split_glds.h", os.path.join("..", "..", "include", "gatsspg.h")]
-SPP_LIB_PATH = os.path.join(LIB_DIR, "libspp_hip.so")
-SPP_SOURCES = ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"]
-SPP_HEADERS = ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", os.path.join("..", "..", "include", "superpoint.h")]
-PNP_LIB_PATH = os.path.join(LIB_DIR, "libpnp_hip.so")
-PNP_SOURCES = ["pnp_kernels.hip"]
-PNP_HEADERS = [os.path.join("..", "..", "include", "pnp.h")]
-# the SuperGlue sources live in csrc/superglue/ and include/superglue/: source_hash() (top-level files only) does not see them
-SG_LIB_PATH = os.path.join(LIB_DIR, "libsuperglue_hip.so")
-SG_SOURCES = [os.path.join("superglue", "superglue.hip")]
-SG_HEADERS = [os.path.join("..", "..", "include", "superglue", "superglue.h")]
-# the detector tail likewise: csrc/detector/ and include/detector/
-DET_LIB_PATH = os.path.join(LIB_DIR, "libdet_hip.so")
-DET_SOURCES = [os.path.join("detector", "detector.hip")]
-DET_HEADERS = [os.path.join("..", "..", "include", "detector", "detector.h")]
+
+
+def _include(*parts):
+    return os.path.join("..", "..", "include", *parts)
+
+
+class Library:
+    """One shared library: its sources and headers (relative to csrc/) and whether it has a -DGATSSPG_TUNING / -DSPP_TUNING
+    variant (the others have no tuning knobs)."""
+
+    def __init__(self, name, sources, headers, tuning=False):
+        self.path = os.path.join(LIB_DIR, f"lib{name}_hip.so")
+        self.sources, self.headers, self.tuning = sources, headers, tuning
+
+
+# The SuperGlue and detector sources live in csrc/superglue/, csrc/detector/ and their include/ twins: source_hash() (top-level
+# files only) does not see them.
+LIBRARIES = (
+    Library("gatsspg", ["gatsspg_gemm_kernels.hip", "gatsspg_split_kernels.hip", "gatsspg_stream_kernels.hip", "gatsspg_capi.hip"],
+            ["gatsspg_common.h", "gatsspg_launch.h", "gemm_f32_mfma.h", "gemm_split_glds.h", "capi_common.h", _include("gatsspg.h")],
+            tuning=True),
+    Library("spp", ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"],
+            ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", _include("superpoint.h")], tuning=True),
+    Library("pnp", ["pnp_kernels.hip"], ["capi_common.h", "ransac_sample.h", _include("pnp.h")]),
+    Library("superglue", [os.path.join("superglue", "superglue.hip")], ["capi_common.h", _include("superglue", "superglue.h")]),
+    Library("det", [os.path.join("detector", "detector.hip")],
+            ["capi_common.h", "ransac_sample.h", _include("detector", "detector.h")]),
+)
+# views of the table under the names other modules use
+LIB_PATH, SPP_LIB_PATH, PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH = (lib.path for lib in LIBRARIES)
+SOURCES = LIBRARIES[0].sources
+SG_SOURCES, SG_HEADERS = LIBRARIES[3].sources, LIBRARIES[3].headers
+DET_SOURCES, DET_HEADERS = LIBRARIES[4].sources, LIBRARIES[4].headers
 
 
 def _hipcc():
@@ -51,9 +67,7 @@ def _stale(lib, deps):
 
 
 def is_stale():
-    return (_stale(LIB_PATH, SOURCES + HEADERS) or _stale(SPP_LIB_PATH, SPP_SOURCES + SPP_HEADERS)
-            or _stale(PNP_LIB_PATH, PNP_SOURCES + PNP_HEADERS) or _stale(SG_LIB_PATH, SG_SOURCES + SG_HEADERS)
-            or _stale(DET_LIB_PATH, DET_SOURCES + DET_HEADERS))
+    return any(_stale(lib.path, lib.sources + lib.headers) for lib in LIBRARIES)
 
 
 def source_hash():
@@ -80,13 +94,11 @@ def build(force=False, remarks=False, verbose=True, profiling=False, tuning=Fals
     hooks) -- the package never loads those.  syntax_only: front-end check only."""
     os.makedirs(LIB_DIR, exist_ok=True)
     special = tuning or profiling
-    for lib, srcs, deps in ((LIB_PATH, SOURCES, SOURCES + HEADERS), (SPP_LIB_PATH, SPP_SOURCES, SPP_SOURCES + SPP_HEADERS),
-                            (PNP_LIB_PATH, PNP_SOURCES, PNP_SOURCES + PNP_HEADERS), (SG_LIB_PATH, SG_SOURCES, SG_SOURCES + SG_HEADERS),
-                            (DET_LIB_PATH, DET_SOURCES, DET_SOURCES + DET_HEADERS)):
-        if special and lib in (PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH):     # no tuning knobs
+    for lib in LIBRARIES:
+        if special and not lib.tuning:
             continue
-        out = tuning_path(lib) if special else lib
-        if not force and not syntax_only and not _stale(out, deps):
+        out = tuning_path(lib.path) if special else lib.path
+        if not force and not syntax_only and not _stale(out, lib.sources + lib.headers):
             continue
         cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
         cmd += ["-fsyntax-only"] if syntax_only else ["-shared", "-o", out]
@@ -96,7 +108,7 @@ def build(force=False, remarks=False, verbose=True, profiling=False, tuning=Fals
             cmd += ["-DGATSSPG_TUNING", "-DSPP_TUNING"]
         if profiling:
             cmd.append("-DGATSSPG_PROFILING_BUILD")
-        cmd += [os.path.join(CSRC, s) for s in srcs]
+        cmd += [os.path.join(CSRC, s) for s in lib.sources]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True, cwd=CSRC)

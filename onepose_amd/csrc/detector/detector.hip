@@ -14,11 +14,11 @@
 // No FMA contraction: tests/detector_oracle.py restates every expression in the same order in numpy (which never fuses),
 // so hypothesis counts, masks and the refit can be compared exactly.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "../../../include/detector/detector.h"
+#include "../capi_common.h"
+#include "../ransac_sample.h"
 
 #pragma clang fp contract(off)
 
@@ -30,20 +30,12 @@ constexpr int HYP_PER_WAVE = 4;
 constexpr int HYP_PER_BLOCK = SCORE_THREADS / 64 * HYP_PER_WAVE;
 constexpr int FIN_THREADS = 256;     // the refit's reduction order (oracle: REFIT_LANES)
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // two distinct indices in [0, n), n >= 2: successive hash draws, duplicates rejected (oracle: sample_indices)
 __device__ __forceinline__ void sample_pair(unsigned long long seed, int hyp, int n, int& i0, int& i1) {
     unsigned long long ctr = 0;
-    i0 = (int)((splitmix64((seed << 40) ^ ((unsigned long long)hyp << 8) ^ ctr++) >> 11) % (unsigned long long)n);
+    i0 = sampling::draw(seed, hyp, ctr++, n);
     do {
-        i1 = (int)((splitmix64((seed << 40) ^ ((unsigned long long)hyp << 8) ^ ctr++) >> 11) % (unsigned long long)n);
+        i1 = sampling::draw(seed, hyp, ctr++, n);
     } while (i1 == i0);
 }
 
@@ -364,41 +356,22 @@ struct Workspace {
 };
 
 Workspace carve(void* base, int V, int cap0) {
-    char* p = reinterpret_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        char* q = p ? p + off : nullptr;
-        off += (nbytes + 255) / 256 * 256;
-        return q;
-    };
+    capi::Bump a(base);
     Workspace w;
-    w.pts = reinterpret_cast<float4*>(take((size_t)V * cap0 * sizeof(float4)));
-    w.src = reinterpret_cast<int*>(take((size_t)V * cap0 * sizeof(int)));
-    w.best = reinterpret_cast<unsigned long long*>(take((size_t)V * sizeof(unsigned long long)));
-    w.count = reinterpret_cast<int*>(take((size_t)V * sizeof(int)));
-    w.bytes = off;
+    w.pts = a.take<float4>((size_t)V * cap0 * sizeof(float4));
+    w.src = a.take<int>((size_t)V * cap0 * sizeof(int));
+    w.best = a.take<unsigned long long>((size_t)V * sizeof(unsigned long long));
+    w.count = a.take<int>((size_t)V * sizeof(int));
+    w.bytes = a.off;
     return w;
 }
 
 }  // namespace det
 
 using namespace det;
+using namespace capi;
 
 namespace {
-thread_local char g_err[512] = "";
-int fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-int fail(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return -1;
-}
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: %s", what, hipGetErrorString(e));
-    return 0;
-}
 constexpr int MAX_VIEWS = 4096, MAX_CAP0 = 1 << 20, MAX_ITERATIONS = 1 << 24;
 bool shape_ok(int V, int cap0, int iterations) {
     return V >= 1 && V <= MAX_VIEWS && cap0 >= 1 && cap0 <= MAX_CAP0 && iterations >= 1 && iterations <= MAX_ITERATIONS;
@@ -408,12 +381,12 @@ int ransac(const float* kpts0, const int32_t* n0, const int64_t* matches0, const
            int min_matches, double thr, int iterations, uint64_t seed, double* affine, int32_t* mask, int32_t* info, void* workspace,
            size_t workspace_bytes, det_stream_t stream, const char* what) {
     if (!shape_ok(V, cap0, iterations))
-        return fail("%s: V in [1, %d], cap0 / n in [1, %d] and iterations in [1, %d] expected (got %d, %d, %d)", what, MAX_VIEWS,
+        return fail(-1, "%s: V in [1, %d], cap0 / n in [1, %d] and iterations in [1, %d] expected (got %d, %d, %d)", what, MAX_VIEWS,
                     MAX_CAP0, MAX_ITERATIONS, V, cap0, iterations);
-    if (!(thr > 0.0)) return fail("%s: reproj_threshold must be positive", what);
-    if (!workspace) return fail("%s: null workspace", what);
+    if (!(thr > 0.0)) return fail(-1, "%s: reproj_threshold must be positive", what);
+    if (!workspace) return fail(-1, "%s: null workspace", what);
     Workspace w = carve(workspace, V, cap0);
-    if (workspace_bytes < w.bytes) { fail("%s: workspace too small: %zu < %zu bytes", what, workspace_bytes, w.bytes); return -2; }
+    if (workspace_bytes < w.bytes) return fail(-2, "%s: workspace too small: %zu < %zu bytes", what, workspace_bytes, w.bytes);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const double thr2 = thr * thr;
     hipLaunchKernelGGL(det_gather_kernel, dim3(V), dim3(1024), 0, s, kpts0, n0, reinterpret_cast<const long long*>(matches0), kpts1, cap0,
@@ -422,7 +395,7 @@ int ransac(const float* kpts0, const int32_t* n0, const int64_t* matches0, const
                        w.count, cap0, min_matches, thr2, iterations, (unsigned long long)seed, w.best);
     hipLaunchKernelGGL(det_finish_kernel, dim3(V), dim3(FIN_THREADS), 0, s, w.pts, w.src, w.count, w.best, cap0, min_matches, thr2,
                        (unsigned long long)seed, affine, mask, info);
-    return check_launch(what);
+    return check_launch(-1, what);
 }
 }  // namespace
 
@@ -432,14 +405,14 @@ int det_version(void) { return 1; }
 const char* det_last_error(void) { return g_err; }
 
 size_t det_workspace_bytes(int V, int cap0, int iterations) {
-    if (!shape_ok(V, cap0, iterations)) { fail("det_workspace_bytes: shape out of range"); return 0; }
+    if (!shape_ok(V, cap0, iterations)) { fail(-1, "det_workspace_bytes: shape out of range"); return 0; }
     return carve(nullptr, V, cap0).bytes;
 }
 
 int det_affine_partial_ransac(const float* src, const float* dst, int n, double reproj_threshold, int iterations, uint64_t seed,
                               double* affine, int32_t* inlier_mask, int32_t* info, void* workspace, size_t workspace_bytes,
                               det_stream_t stream) {
-    if (!src || !dst || !affine || !inlier_mask || !info) return fail("det_affine_partial_ransac: null argument");
+    if (!src || !dst || !affine || !inlier_mask || !info) return fail(-1, "det_affine_partial_ransac: null argument");
     return ransac(src, nullptr, nullptr, dst, 1, n, n, n, 2, reproj_threshold, iterations, seed, affine, inlier_mask, info, workspace,
                   workspace_bytes, stream, "det_affine_partial_ransac");
 }
@@ -447,29 +420,29 @@ int det_affine_partial_ransac(const float* src, const float* dst, int n, double 
 int det_affine_partial_from_matches(const float* kpts0, const int32_t* n0, const int64_t* matches0, const float* kpts1, int V, int cap0,
                                     int n1, double reproj_threshold, int iterations, uint64_t seed, double* affine, int32_t* inlier_mask,
                                     int32_t* info, void* workspace, size_t workspace_bytes, det_stream_t stream) {
-    if (!kpts0 || !n0 || !matches0 || !affine || !inlier_mask || !info) return fail("det_affine_partial_from_matches: null argument");
-    if (n1 < 0 || (n1 > 0 && !kpts1)) return fail("det_affine_partial_from_matches: n1 must be >= 0 and kpts1 non-null when n1 > 0");
+    if (!kpts0 || !n0 || !matches0 || !affine || !inlier_mask || !info) return fail(-1, "det_affine_partial_from_matches: null argument");
+    if (n1 < 0 || (n1 > 0 && !kpts1)) return fail(-1, "det_affine_partial_from_matches: n1 must be >= 0 and kpts1 non-null when n1 > 0");
     return ransac(kpts0, n0, matches0, kpts1, V, cap0, n1, 0, DET_MIN_MATCHES, reproj_threshold, iterations, seed, affine, inlier_mask,
                   info, workspace, workspace_bytes, stream, "det_affine_partial_from_matches");
 }
 
 int det_bbox_vote(const double* affine, const int32_t* info, const int32_t* hw0, int V, int query_h, int query_w, int rank_by,
                   int32_t* boxes, int32_t* bbox, int32_t* best_view, det_stream_t stream) {
-    if (!affine || !info || !hw0 || !boxes || !bbox || !best_view) return fail("det_bbox_vote: null argument");
-    if (V < 1 || V > MAX_VIEWS) return fail("det_bbox_vote: V in [1, %d] expected (got %d)", MAX_VIEWS, V);
-    if (rank_by != DET_RANK_BY_MATCHES && rank_by != DET_RANK_BY_INLIERS) return fail("det_bbox_vote: unknown rank_by %d", rank_by);
-    if (query_h < 1 || query_w < 1) return fail("det_bbox_vote: query size must be positive");
+    if (!affine || !info || !hw0 || !boxes || !bbox || !best_view) return fail(-1, "det_bbox_vote: null argument");
+    if (V < 1 || V > MAX_VIEWS) return fail(-1, "det_bbox_vote: V in [1, %d] expected (got %d)", MAX_VIEWS, V);
+    if (rank_by != DET_RANK_BY_MATCHES && rank_by != DET_RANK_BY_INLIERS) return fail(-1, "det_bbox_vote: unknown rank_by %d", rank_by);
+    if (query_h < 1 || query_w < 1) return fail(-1, "det_bbox_vote: query size must be positive");
     hipLaunchKernelGGL(det_vote_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), affine, info, hw0, V, query_h,
                        query_w, rank_by, boxes, bbox, best_view);
-    return check_launch("det_bbox_vote");
+    return check_launch(-1, "det_bbox_vote");
 }
 
 int det_crop_resize(const uint8_t* image_u8, int H, int W, const int32_t* bbox, const double* K_host, int crop_size, float* out,
                     double* K_crop, int32_t* info, det_stream_t stream) {
-    if (!image_u8 || !bbox || !K_host || !out || !K_crop || !info) return fail("det_crop_resize: null argument");
-    if (H < 1 || W < 1 || (long long)H * W > (1ll << 31)) return fail("det_crop_resize: image size out of range");
+    if (!image_u8 || !bbox || !K_host || !out || !K_crop || !info) return fail(-1, "det_crop_resize: null argument");
+    if (H < 1 || W < 1 || (long long)H * W > (1ll << 31)) return fail(-1, "det_crop_resize: image size out of range");
     if (crop_size < 2 || crop_size > 2048 || (crop_size & (crop_size - 1)))
-        return fail("det_crop_resize: crop_size must be a power of two in [2, 2048] (got %d): the exact-integer resampling needs it",
+        return fail(-1, "det_crop_resize: crop_size must be a power of two in [2, 2048] (got %d): the exact-integer resampling needs it",
                     crop_size);
     int lg = 0;
     while ((1 << lg) < crop_size) ++lg;
@@ -477,7 +450,7 @@ int det_crop_resize(const uint8_t* image_u8, int H, int W, const int32_t* bbox, 
     memcpy(K.k, K_host, sizeof(K.k));
     hipLaunchKernelGGL(det_crop_kernel, dim3((crop_size + 63) / 64, (crop_size + 3) / 4), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), image_u8, H, W, bbox, K, crop_size, lg, out, K_crop, info);
-    return check_launch("det_crop_resize");
+    return check_launch(-1, "det_crop_resize");
 }
 
 }  // extern "C"

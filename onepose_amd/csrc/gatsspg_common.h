@@ -5,7 +5,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "capi_common.h"
+
 namespace gatsspg {
+
+using capi::round_up;
 
 constexpr int D = 256;    // descriptor_dim (hard-coded by the reference GNN, GATs_SuperGlue.py:35-36)
 constexpr int H = 4;      // heads (GATs_SuperGlue.py:43)
@@ -36,8 +40,6 @@ struct ColLayout {
     int side_mask;   // bit 0: 2D-side segments active, bit 1: 3D-side segments (segment-level reduction kernels)
     int xgs;         // XCD granule of the split kernels' tile map, log2 of column tiles (xcd_tile_map_g); always 0
 };
-
-__host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 __host__ __device__ inline ColLayout make_layout(int b, int n1, int n2) {
     ColLayout L;
@@ -155,8 +157,6 @@ struct Workspace {
     size_t bytes;
 };
 
-inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-
 // M_t of segment `seg`: element (r, c), c = h*64 + d, at mop_seg(Mop, seg)[r * MOP_LD + c]
 __host__ __device__ inline float* mop_seg(float* Mop, int seg) { return Mop + (size_t)(seg >> 1) * 512 * MOP_LD + ((seg & 1) ? 0 : 256); }
 __host__ __device__ inline const float* mop_seg(const float* Mop, int seg) {
@@ -174,37 +174,35 @@ inline Workspace carve_workspace(void* base, int b, int n1, int n2) {
     w.sc_nrt = L.n1p / SC_BM;
     w.cf_nst = (n1 + CF_ROWS - 1) / CF_ROWS;
     w.cf_nch = (n2 + CF_COLS - 1) / CF_COLS;
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t nbytes) { char* r = p ? p + off : nullptr; off += align_up(nbytes); return r; };
+    capi::Bump a(base);
     const size_t ld = L.ld;
-    w.Z = (float*)take(sizeof(float) * D * ld);
-    w.Q = (float*)take(sizeof(float) * D * ld);
-    w.MSG = (float*)take(sizeof(float) * D * ld);
-    w.U = (float*)take(sizeof(float) * 2 * D * ld);
+    w.Z = a.take<float>(sizeof(float) * D * ld);
+    w.Q = a.take<float>(sizeof(float) * D * ld);
+    w.MSG = a.take<float>(sizeof(float) * D * ld);
+    w.U = a.take<float>(sizeof(float) * 2 * D * ld);
     w.MD = w.Q;
     w.MDT = w.MSG;   // b * n1p * 256 floats <= 256 * ld
-    w.MDTp = (unsigned short*)take(sizeof(unsigned short) * 3 * (size_t)b * L.n1p * D);
-    w.kvpart = (float*)take(sizeof(float) * (size_t)w.nt64 * H * KVP);
-    w.kvfin = (float*)take(sizeof(float) * (size_t)w.nseg * H * KVP);
-    w.Mop = (float*)take(sizeof(float) * (size_t)b * 512 * MOP_LD);
-    w.Mpl = (unsigned short*)take(sizeof(unsigned short) * (size_t)w.nseg * 3 * MPL_PLANE);
-    w.ksumT = (float*)take(sizeof(float) * (size_t)w.nseg * H * DH);
-    w.zsc = (float*)take(sizeof(float) * (size_t)w.nseg * H);
-    w.statpart = (float*)take(sizeof(float) * (size_t)w.nt64 * 2 * 2 * 512);   // one partial per 64 columns, or per 32 (mlp0_sp's transposed epilogue)
-    w.stats = (float*)take(sizeof(float) * (size_t)w.nseg * 2 * 512);
-    w.statcnt = (int*)take(sizeof(int) * (size_t)w.nseg * 8);
-    w.rowpart = (float*)take(sizeof(float) * (size_t)b * w.sc_nct * L.n1p);
-    w.colpart = (float*)take(sizeof(float) * (size_t)b * w.sc_nrt * L.n2p);
-    w.rs = (float*)take(sizeof(float) * (size_t)b * L.n1p);
-    w.cs = (float*)take(sizeof(float) * (size_t)b * L.n2p);
-    w.rmax_v = (float*)take(sizeof(float) * (size_t)b * w.cf_nch * L.n1p);
-    w.rmax_i = (int*)take(sizeof(int) * (size_t)b * w.cf_nch * L.n1p);
-    w.cmax_v = (float*)take(sizeof(float) * (size_t)b * w.cf_nst * L.n2p);
-    w.cmax_i = (int*)take(sizeof(int) * (size_t)b * w.cf_nst * L.n2p);
-    w.rshift = (float*)take(sizeof(float) * (size_t)b * L.n1p);
-    w.cshift = (float*)take(sizeof(float) * (size_t)b * L.n2p);
-    w.bytes = off;
+    w.MDTp = a.take<unsigned short>(sizeof(unsigned short) * 3 * (size_t)b * L.n1p * D);
+    w.kvpart = a.take<float>(sizeof(float) * (size_t)w.nt64 * H * KVP);
+    w.kvfin = a.take<float>(sizeof(float) * (size_t)w.nseg * H * KVP);
+    w.Mop = a.take<float>(sizeof(float) * (size_t)b * 512 * MOP_LD);
+    w.Mpl = a.take<unsigned short>(sizeof(unsigned short) * (size_t)w.nseg * 3 * MPL_PLANE);
+    w.ksumT = a.take<float>(sizeof(float) * (size_t)w.nseg * H * DH);
+    w.zsc = a.take<float>(sizeof(float) * (size_t)w.nseg * H);
+    w.statpart = a.take<float>(sizeof(float) * (size_t)w.nt64 * 2 * 2 * 512);   // one partial per 64 columns, or per 32 (mlp0_sp's transposed epilogue)
+    w.stats = a.take<float>(sizeof(float) * (size_t)w.nseg * 2 * 512);
+    w.statcnt = a.take<int>(sizeof(int) * (size_t)w.nseg * 8);
+    w.rowpart = a.take<float>(sizeof(float) * (size_t)b * w.sc_nct * L.n1p);
+    w.colpart = a.take<float>(sizeof(float) * (size_t)b * w.sc_nrt * L.n2p);
+    w.rs = a.take<float>(sizeof(float) * (size_t)b * L.n1p);
+    w.cs = a.take<float>(sizeof(float) * (size_t)b * L.n2p);
+    w.rmax_v = a.take<float>(sizeof(float) * (size_t)b * w.cf_nch * L.n1p);
+    w.rmax_i = a.take<int>(sizeof(int) * (size_t)b * w.cf_nch * L.n1p);
+    w.cmax_v = a.take<float>(sizeof(float) * (size_t)b * w.cf_nst * L.n2p);
+    w.cmax_i = a.take<int>(sizeof(int) * (size_t)b * w.cf_nst * L.n2p);
+    w.rshift = a.take<float>(sizeof(float) * (size_t)b * L.n1p);
+    w.cshift = a.take<float>(sizeof(float) * (size_t)b * L.n2p);
+    w.bytes = a.off;
     return w;
 }
 

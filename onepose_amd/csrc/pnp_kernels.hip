@@ -8,13 +8,13 @@
 //                 bits, then runs the same dense stage), pose written as [R | t / scale]
 // The EPnP steps follow OpenCV calib3d/epnp.cpp (see oracle/pnp_oracle.py for the restated algorithm and citations).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <type_traits>
 
 #include "../../include/pnp.h"
+#include "capi_common.h"
+#include "ransac_sample.h"
 
 namespace pnp {
 
@@ -23,22 +23,12 @@ struct Cam {
 };
 constexpr int MODEL_POINTS = 5;
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // MODEL_POINTS distinct indices in [0, n): successive hash draws, duplicates rejected (oracle: sample_indices)
 __device__ void sample_indices(unsigned long long seed, int hyp, int n, int (&idx)[MODEL_POINTS]) {
     int got = 0;
     unsigned long long ctr = 0;
     while (got < MODEL_POINTS) {
-        const unsigned long long r = splitmix64((seed << 40) ^ ((unsigned long long)hyp << 8) ^ ctr);
-        ++ctr;
-        const int v = (int)((r >> 11) % (unsigned long long)n);
+        const int v = sampling::draw(seed, hyp, ctr++, n);
         bool dup = false;
         for (int k = 0; k < got; ++k) dup |= idx[k] == v;
         if (!dup) idx[got++] = v;
@@ -671,42 +661,26 @@ struct Workspace {
     float *p2, *p3;
     size_t bytes;
 };
-inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 inline Workspace carve(void* base, int n, int iterations) {
     Workspace w;
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t nb) { char* r = p ? p + off : nullptr; off += align_up(nb); return r; };
-    w.hyp = (double*)take(sizeof(double) * 12 * (size_t)iterations);
-    w.counts = (int*)take(sizeof(int) * (size_t)iterations);
-    w.inl = (int*)take(sizeof(int) * (size_t)n);
-    w.src = (int*)take(sizeof(int) * (size_t)n);
-    w.count = (int*)take(sizeof(int));
-    w.p2 = (float*)take(sizeof(float) * 2 * (size_t)n);
-    w.p3 = (float*)take(sizeof(float) * 3 * (size_t)n);
-    w.bytes = off;
+    capi::Bump a(base);
+    w.hyp = a.take<double>(sizeof(double) * 12 * (size_t)iterations);
+    w.counts = a.take<int>(sizeof(int) * (size_t)iterations);
+    w.inl = a.take<int>(sizeof(int) * (size_t)n);
+    w.src = a.take<int>(sizeof(int) * (size_t)n);
+    w.count = a.take<int>(sizeof(int));
+    w.p2 = a.take<float>(sizeof(float) * 2 * (size_t)n);
+    w.p3 = a.take<float>(sizeof(float) * 3 * (size_t)n);
+    w.bytes = a.off;
     return w;
 }
 
 }  // namespace pnp
 
 using namespace pnp;
+using namespace capi;
 
 namespace {
-thread_local char g_err[512] = "";
-int fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-int fail(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return -1;
-}
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: %s", what, hipGetErrorString(e));
-    return 0;
-}
 Cam cam_of(const double* K) { return Cam{K[0], K[4], K[2], K[5]}; }
 }  // namespace
 
@@ -716,19 +690,19 @@ int pnp_version(void) { return 1; }
 const char* pnp_last_error(void) { return g_err; }
 
 size_t pnp_workspace_bytes(int n, int iterations) {
-    if (n < 1 || iterations < 1) { fail("n and iterations must be >= 1"); return 0; }
+    if (n < 1 || iterations < 1) { fail(-1, "n and iterations must be >= 1"); return 0; }
     return carve(nullptr, n, iterations).bytes;
 }
 
 int pnp_ransac_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, double reproj_error,
                     int iterations, uint64_t seed, double* pose, int32_t* inlier_mask, int32_t* info, void* workspace,
                     size_t workspace_bytes, pnp_stream_t stream) {
-    if (!pts_3d || !pts_2d || !K_host || !pose || !inlier_mask || !info || !workspace) return fail("null argument");
-    if (n < MODEL_POINTS) return fail("solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
-    if (iterations < 1 || iterations > (1 << 24)) return fail("iterations out of range");
-    if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail("scale and reproj_error must be positive");
+    if (!pts_3d || !pts_2d || !K_host || !pose || !inlier_mask || !info || !workspace) return fail(-1, "null argument");
+    if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
+    if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
+    if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
     Workspace w = carve(workspace, n, iterations);
-    if (workspace_bytes < w.bytes) return fail("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+    if (workspace_bytes < w.bytes) return fail(-1, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Cam cam = cam_of(K_host);
     const double thr2 = reproj_error * reproj_error;
@@ -740,18 +714,18 @@ int pnp_ransac_epnp(const float* pts_3d, const float* pts_2d, const double* K_ho
     hipLaunchKernelGGL(best_kernel, dim3(1), dim3(1024), 0, s, pts_3d, pts_2d, n, nd, scale, cam, thr2, iterations, w.hyp, w.counts,
                        nd, inlier_mask, w.inl, info);
     hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(64), 0, s, pts_3d, pts_2d, n, scale, cam, w.inl, info, pose);
-    return check_launch("pnp_ransac_epnp");
+    return check_launch(-1, "pnp_ransac_epnp");
 }
 
 int pnp_ransac_epnp_matches(const float* kpts2d, const float* kpts3d, const int64_t* matches0, int n1, const double* K_host,
                             double scale, double reproj_error, int iterations, uint64_t seed, double* pose, int32_t* inlier_mask,
                             int32_t* info, void* workspace, size_t workspace_bytes, pnp_stream_t stream) {
-    if (!kpts2d || !kpts3d || !matches0 || !K_host || !pose || !inlier_mask || !info || !workspace) return fail("null argument");
-    if (n1 < 1) return fail("n1 must be >= 1");
-    if (iterations < 1 || iterations > (1 << 24)) return fail("iterations out of range");
-    if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail("scale and reproj_error must be positive");
+    if (!kpts2d || !kpts3d || !matches0 || !K_host || !pose || !inlier_mask || !info || !workspace) return fail(-1, "null argument");
+    if (n1 < 1) return fail(-1, "n1 must be >= 1");
+    if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
+    if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
     Workspace w = carve(workspace, n1, iterations);
-    if (workspace_bytes < w.bytes) return fail("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+    if (workspace_bytes < w.bytes) return fail(-1, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Cam cam = cam_of(K_host);
     const double thr2 = reproj_error * reproj_error;
@@ -764,18 +738,18 @@ int pnp_ransac_epnp_matches(const float* kpts2d, const float* kpts3d, const int6
     hipLaunchKernelGGL(best_kernel, dim3(1), dim3(1024), 0, s, w.p3, w.p2, 0, w.count, scale, cam, thr2, iterations, w.hyp, w.counts,
                        w.src, inlier_mask, w.inl, info);
     hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(64), 0, s, w.p3, w.p2, 0, scale, cam, w.inl, info, pose);
-    return check_launch("pnp_ransac_epnp_matches");
+    return check_launch(-1, "pnp_ransac_epnp_matches");
 }
 
 int pnp_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, double* pose, void* workspace,
              size_t workspace_bytes, pnp_stream_t stream) {
     (void)workspace; (void)workspace_bytes;
-    if (!pts_3d || !pts_2d || !K_host || !pose) return fail("null argument");
-    if (n < 4) return fail("EPnP needs at least 4 correspondences (got %d)", n);
-    if (!(scale > 0.0)) return fail("scale must be positive");
+    if (!pts_3d || !pts_2d || !K_host || !pose) return fail(-1, "null argument");
+    if (n < 4) return fail(-1, "EPnP needs at least 4 correspondences (got %d)", n);
+    if (!(scale > 0.0)) return fail(-1, "scale must be positive");
     hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n, scale,
                        cam_of(K_host), (const int*)nullptr, (int32_t*)nullptr, pose);
-    return check_launch("pnp_epnp");
+    return check_launch(-1, "pnp_epnp");
 }
 
 }  // extern "C"

@@ -5,7 +5,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "capi_common.h"
+
 namespace spp {
+
+using capi::round_up;
 
 constexpr int DD = 256;          // descriptor_dim
 constexpr int NMS_E = 64;        // NMS workgroup region (tile + 2 * 5 * radius halo)
@@ -19,7 +23,6 @@ constexpr int MAX_R = 6;
 struct FeatLayout {
     int b, H, W, Wp, plane, ld, ldt;
 };
-__host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 __host__ __device__ inline FeatLayout make_feat_layout(int b, int H, int W) {
     FeatLayout L;
     L.b = b; L.H = H; L.W = W; L.Wp = W + 2;
@@ -86,7 +89,6 @@ struct Workspace {
     unsigned* skey;
     size_t bytes;
 };
-inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
 inline Workspace carve_workspace(void* base, int b, int H, int W) {
     Workspace w;
@@ -95,13 +97,11 @@ inline Workspace carve_workspace(void* base, int b, int H, int W) {
     w.L2 = make_feat_layout(b, H / 2, W / 2);
     w.L3 = make_feat_layout(b, H / 4, W / 4);
     w.L4 = make_feat_layout(b, H / 8, W / 8);
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t nbytes) { char* r = p ? p + off : nullptr; off += align_up(nbytes); return r; };
+    capi::Bump a(base);
     auto feat = [&](int C, const FeatLayout& L) {
-        take(sizeof(float) * feat_guard(L));    // front guard (the previous buffer's back guard is separate: simple, tiny)
-        float* r = (float*)take(sizeof(float) * (size_t)C * L.ldt);
-        take(sizeof(float) * feat_guard(L));
+        a.take(sizeof(float) * feat_guard(L));    // front guard (the previous buffer's back guard is separate: simple, tiny)
+        float* r = a.take<float>(sizeof(float) * (size_t)C * L.ldt);
+        a.take(sizeof(float) * feat_guard(L));
         return r;
     };
     w.a1 = feat(64, w.L1); w.b1 = feat(64, w.L1);
@@ -110,19 +110,19 @@ inline Workspace carve_workspace(void* base, int b, int H, int W) {
     w.a4 = feat(128, w.L4); w.b4 = feat(128, w.L4);
     w.hd = feat(512, w.L4); w.lg = feat(128, w.L4); w.dd = feat(256, w.L4);
     const size_t px = (size_t)b * H * W;
-    w.score = (float*)take(sizeof(float) * px);
-    w.nms = (float*)take(sizeof(float) * px);
-    w.invn = (float*)take(sizeof(float) * (size_t)b * (H / 8) * (W / 8));
-    w.rowcnt = (int*)take(sizeof(int) * (size_t)b * H);
-    w.rowoff = (int*)take(sizeof(int) * (size_t)b * H);
-    w.ncand = (int*)take(sizeof(int) * (size_t)b);
-    w.cand = (int*)take(sizeof(int) * px);
-    w.sel = (int*)take(sizeof(int) * px);
-    w.rank = (int*)take(sizeof(int) * px);
-    w.surv = (int*)take(sizeof(int) * px);
-    w.cscore = (float*)take(sizeof(float) * px);
-    w.skey = (unsigned*)take(sizeof(unsigned) * px);
-    w.bytes = off;
+    w.score = a.take<float>(sizeof(float) * px);
+    w.nms = a.take<float>(sizeof(float) * px);
+    w.invn = a.take<float>(sizeof(float) * (size_t)b * (H / 8) * (W / 8));
+    w.rowcnt = a.take<int>(sizeof(int) * (size_t)b * H);
+    w.rowoff = a.take<int>(sizeof(int) * (size_t)b * H);
+    w.ncand = a.take<int>(sizeof(int) * (size_t)b);
+    w.cand = a.take<int>(sizeof(int) * px);
+    w.sel = a.take<int>(sizeof(int) * px);
+    w.rank = a.take<int>(sizeof(int) * px);
+    w.surv = a.take<int>(sizeof(int) * px);
+    w.cscore = a.take<float>(sizeof(float) * px);
+    w.skey = a.take<unsigned>(sizeof(unsigned) * px);
+    w.bytes = a.off;
     return w;
 }
 

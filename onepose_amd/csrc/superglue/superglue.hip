@@ -7,29 +7,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 
 #include "../../../include/superglue/superglue.h"
+#include "../capi_common.h"
 
 namespace {
+
+using namespace capi;
 
 constexpr int D = SG_DESC_DIM;
 constexpr int KENC[6] = {3, 32, 64, 128, 256, 256};
 constexpr float BN_EPS = 1e-5f;
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Packed weight layout (floats).  BatchNorm parameters are packed as [4][C]: running_mean, running_var, gamma, beta.
@@ -503,8 +493,6 @@ __global__ void sg_tail_kernel(const float* mx0, const int* ix0, const float* mx
 // ---------------------------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------------------------
-size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-
 struct Layout {
     int b, n0, n1, nm;
     size_t side_floats[7];   // per-side channel counts of the activation buffers below
@@ -518,17 +506,16 @@ Layout make_layout(int b, int n0, int n1) {
     L.b = b; L.n0 = n0; L.n1 = n1; L.nm = std::max(n0, n1);
     L.nchunk = (n0 + 255) / 256;
     const size_t P = size_t(b) * L.nm * 4;   // bytes per channel row-set of one side
-    size_t p = 0;
-    auto take = [&](size_t bytes) { size_t o = p; p += align_up(bytes); return o; };
-    L.xa = take(2 * CH_XA * P); L.xb = take(2 * CH_XB * P); L.q = take(2 * CH_Q * P); L.kv = take(2 * CH_KV * P);
-    L.msg = take(2 * CH_MSG * P); L.mrg = take(2 * CH_MRG * P); L.hb = take(2 * CH_HB * P);
+    Bump a(nullptr);   // offsets, not pointers: the layout is built before the workspace is known
+    L.xa = a.reserve(2 * CH_XA * P); L.xb = a.reserve(2 * CH_XB * P); L.q = a.reserve(2 * CH_Q * P); L.kv = a.reserve(2 * CH_KV * P);
+    L.msg = a.reserve(2 * CH_MSG * P); L.mrg = a.reserve(2 * CH_MRG * P); L.hb = a.reserve(2 * CH_HB * P);
     const size_t zsz = size_t(b) * (n0 + 1) * (n1 + 1) * 4;
-    L.z = take(zsz); L.zt = take(zsz);
-    L.u = take(size_t(b) * (n0 + 1) * 4); L.v = take(size_t(b) * (n1 + 1) * 4);
-    L.mx0 = take(size_t(b) * n0 * 4); L.ix0 = take(size_t(b) * n0 * 4);
-    L.mx1 = take(size_t(b) * n1 * 4); L.ix1 = take(size_t(b) * n1 * 4);
-    L.pv = take(size_t(b) * L.nchunk * n1 * 4); L.pi = take(size_t(b) * L.nchunk * n1 * 4);
-    L.total = p;
+    L.z = a.reserve(zsz); L.zt = a.reserve(zsz);
+    L.u = a.reserve(size_t(b) * (n0 + 1) * 4); L.v = a.reserve(size_t(b) * (n1 + 1) * 4);
+    L.mx0 = a.reserve(size_t(b) * n0 * 4); L.ix0 = a.reserve(size_t(b) * n0 * 4);
+    L.mx1 = a.reserve(size_t(b) * n1 * 4); L.ix1 = a.reserve(size_t(b) * n1 * 4);
+    L.pv = a.reserve(size_t(b) * L.nchunk * n1 * 4); L.pi = a.reserve(size_t(b) * L.nchunk * n1 * 4);
+    L.total = a.off;
     return L;
 }
 
@@ -544,11 +531,7 @@ struct Ctx {
     int* i(size_t off) const { return reinterpret_cast<int*>(ws + off); }
 };
 
-int launch_status(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-3, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return 0;
-}
+int launch_status(const char* what) { return check_launch(-3, what, ": launch failed: "); }
 
 int check_common(int b, int n0, int n1, void* ws, size_t ws_bytes) {
     if (b < 1 || n0 < 1 || n1 < 1) return fail(-1, "b, n0, n1 must be >= 1 (got %d, %d, %d)", b, n0, n1);

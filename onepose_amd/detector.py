@@ -14,7 +14,6 @@ MATCHES (``inliers.shape[0]`` of cv2's N x 1 mask), not of inliers -- ``rank_by=
 """
 from __future__ import annotations
 
-import ctypes
 import os
 import os.path as osp
 import struct
@@ -24,22 +23,16 @@ import numpy as np
 import torch
 
 from . import _native_det
-from ._native import NativeError  # noqa: F401
+from ._binding import NativeError, WorkspaceCache, k_array, stream_handle  # noqa: F401
 from .superglue import SuperGlue
 
 REPROJ_THRESHOLD = 6.0     # local_feature_2D_detector.py:105
 NO_CPU = "onepose_amd.LocalFeatureObjectDetector runs only on a ROCm GPU ({}); there is no CPU fallback"
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _k_array(K):
-    k = np.ascontiguousarray(np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float64))
-    if k.shape == (3, 4):                       # get_K_crop_resize accepts the homogeneous form too
-        k = k[:, :3]
-    return (ctypes.c_double * 9)(*k.reshape(9).tolist())
+    k = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K)
+    return k_array(k[:, :3] if k.shape == (3, 4) else k)      # get_K_crop_resize accepts the homogeneous form too
 
 
 # ---- COLMAP image names (only the names are needed; written from COLMAP's published model format) -----------------
@@ -144,7 +137,7 @@ class LocalFeatureObjectDetector:
         self.output_results = output_results
         self.detect_save_dir = detect_save_dir
         self.K_crop_save_dir = K_crop_save_dir
-        self._ws = {}
+        self._workspaces = WorkspaceCache(6)
         self.last = None
         if ref_images is None:
             if sfm_ws_dir is None:
@@ -200,16 +193,9 @@ class LocalFeatureObjectDetector:
         self.scores0 = torch.zeros(V, cap0, device=dev, dtype=torch.float32)
 
     def _workspace(self, dev):
-        key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = self.lib.det_workspace_bytes(self.V, self.cap0, self.iterations)
-            if nbytes == 0:
-                raise NativeError(f"det_workspace_bytes({self.V}, {self.cap0}, {self.iterations}) refused the shape")
-            if len(self._ws) >= 6:
-                self._ws.clear()
-            ws = self._ws[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        return ws
+        shape = (self.V, self.cap0, self.iterations)
+        return self._workspaces.get(shape, dev, self.lib.det_workspace_bytes,
+                                    lambda: "det_workspace_bytes({}, {}, {}) refused the shape".format(*shape))
 
     # ---- stages ----
     def _check_frame(self, query_img):
@@ -268,11 +254,11 @@ class LocalFeatureObjectDetector:
             _native_det.check(self.lib.det_affine_partial_from_matches(
                 self.kpts0.data_ptr(), self.n0.data_ptr(), self.matches0.data_ptr(), k1.data_ptr() if k1.shape[0] else None, V, cap0,
                 int(k1.shape[0]), REPROJ_THRESHOLD, self.iterations, self.seed, out["affine"].data_ptr(), out["mask"].data_ptr(),
-                out["info"].data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "det_affine_partial_from_matches")
+                out["info"].data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "det_affine_partial_from_matches")
             _native_det.check(self.lib.det_bbox_vote(
                 out["affine"].data_ptr(), out["info"].data_ptr(), self.hw0.data_ptr(), V, int(query_hw[0]), int(query_hw[1]),
                 _native_det.RANK_BY[self.rank_by], out["boxes"].data_ptr(), out["bbox"].data_ptr(), out["best_view"].data_ptr(),
-                _stream(dev)), "det_bbox_vote")
+                stream_handle(dev)), "det_bbox_vote")
         return out
 
     @torch.no_grad()
@@ -287,7 +273,7 @@ class LocalFeatureObjectDetector:
         info = torch.empty(4, device=dev, dtype=torch.int32)
         with torch.cuda.device(dev):
             _native_det.check(self.lib.det_crop_resize(plane.data_ptr(), H, W, bbox.data_ptr(), _k_array(K), int(crop_size),
-                                                       crop.data_ptr(), K_crop.data_ptr(), info.data_ptr(), _stream(dev)),
+                                                       crop.data_ptr(), K_crop.data_ptr(), info.data_ptr(), stream_handle(dev)),
                               "det_crop_resize")
         return crop, K_crop, info
 

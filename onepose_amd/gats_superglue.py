@@ -14,13 +14,13 @@ no PyTorch / CPU fallback: tensors that are not on a ROCm device raise.
 """
 from __future__ import annotations
 
-import collections
 import ctypes
 
 import torch
 import torch.nn as nn
 
 from . import _native
+from ._binding import PackedWeights, WorkspaceCache, on_device, stream_handle
 
 D = 256
 NUM_HEADS = 4
@@ -119,21 +119,19 @@ class KeypointEncoder(nn.Module):
             nbytes = lib.gatsspg_kenc_scratch_bytes(b, n)
             scratch = torch.empty(nbytes, device=kpts.device, dtype=torch.uint8)
             _native.check(lib.gatsspg_keypoint_encoder(ctypes.byref(kw), kpts.data_ptr(), scores.data_ptr(), b, n,
-                                                       out.data_ptr(), scratch.data_ptr(), nbytes, _stream(kpts.device)),
+                                                       out.data_ptr(), scratch.data_ptr(), nbytes, stream_handle(kpts.device)),
                           "gatsspg_keypoint_encoder")
         return out
 
 
+_NO_CPU = ("onepose_amd.GATsSuperGlue runs only on a ROCm GPU (tensor '{}' is on {}); "
+           "there is no CPU fallback -- move the module and its inputs to the GPU")
+
+
 def _require_gpu(t, name):
     if not t.is_cuda:
-        raise RuntimeError(
-            f"onepose_amd.GATsSuperGlue runs only on a ROCm GPU (tensor '{name}' is on {t.device}); "
-            "there is no CPU fallback -- move the module and its inputs to the GPU")
+        raise RuntimeError(_NO_CPU.format(name, t.device))
     return t
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class Database:
@@ -153,7 +151,7 @@ class Database:
             raise ValueError(f"database cache was built for b={self.b} n2={self.n2} num_leaf={self.num_leaf} on "
                              f"{self.cache.device}; got b={b} n2={n2} num_leaf={num_leaf} on {device}")
         engine.packed_weights(device)
-        if (engine._packed_key, engine.flags()) != self.weights_key:
+        if (engine._packed.key, engine.flags()) != self.weights_key:
             raise ValueError("database cache was built with different weights / flags / precision; call prepare_database again")
         cur = torch.cuda.current_stream(device)
         if cur.cuda_stream != self.stream:
@@ -163,55 +161,24 @@ class Database:
 # --------------------------------------------------------------------------------------------------
 # the engine: packed weights + workspace + stage calls (also used by the per-kernel parity tests)
 # --------------------------------------------------------------------------------------------------
-def _on_device(fn):
-    """Run an engine method with the CURRENT HIP device set to the device of its first tensor argument / `dims`: the
-    C ABI takes a stream handle but launches (and sets kernel attributes) on the current device, so
-    ``model.to('cuda:1')(inputs)`` must not depend on the caller having called ``torch.cuda.set_device(1)``."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(self, *args, **kwargs):
-        dev = None
-        for a in args:
-            if torch.is_tensor(a):
-                dev = a.device
-                break
-            if isinstance(a, tuple) and a and isinstance(a[-1], torch.device):
-                dev = a[-1]
-                break
-        if dev is None or dev.type != "cuda":
-            return fn(self, *args, **kwargs)
-        with torch.cuda.device(dev):
-            return fn(self, *args, **kwargs)
-    return wrapper
-
-
 class GATsSPGEngine:
-    """Owns the device-side packed weights and workspaces of one module on one device.
+    """Owns the device-side packed weights (and their cross-stream ordering: _binding.PackedWeights) and the workspaces
+    (_binding.WorkspaceCache) of one module on one device."""
 
-    Workspaces are cached per (shape, device, STREAM): two forwards of one module on two streams never share scratch
-    (Z / Q / U live there).  The packed weights (and a Database cache) are written once on the stream that first asks for
-    them; an event recorded behind that write is waited on by every other stream before its first read, and a re-pack
-    (weights changed) synchronises the device before the old blob is dropped -- so concurrent use of a module from several
-    streams is safe including the first call on each stream."""
-
-    # Least-recently-used eviction, one entry at a time (round-5 judge, weak #10: the former clear-all at 8 entries dropped
-    # and re-allocated every workspace in turn for 3 database sizes x 4 streams).  32 entries cover 8 object databases on 4
-    # streams; the byte cap keeps a pathological mix (many large batched shapes) from pinning HBM.
+    # 32 entries cover 8 object databases on 4 streams
     MAX_CACHED_WORKSPACES = 32
     MAX_CACHED_WORKSPACE_BYTES = 32 << 30
 
     def __init__(self, module):
         self.module = module
         self.lib = _native.load()
-        self._packed = None
-        self._packed_key = None
-        self._packed_event = None      # recorded on the packing stream right after gatsspg_pack_weights
-        self._packed_stream = None
-        self._ws = collections.OrderedDict()
-        self._ws_bytes = 0
-        self.workspace_allocations = 0  # how many workspaces were ever allocated (tests: no re-allocation after warm-up)
+        self._packed = PackedWeights(_NO_CPU.format("parameter", "{}"))
+        self._workspaces = WorkspaceCache(self.MAX_CACHED_WORKSPACES, self.MAX_CACHED_WORKSPACE_BYTES)
         self._slots = None              # (module._parameters dict, name) of every tensor the forward reads, in pack order
+
+    @property
+    def workspace_allocations(self):
+        return self._workspaces.allocations
 
     # ---- weights ----
     def _raw_tensors(self):
@@ -238,18 +205,9 @@ class GATsSPGEngine:
         self._slots = None
 
     def packed_weights(self, device):
-        params = self._raw_tensors()
-        key = (str(device), [p._version for p in params], [p.data_ptr() for p in params])
-        if self._packed is not None and key == self._packed_key:
-            cur = torch.cuda.current_stream(device)
-            if cur.cuda_stream != self._packed_stream:     # another stream: order its reads behind the pack kernels
-                cur.wait_event(self._packed_event)
-            return self._packed
-        if self._packed is not None:
-            torch.cuda.synchronize(self._packed.device)    # re-pack: nobody may still be reading the blob that is dropped below
-        for p in params:
-            _require_gpu(p, "parameter")
-        keep = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in params]
+        return self._packed.get(device, self._raw_tensors(), self._pack)
+
+    def _pack(self, keep):
         raw = _native.RawWeights()
         it = iter(keep)
         gi = ai = 0
@@ -265,36 +223,14 @@ class GATsSPGEngine:
                 raw.mlp3_w[ai], raw.mlp3_b[ai] = next(it).data_ptr(), next(it).data_ptr()
                 ai += 1
         raw.final_w, raw.final_b = next(it).data_ptr(), next(it).data_ptr()
-        packed = torch.empty(self.lib.gatsspg_packed_weights_bytes() // 4, device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            _native.check(self.lib.gatsspg_pack_weights(ctypes.byref(raw), packed.data_ptr(), _stream(device)),
-                          "gatsspg_pack_weights")
-            self._packed_event = torch.cuda.Event()
-            self._packed_event.record(torch.cuda.current_stream(device))
-            self._packed_stream = torch.cuda.current_stream(device).cuda_stream
-        self._packed, self._packed_key = packed, key
+        packed = torch.empty(self.lib.gatsspg_packed_weights_bytes() // 4, device=keep[0].device, dtype=torch.float32)
+        _native.check(self.lib.gatsspg_pack_weights(ctypes.byref(raw), packed.data_ptr(), stream_handle(packed.device)),
+                      "gatsspg_pack_weights")
         return packed
 
-    # ---- workspace ----
     def workspace(self, b, n1, n2, num_leaf, device):
-        key = (b, n1, n2, num_leaf, str(device), torch.cuda.current_stream(device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is not None:
-            self._ws.move_to_end(key)
-            return ws
-        nbytes = self.lib.gatsspg_workspace_bytes(b, n1, n2, num_leaf)
-        if nbytes == 0:
-            raise _native.NativeError("gatsspg_workspace_bytes: " + self.lib.gatsspg_last_error().decode())
-        # evict the least recently used entries, one at a time (the caching allocator keeps a dropped buffer alive until the
-        # stream it was used on is done with it: record_stream is not needed for a buffer that only ever saw its own stream)
-        while self._ws and (len(self._ws) >= self.MAX_CACHED_WORKSPACES or self._ws_bytes + nbytes > self.MAX_CACHED_WORKSPACE_BYTES):
-            _, old = self._ws.popitem(last=False)
-            self._ws_bytes -= old.numel()
-        ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
-        self._ws[key] = ws
-        self._ws_bytes += nbytes
-        self.workspace_allocations += 1
-        return ws
+        return self._workspaces.get((b, n1, n2, num_leaf), device, self.lib.gatsspg_workspace_bytes,
+                                    lambda: "gatsspg_workspace_bytes: " + self.lib.gatsspg_last_error().decode())
 
     def flags(self):
         hp = self.module.hparams
@@ -304,7 +240,7 @@ class GATsSPGEngine:
                 | _native.PRECISIONS[self.module.precision])
 
     # ---- whole forward, all b samples ----
-    @_on_device
+    @on_device
     def forward(self, dq, d3, d2db, scale_factor, match_threshold, database=None):
         b, _, n1 = dq.shape
         n2 = d3.shape[2]
@@ -323,15 +259,15 @@ class GATsSPGEngine:
                 packed.data_ptr(), dq.data_ptr(), database.desc2d_db.data_ptr(), database.cache.data_ptr(),
                 database.cache.numel() * 4, b, n1, n2, num_leaf, self.flags(), float(scale_factor), float(match_threshold),
                 conf.data_ptr(), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(),
-                _stream(dev)), "gatsspg_forward_cached")
+                stream_handle(dev)), "gatsspg_forward_cached")
             return conf, m0, m1, s0, s1
         _native.check(self.lib.gatsspg_forward(
             packed.data_ptr(), dq.data_ptr(), d3.data_ptr(), d2db.data_ptr(), b, n1, n2, num_leaf, self.flags(),
             float(scale_factor), float(match_threshold), conf.data_ptr(), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(),
-            s1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "gatsspg_forward")
+            s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_forward")
         return conf, m0, m1, s0, s1
 
-    @_on_device
+    @on_device
     def prepare_database(self, d3, d2db):
         """Query-independent part of the first three GNN layers for a resident 3D database (amortised mode)."""
         b, _, n2 = d3.shape
@@ -343,52 +279,52 @@ class GATsSPGEngine:
         ws = self.workspace(b, 2, n2, num_leaf, dev)
         _native.check(self.lib.gatsspg_prepare_database(
             packed.data_ptr(), d3.data_ptr(), d2db.data_ptr(), b, n2, num_leaf, self.flags(), cache.data_ptr(), nbytes,
-            ws.data_ptr(), ws.numel(), _stream(dev)), "gatsspg_prepare_database")
-        return Database(cache, d3, d2db, b, n2, num_leaf, (self._packed_key, self.flags()))
+            ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_prepare_database")
+        return Database(cache, d3, d2db, b, n2, num_leaf, (self._packed.key, self.flags()))
 
     # ---- stages (parity tests) ----
-    @_on_device
+    @on_device
     def load_state(self, dq, d3, num_leaf):
         b, _, n1 = dq.shape
         n2 = d3.shape[2]
         ws = self.workspace(b, n1, n2, num_leaf, dq.device)
         _native.check(self.lib.gatsspg_load_state(dq.data_ptr(), d3.data_ptr(), b, n1, n2, num_leaf, ws.data_ptr(),
-                                                  ws.numel(), _stream(dq.device)), "gatsspg_load_state")
+                                                  ws.numel(), stream_handle(dq.device)), "gatsspg_load_state")
         return (b, n1, n2, num_leaf, dq.device)
 
-    @_on_device
+    @on_device
     def store_state(self, dims, which=0):
         b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
         o2 = torch.empty(b, D, n1, device=dev, dtype=torch.float32)
         o3 = torch.empty(b, D, n2, device=dev, dtype=torch.float32)
         _native.check(self.lib.gatsspg_store_state(which, o2.data_ptr(), o3.data_ptr(), b, n1, n2, num_leaf,
-                                                   ws.data_ptr(), ws.numel(), _stream(dev)), "gatsspg_store_state")
+                                                   ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_store_state")
         return o2, o3
 
-    @_on_device
+    @on_device
     def gats_layer(self, dims, layer, d2db, flags=None):
         b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
         _native.check(self.lib.gatsspg_gats_layer(self.packed_weights(dev).data_ptr(), layer, d2db.data_ptr(), b, n1, n2,
                                                   num_leaf, self.flags() if flags is None else flags, ws.data_ptr(),
-                                                  ws.numel(), _stream(dev)), "gatsspg_gats_layer")
+                                                  ws.numel(), stream_handle(dev)), "gatsspg_gats_layer")
 
-    @_on_device
+    @on_device
     def attn_layer(self, dims, layer, kind):
         b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
         _native.check(self.lib.gatsspg_attn_layer(self.packed_weights(dev).data_ptr(), layer, kind, b, n1, n2, num_leaf,
-                                                  self.flags(), ws.data_ptr(), ws.numel(), _stream(dev)), "gatsspg_attn_layer")
+                                                  self.flags(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_attn_layer")
 
-    @_on_device
+    @on_device
     def final_proj_norm(self, dims):
         b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
         _native.check(self.lib.gatsspg_final_proj_norm(self.packed_weights(dev).data_ptr(), b, n1, n2, num_leaf,
-                                                       ws.data_ptr(), ws.numel(), _stream(dev)), "gatsspg_final_proj_norm")
+                                                       ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_final_proj_norm")
 
-    @_on_device
+    @on_device
     def score_match(self, dims, scale_factor, match_threshold):
         b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
@@ -399,7 +335,7 @@ class GATsSPGEngine:
         s1 = torch.empty(b, n2, device=dev, dtype=torch.float32)
         _native.check(self.lib.gatsspg_score_dual_softmax_match(
             b, n1, n2, num_leaf, float(scale_factor), float(match_threshold), conf.data_ptr(), m0.data_ptr(),
-            m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+            m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
             "gatsspg_score_dual_softmax_match")
         return conf, m0, m1, s0, s1
 

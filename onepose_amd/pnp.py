@@ -8,25 +8,14 @@ The solver is the HIP library behind include/pnp.h; there is no cv2 / CPU fallba
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _native_pnp
-from ._native import NativeError  # noqa: F401
+from ._binding import NativeError, k_array as _k_array, stream_handle  # noqa: F401
 
 REPROJ_ERROR = 5.0        # eval_utils.py:30
 ITERATIONS = 10000        # eval_utils.py:31
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _k_array(K):
-    k = np.ascontiguousarray(np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float64)).reshape(9)
-    return (ctypes.c_double * 9)(*k.tolist())
 
 
 @torch.no_grad()
@@ -48,7 +37,7 @@ def ransac_pnp_device(K, pts_2d, pts_3d, scale=1.0, reproj_error=REPROJ_ERROR, i
     with torch.cuda.device(dev):   # the C ABI launches on the current device
         _native_pnp.check(lib.pnp_ransac_epnp(p3.data_ptr(), p2.data_ptr(), _k_array(K), float(scale), n, float(reproj_error),
                                               int(iterations), int(seed), pose.data_ptr(), mask.data_ptr(), info.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), _stream(dev)), "pnp_ransac_epnp")
+                                              ws.data_ptr(), ws.numel(), stream_handle(dev)), "pnp_ransac_epnp")
     return pose, mask[:n], info
 
 
@@ -71,7 +60,7 @@ def ransac_pnp_from_matches(K, kpts2d, kpts3d, matches0, scale=1.0, reproj_error
     with torch.cuda.device(dev):
         _native_pnp.check(lib.pnp_ransac_epnp_matches(k2.data_ptr(), k3.data_ptr(), m0.data_ptr(), n1, _k_array(K), float(scale),
                                                       float(reproj_error), int(iterations), int(seed), pose.data_ptr(), mask.data_ptr(),
-                                                      info.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "pnp_ransac_epnp_matches")
+                                                      info.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "pnp_ransac_epnp_matches")
     return pose, mask, info
 
 
@@ -102,7 +91,7 @@ def epnp(K, pts_2d, pts_3d, scale=1.0):
     lib = _native_pnp.load()
     with torch.cuda.device(p2.device):
         _native_pnp.check(lib.pnp_epnp(p3.data_ptr(), p2.data_ptr(), _k_array(K), float(scale), p2.shape[0], pose.data_ptr(), None, 0,
-                                       _stream(p2.device)), "pnp_epnp")
+                                       stream_handle(p2.device)), "pnp_epnp")
     return pose
 
 

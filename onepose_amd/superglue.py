@@ -15,8 +15,7 @@ import torch
 from torch import nn
 
 from . import _native_sg
-from ._native import NativeError
-from .superpoint import _on_device, _stream
+from ._binding import PackedWeights, WorkspaceCache, on_device, stream_handle
 
 D = 256
 HEADS = 4
@@ -76,11 +75,9 @@ class SuperGlueEngine:
     def __init__(self, module):
         self.module = module
         self.lib = _native_sg.load()
-        self._packed = None
-        self._packed_key = None
-        self._packed_event = None
-        self._packed_stream = None
-        self._ws = {}
+        self._packed = PackedWeights("onepose_amd.SuperGlue runs only on a ROCm GPU (a parameter is on {}); "
+                                     "there is no CPU fallback -- move the module to the GPU")
+        self._workspaces = WorkspaceCache(6)
 
     def _raw(self):
         """(module, name) of every float tensor of the state_dict in its order, read through getattr on every call."""
@@ -88,43 +85,18 @@ class SuperGlueEngine:
         return [getattr(sub, name) for sub, name in m._raw_slots]
 
     def packed_weights(self, device):
-        raw = self._raw()
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in raw)
-        if self._packed is not None and key == self._packed_key:
-            cur = torch.cuda.current_stream(device)
-            if cur.cuda_stream != self._packed_stream:
-                cur.wait_event(self._packed_event)
-            return self._packed
-        if self._packed is not None:
-            torch.cuda.synchronize(self._packed.device)    # nobody may still read the blob dropped below
-        for p in raw:
-            if not p.is_cuda:
-                raise RuntimeError(f"onepose_amd.SuperGlue runs only on a ROCm GPU (a parameter is on {p.device}); "
-                                   "there is no CPU fallback -- move the module to the GPU")
-        keep = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in raw]
+        return self._packed.get(device, self._raw(), self._pack)
+
+    def _pack(self, keep):
         n_layers = self.module.n_layers
         ptrs = (ctypes.c_void_p * len(keep))(*[k.data_ptr() for k in keep])
-        packed = torch.empty(self.lib.sg_packed_weights_bytes(n_layers) // 4, device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            _native_sg.check(self.lib.sg_pack_weights(ptrs, n_layers, packed.data_ptr(), _stream(device)), "sg_pack_weights")
-            self._packed_event = torch.cuda.Event()
-            self._packed_event.record(torch.cuda.current_stream(device))
-            self._packed_stream = torch.cuda.current_stream(device).cuda_stream
-        self._packed, self._packed_key = packed, key
+        packed = torch.empty(self.lib.sg_packed_weights_bytes(n_layers) // 4, device=keep[0].device, dtype=torch.float32)
+        _native_sg.check(self.lib.sg_pack_weights(ptrs, n_layers, packed.data_ptr(), stream_handle(packed.device)), "sg_pack_weights")
         return packed
 
     def workspace(self, b, n0, n1, device):
-        key = (b, n0, n1, str(device), torch.cuda.current_stream(device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = self.lib.sg_workspace_bytes(b, n0, n1)
-            if nbytes == 0:
-                raise NativeError(f"sg_workspace_bytes({b}, {n0}, {n1}) refused the shape")
-            if len(self._ws) >= 6:
-                self._ws.clear()
-            ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
-            self._ws[key] = ws
-        return ws
+        return self._workspaces.get((b, n0, n1), device, self.lib.sg_workspace_bytes,
+                                    lambda: f"sg_workspace_bytes({b}, {n0}, {n1}) refused the shape")
 
     @staticmethod
     def outputs(b, n0, n1, device):
@@ -132,7 +104,7 @@ class SuperGlueEngine:
         return (torch.empty(b, n0, device=device, dtype=torch.int64), torch.empty(b, n1, device=device, dtype=torch.int64),
                 torch.empty(b, n0, device=device, dtype=torch.float32), torch.empty(b, n1, device=device, dtype=torch.float32))
 
-    @_on_device
+    @on_device
     def forward(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1, out=None, z_out=None):
         """kpts [b,n,2], scores [b,n], desc [b,256,n] on one GPU; hw = (H, W) of each image.  Returns the four outputs."""
         dev = kpts0.device
@@ -151,11 +123,11 @@ class SuperGlueEngine:
             self.packed_weights(dev).data_ptr(), self.module.n_layers, kinds, int(cfg["sinkhorn_iterations"]),
             float(cfg["match_threshold"]), k0.data_ptr(), s0.data_ptr(), d0.data_ptr(), k1.data_ptr(), s1.data_ptr(), d1.data_ptr(),
             b, n0, n1, int(hw0[0]), int(hw0[1]), int(hw1[0]), int(hw1[1]), m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(),
-            ms1.data_ptr(), z_out.data_ptr() if z_out is not None else None, ws.data_ptr(), ws.numel(), _stream(dev)), "sg_forward")
+            ms1.data_ptr(), z_out.data_ptr() if z_out is not None else None, ws.data_ptr(), ws.numel(), stream_handle(dev)), "sg_forward")
         return m0, m1, ms0, ms1
 
     # ---- stages (tests) ----
-    @_on_device
+    @on_device
     def keypoint_encode(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1):
         dev = kpts0.device
         t = [_check(x, "input", dev) for x in (kpts0, scores0, desc0, kpts1, scores1, desc1)]
@@ -164,11 +136,11 @@ class SuperGlueEngine:
         o0, o1 = torch.empty_like(t[2]), torch.empty_like(t[5])
         _native_sg.check(self.lib.sg_keypoint_encode(
             self.packed_weights(dev).data_ptr(), self.module.n_layers, *[x.data_ptr() for x in t], b, n0, n1, int(hw0[0]),
-            int(hw0[1]), int(hw1[0]), int(hw1[1]), o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+            int(hw0[1]), int(hw1[0]), int(hw1[1]), o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
             "sg_keypoint_encode")
         return o0, o1
 
-    @_on_device
+    @on_device
     def layer(self, index, desc0, desc1):
         dev = desc0.device
         d0, d1 = _check(desc0, "desc0", dev), _check(desc1, "desc1", dev)
@@ -177,10 +149,10 @@ class SuperGlueEngine:
         o0, o1 = torch.empty_like(d0), torch.empty_like(d1)
         _native_sg.check(self.lib.sg_layer(
             self.packed_weights(dev).data_ptr(), self.module.n_layers, index, self.module.layer_kinds[index], d0.data_ptr(),
-            d1.data_ptr(), b, n0, n1, o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "sg_layer")
+            d1.data_ptr(), b, n0, n1, o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "sg_layer")
         return o0, o1
 
-    @_on_device
+    @on_device
     def attention(self, q, kv):
         """Softmax attention of the layers' kernel on head-contiguous q [b,256,N] and kv [b,512,M] (k rows, then v rows);
         returns [b,256,N]: per head h, out[h*64+d] = sum_m softmax_m(q_h . k_h[:, m] / 8) v[h*64+d, m]."""
@@ -190,10 +162,10 @@ class SuperGlueEngine:
             raise ValueError("q must be [b,256,N] and kv [b,512,M] with one b")
         b, n, m = qq.shape[0], qq.shape[2], kk.shape[2]
         out = torch.empty_like(qq)
-        _native_sg.check(self.lib.sg_attention(qq.data_ptr(), kk.data_ptr(), b, n, m, out.data_ptr(), _stream(dev)), "sg_attention")
+        _native_sg.check(self.lib.sg_attention(qq.data_ptr(), kk.data_ptr(), b, n, m, out.data_ptr(), stream_handle(dev)), "sg_attention")
         return out
 
-    @_on_device
+    @on_device
     def sinkhorn(self, scores, bin_score, iters):
         dev = scores.device
         sc = _check(scores, "scores", dev)
@@ -202,10 +174,10 @@ class SuperGlueEngine:
         ws = self.workspace(b, n0, n1, dev)
         z = torch.empty(b, n0 + 1, n1 + 1, device=dev, dtype=torch.float32)
         _native_sg.check(self.lib.sg_sinkhorn(sc.data_ptr(), alpha.data_ptr(), b, n0, n1, int(iters), z.data_ptr(), ws.data_ptr(),
-                                              ws.numel(), _stream(dev)), "sg_sinkhorn")
+                                              ws.numel(), stream_handle(dev)), "sg_sinkhorn")
         return z
 
-    @_on_device
+    @on_device
     def match_tail(self, z, match_threshold):
         dev = z.device
         zz = _check(z, "z", dev)
@@ -213,7 +185,7 @@ class SuperGlueEngine:
         ws = self.workspace(b, n0, n1, dev)
         m0, m1, s0, s1 = self.outputs(b, n0, n1, dev)
         _native_sg.check(self.lib.sg_match_tail(zz.data_ptr(), b, n0, n1, float(match_threshold), m0.data_ptr(), m1.data_ptr(),
-                                                s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                                                s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
                          "sg_match_tail")
         return m0, m1, s0, s1
 

@@ -16,32 +16,13 @@ import torch
 from torch import nn
 
 from . import _native_spp
-from ._native import NativeError
+from ._binding import PackedWeights, WorkspaceCache, on_device, stream_handle
 
 LAYERS = (  # (name, out, in, k) -- reference :115-133
     ("conv1a", 64, 1, 3), ("conv1b", 64, 64, 3), ("conv2a", 64, 64, 3), ("conv2b", 64, 64, 3),
     ("conv3a", 128, 64, 3), ("conv3b", 128, 128, 3), ("conv4a", 128, 128, 3), ("conv4b", 128, 128, 3),
     ("convPa", 256, 128, 3), ("convPb", 65, 256, 1), ("convDa", 256, 128, 3), ("convDb", 256, 256, 1),
 )
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _on_device(fn):
-    """Run an engine method with the CURRENT HIP device set to the device of its first tensor argument (the C ABI takes a
-    stream handle but launches on the current device)."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(self, *args, **kwargs):
-        dev = next((a.device for a in args if torch.is_tensor(a)), None)
-        if dev is None or dev.type != "cuda":
-            return fn(self, *args, **kwargs)
-        with torch.cuda.device(dev):
-            return fn(self, *args, **kwargs)
-    return wrapper
 
 
 class SuperPointEngine:
@@ -51,64 +32,35 @@ class SuperPointEngine:
     def __init__(self, module):
         self.module = module
         self.lib = _native_spp.load()
-        self._packed = None
-        self._packed_key = None
-        self._packed_event = None      # recorded on the packing stream right after spp_pack_weights
-        self._packed_stream = None
-        self._ws = {}
+        self._packed = PackedWeights("onepose_amd.SuperPoint runs only on a ROCm GPU (a parameter is on {}); "
+                                     "there is no CPU fallback -- move the module to the GPU")
+        self._workspaces = WorkspaceCache(6)
 
     def _params(self):
         m = self.module
-        return [getattr(m, n).weight for n, *_ in LAYERS], [getattr(m, n).bias for n, *_ in LAYERS]
+        return [getattr(m, n).weight for n, *_ in LAYERS] + [getattr(m, n).bias for n, *_ in LAYERS]
 
     def packed_weights(self, device):
-        ws, bs = self._params()
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in ws + bs)
-        if self._packed is not None and key == self._packed_key:
-            cur = torch.cuda.current_stream(device)
-            if cur.cuda_stream != self._packed_stream:     # another stream: order its reads behind the pack / split kernels
-                cur.wait_event(self._packed_event)
-            return self._packed
-        if self._packed is not None:
-            torch.cuda.synchronize(self._packed.device)    # re-pack: nobody may still be reading the blob that is dropped below
-        for p in ws + bs:
-            if not p.is_cuda:
-                raise RuntimeError(f"onepose_amd.SuperPoint runs only on a ROCm GPU (a parameter is on {p.device}); "
-                                   "there is no CPU fallback -- move the module to the GPU")
-        keep_w = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in ws]
-        keep_b = [p.detach().to(device=device, dtype=torch.float32).contiguous() for p in bs]
+        return self._packed.get(device, self._params(), self._pack)
+
+    def _pack(self, keep):
         raw = _native_spp.RawWeights()
         for i in range(_native_spp.NUM_LAYERS):
-            raw.weight[i], raw.bias[i] = keep_w[i].data_ptr(), keep_b[i].data_ptr()
-        packed = torch.empty(self.lib.spp_packed_weights_bytes() // 4, device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            _native_spp.check(self.lib.spp_pack_weights(ctypes.byref(raw), packed.data_ptr(), _stream(device)), "spp_pack_weights")
-            self._packed_event = torch.cuda.Event()
-            self._packed_event.record(torch.cuda.current_stream(device))
-            self._packed_stream = torch.cuda.current_stream(device).cuda_stream
-        # keep_* may be released here: the caching allocator is stream-ordered and the packing kernels were
-        # enqueued on this stream
-        self._packed, self._packed_key = packed, key
+            raw.weight[i], raw.bias[i] = keep[i].data_ptr(), keep[_native_spp.NUM_LAYERS + i].data_ptr()
+        packed = torch.empty(self.lib.spp_packed_weights_bytes() // 4, device=keep[0].device, dtype=torch.float32)
+        _native_spp.check(self.lib.spp_pack_weights(ctypes.byref(raw), packed.data_ptr(), stream_handle(packed.device)),
+                          "spp_pack_weights")
         return packed
 
     def workspace(self, b, h, w, device):
-        key = (b, h, w, str(device), torch.cuda.current_stream(device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = self.lib.spp_workspace_bytes(b, h, w)
-            if nbytes == 0:
-                raise NativeError("spp_workspace_bytes: " + self.lib.spp_last_error().decode())
-            if len(self._ws) >= 6:
-                self._ws.clear()
-            ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
-            self._ws[key] = ws
-        return ws
+        return self._workspaces.get((b, h, w), device, self.lib.spp_workspace_bytes,
+                                    lambda: "spp_workspace_bytes: " + self.lib.spp_last_error().decode())
 
     def flags(self):
         return _native_spp.PRECISIONS[self.module.precision]
 
     # ---- stages (tests) ----
-    @_on_device
+    @on_device
     def dense(self, image):
         b, _, h, w = image.shape
         dev = image.device
@@ -116,7 +68,7 @@ class SuperPointEngine:
         score = torch.empty(b, h // 8 * 8, w // 8 * 8, device=dev, dtype=torch.float32)
         dense = torch.empty(b, 256, h // 8, w // 8, device=dev, dtype=torch.float32)
         _native_spp.check(self.lib.spp_dense(self.packed_weights(dev).data_ptr(), image.data_ptr(), b, h, w, score.data_ptr(),
-                                             dense.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev), self.flags()), "spp_dense")
+                                             dense.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev), self.flags()), "spp_dense")
         return score, dense
 
     def _outputs(self, b, capacity, dev):
@@ -132,7 +84,7 @@ class SuperPointEngine:
         # -1 = keep everything: NMS survivors are more than `radius` apart (plateaus aside); retried at H*W on overflow
         return mk if mk >= 0 else max(1024, (h * w) // ((cfg["nms_radius"] + 1) ** 2))
 
-    @_on_device
+    @on_device
     def detect(self, score, dense, cfg, align_corners, capacity=None, return_nms=False):
         b, h, w = score.shape
         dev = score.device
@@ -143,10 +95,10 @@ class SuperPointEngine:
         _native_spp.check(self.lib.spp_detect(
             score.data_ptr(), dense.data_ptr(), b, h, w, cfg["nms_radius"], cfg["keypoint_threshold"], cfg["max_keypoints"],
             cfg["remove_borders"], int(align_corners), cap, kp.data_ptr(), sc.data_ptr(), de.data_ptr(), cnt.data_ptr(),
-            nms.data_ptr() if return_nms else None, ws.data_ptr(), ws.numel(), _stream(dev)), "spp_detect")
+            nms.data_ptr() if return_nms else None, ws.data_ptr(), ws.numel(), stream_handle(dev)), "spp_detect")
         return kp, sc, de, cnt, nms
 
-    @_on_device
+    @on_device
     def forward(self, image, cfg, align_corners, capacity=None):
         b, _, h, w = image.shape
         dev = image.device
@@ -156,7 +108,7 @@ class SuperPointEngine:
         _native_spp.check(self.lib.spp_forward(
             self.packed_weights(dev).data_ptr(), image.data_ptr(), b, h, w, cfg["nms_radius"], cfg["keypoint_threshold"],
             cfg["max_keypoints"], cfg["remove_borders"], int(align_corners), cap, kp.data_ptr(), sc.data_ptr(), de.data_ptr(),
-            cnt.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev), self.flags()), "spp_forward")
+            cnt.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev), self.flags()), "spp_forward")
         return kp, sc, de, cnt
 
 

@@ -11,6 +11,7 @@ import torch
 import det_cases as dc
 import detector_oracle as do
 from onepose_amd import _native_det
+from onepose_amd._binding import stream_handle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,7 +23,7 @@ def lib():
 
 
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
+    return stream_handle(torch.device(DEV))
 
 
 def gpu(a):

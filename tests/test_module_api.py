@@ -139,46 +139,66 @@ def test_import_has_no_process_wide_side_effect():
     assert "OPTIN 8 8" in out.stdout, out.stdout
 
 
-def test_workspace_cache_is_lru():
+class _FakeTensor:
+    def __init__(self, n):
+        self.n = n
+
+    def numel(self):
+        return self.n
+
+
+def _check_lru(monkeypatch, ws, cache, cap):
+    """The LRU contract of _binding.WorkspaceCache, driven through ``ws(n, stream)`` (a workspace of 1000 * n bytes on ``stream``)
+    with a stand-in allocator: ``cap`` entries at most, one eviction per miss at the cap."""
+    import torch
+    stream = [0]
+    monkeypatch.setattr(torch, "empty", lambda n, **kw: _FakeTensor(n))
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: type("S", (), {"cuda_stream": stream[0]})())
+
+    def get(n, s):
+        stream[0] = s
+        return ws(n)
+    first = [get(10 * (i + 1), 0) for i in range(cap)]
+    a, b = first[0], first[1]
+    assert cache.allocations == cap
+    assert get(10, 0) is a                      # hit: becomes most recent
+    e = get(10 * (cap + 1), 0)                  # evicts the least recent = n 20, nothing else
+    assert cache.allocations == cap + 1 and len(cache.entries) == cap
+    assert get(10, 0) is a and all(get(10 * (i + 1), 0) is first[i] for i in range(2, cap)) and get(10 * (cap + 1), 0) is e
+    assert cache.allocations == cap + 1
+    assert get(20, 0) is not b and cache.allocations == cap + 2
+    assert get(10, 1) is not a                  # another stream never shares scratch
+    cache.max_bytes = 60000                     # byte cap: evict until the new buffer fits
+    get(45, 0)
+    assert cache.bytes <= 60000 + 45000
+
+
+def test_workspace_cache_is_lru(monkeypatch):
     """Round-5 judge, weak #10: eviction drops the least recently used workspace, one at a time (not everything).  The cache policy is
     host logic: exercised here with a stand-in allocator (the GPU test cycles real shapes and streams)."""
-    import collections
+    from onepose_amd._binding import WorkspaceCache
     from onepose_amd.gats_superglue import GATsSPGEngine
 
     class FakeLib:
         def gatsspg_workspace_bytes(self, b, n1, n2, num_leaf):
             return 1000 * n2
 
-    class FakeTensor:
-        def __init__(self, n):
-            self.n = n
-
-        def numel(self):
-            return self.n
-
     eng = GATsSPGEngine.__new__(GATsSPGEngine)
-    eng.lib, eng._ws, eng._ws_bytes, eng.workspace_allocations = FakeLib(), collections.OrderedDict(), 0, 0
-    eng.MAX_CACHED_WORKSPACES = 4
-    stream = [0]
-    import onepose_amd.gats_superglue as gs
-    real_empty, real_cur = gs.torch.empty, gs.torch.cuda.current_stream
-    gs.torch.empty = lambda n, **kw: FakeTensor(n)
-    gs.torch.cuda.current_stream = lambda dev=None: type("S", (), {"cuda_stream": stream[0]})()
-    try:
-        def ws(n2, s):
-            stream[0] = s
-            return eng.workspace(1, 100, n2, 8, "cuda:0")
-        a = ws(10, 0); b = ws(20, 0); c = ws(30, 0); d = ws(40, 0)
-        assert eng.workspace_allocations == 4
-        assert ws(10, 0) is a                       # hit: becomes most recent
-        e = ws(50, 0)                               # evicts the least recent = n2 20, nothing else
-        assert eng.workspace_allocations == 5 and len(eng._ws) == 4
-        assert ws(10, 0) is a and ws(30, 0) is c and ws(40, 0) is d and ws(50, 0) is e
-        assert eng.workspace_allocations == 5
-        assert ws(20, 0) is not b and eng.workspace_allocations == 6
-        assert ws(10, 1) is not a                   # another stream never shares scratch
-        eng.MAX_CACHED_WORKSPACE_BYTES = 60000      # byte cap: evict until the new buffer fits
-        ws(45, 0)
-        assert eng._ws_bytes <= 60000 + 45000
-    finally:
-        gs.torch.empty, gs.torch.cuda.current_stream = real_empty, real_cur
+    eng.lib, eng._workspaces = FakeLib(), WorkspaceCache(4, GATsSPGEngine.MAX_CACHED_WORKSPACE_BYTES)
+    _check_lru(monkeypatch, lambda n2: eng.workspace(1, 100, n2, 8, "cuda:0"), eng._workspaces, 4)
+    assert eng.workspace_allocations == eng._workspaces.allocations == 8
+
+
+def test_extractor_workspace_cache_evicts_one_of_six(monkeypatch):
+    """The extractor, the 2D-2D matcher and the detector keep at most 6 workspaces; reaching the cap drops the least recently
+    used one, not all six (driven through SuperPointEngine.workspace)."""
+    from onepose_amd._binding import WorkspaceCache
+    from onepose_amd.superpoint import SuperPointEngine
+
+    class FakeLib:
+        def spp_workspace_bytes(self, b, h, w):
+            return 1000 * w
+
+    eng = SuperPointEngine.__new__(SuperPointEngine)
+    eng.lib, eng._workspaces = FakeLib(), WorkspaceCache(6)
+    _check_lru(monkeypatch, lambda w: eng.workspace(1, 480, w, "cuda:0"), eng._workspaces, 6)
