@@ -36,7 +36,8 @@ class Library:
 # files only) does not see them.
 LIBRARIES = (
     Library("gatsspg", ["gatsspg_gemm_kernels.hip", "gatsspg_split_kernels.hip", "gatsspg_stream_kernels.hip", "gatsspg_capi.hip"],
-            ["gatsspg_common.h", "gatsspg_launch.h", "gemm_f32_mfma.h", "gemm_split_glds.h", "capi_common.h", _include("gatsspg.h")],
+            ["gatsspg_common.h", "gatsspg_launch.h", "gatsspg_epilogue.h", "gemm_f32_mfma.h", "gemm_split_glds.h", "capi_common.h",
+             _include("gatsspg.h")],
             tuning=True),
     Library("spp", ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"],
             ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", _include("superpoint.h")], tuning=True),

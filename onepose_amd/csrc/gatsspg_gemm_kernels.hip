@@ -2,7 +2,7 @@
 // linear-attention KV reduction / apply, and the N_2D x N_3D score contraction.
 // Reference maths: GATs_SuperGlue.py:69-128 (linear_attention, MultiHeadedAttention,
 // AttentionPropagation, MLP) and :209-218 (final_proj, normalize, score einsum, exp of the softmax).
-#include "gemm_f32_mfma.h"
+#include "gatsspg_epilogue.h"
 #include "gatsspg_launch.h"
 
 namespace gatsspg {
@@ -10,8 +10,9 @@ namespace gatsspg {
 // dynamic LDS of a main loop (operand stages; the epilogues re-use it)
 template <class T, int PREC = 0>
 constexpr size_t smem_bytes() {
+    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6: the fp16 modes run on the kernels of gatsspg_split_kernels.hip");
     size_t b = sizeof(float) * T::SMEM_FLOATS;
-    if constexpr (PREC == 1 || PREC >= 3) {
+    if constexpr (PREC == 1) {
         if (Bf3Layout<T>::SMEM_BYTES > b) b = Bf3Layout<T>::SMEM_BYTES;
     }
     if constexpr (PREC == 2) {
@@ -34,7 +35,7 @@ constexpr int smem_floats_mainloop() { return (int)(smem_bytes<T, PREC>() / size
 using QkvTileW8 = GemmTile<128, QKV_BN, 4, 2, false>;     // both arithmetics: 8 waves, one 32x32 MFMA tile each (fp32: 38.0 vs 40.1 us on 4 waves)
 // (split-bf16 on 4 waves, 64x32 per wave: 31.2 vs 24.6 us; removed with the QKV_BTILE knob)
 
-// PREC = 0: exact fp32 MFMA.  PREC = 1: split-bf16 main loop on the pre-split weight planes Whi / Wlo.
+// PREC = 0: exact fp32 MFMA.  PREC = 1 / 2: three- / six-term split-bf16 main loop on the pre-split weight planes Whi / Wlo (/ Wl2).
 // (forcing 80 VGPRs so that three 8-wave workgroups fit a CU -- the 756 tiles of the headline shape then fit 768 slots in one
 // round -- was measured: kernel -2 %, frames/s in flight unchanged; not kept)
 // DS: the Q tiles leave straight from the accumulators (store_tile_regs) instead of through an LDS staging tile
@@ -46,8 +47,8 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel
                                                             const unsigned short* __restrict__ Wl2,
                                                             const float* __restrict__ Z, float* __restrict__ Qbuf,
                                                             float* __restrict__ kvpart, ColLayout L) {
+    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6 (the fp16 modes: qkv_kv_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if constexpr (PREC >= 3) fp16_saturate_mode();
     int rt, ct;
     if (!xcd_tile_map(6, active_tiles(L), rt, ct)) return;
     ct = global_tile(L, ct);
@@ -56,37 +57,26 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel
     const float* A = Wqkv + (size_t)rt * 128 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
-    // this lane's 16 bias values per MFMA tile (rows 8k + 4 half + 0..3 of the tile: four 16-byte loads), requested BEFORE the
-    // main loop.  (Read in the epilogue next to elu's branch they became 16 dependent load -> wait -> write rounds per lane.)
+    // this lane's 16 bias values per MFMA tile, requested BEFORE the main loop (load_bias16, gatsspg_epilogue.h)
     // (the six-term loop has no 16 registers to park it in and fetches it after the loop)
     float bias[T::TM][16];
-    auto load_bias = [&]() {
-#pragma unroll
-        for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const vf4 b4 = ldg4(bqkv + rt * 128 + (wm * T::TM + tm) * 32 + 8 * k + 4 * half);
-                bias[tm][4 * k + 0] = b4[0]; bias[tm][4 * k + 1] = b4[1]; bias[tm][4 * k + 2] = b4[2]; bias[tm][4 * k + 3] = b4[3];
-            }
-    };
-    // BT: the bias through an LDS table behind the operand buffers instead (read_bias16, gemm_f32_mfma.h)
+    // BT: the bias through an LDS table behind the operand buffers instead (read_bias16)
     float* btab = smem + smem_floats_mainloop<T, PREC>();
     if constexpr (BT) {
         static_assert(T::BM == 128 && T::KS == 1, "half a piece of bias values, one wave group");
         if ((tid >> 6) == 0 && lane < 32) glds16(bqkv + rt * 128 + 4 * lane, btab);
     } else if constexpr (PREC != 2) {
-        load_bias();
+        load_bias16<T>(bqkv + rt * 128, wm, half, bias);
     }
     f32x16 acc[T::TM][T::TN];
     zero_acc(acc);
-    if constexpr (PREC == 1 || PREC >= 3) {   // PREC >= 3: the planes hold fp16 terms, the products run on the f16 MFMA (4: four products)
+    if constexpr (PREC == 1) {
         // weight planes are slab-major ([K/32][rows][32], split_weights_kernel): a 128 x 32 slab is 8 KB of consecutive bytes
         const size_t ro = (size_t)rt * 128 * BK;
         auto ah = [&](int kt) { return Whi + ro + (size_t)kt * 768 * BK; };
         auto alo = [&](int kt) { return Wlo + ro + (size_t)kt * 768 * BK; };
         auto bl = [&](int kt) { return Z + (size_t)kt * BK * ld + c0; };
-        gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), NoHooks, (PREC >= 3), (PREC == 4 ? 4 : 3)>(
-            acc, reinterpret_cast<unsigned short*>(smem), D / BK, ah, alo, BK, bl, ld);
+        gemm_mainloop_bf3<T>(acc, reinterpret_cast<unsigned short*>(smem), D / BK, ah, alo, BK, bl, ld);
     } else if constexpr (PREC == 2) {
         const size_t ro = (size_t)rt * 128 * BK;
         gemm_mainloop_bf6<T>(
@@ -96,10 +86,10 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel
     } else {
         auto al = [&](int kt) { return A + kt * BK; };
         auto bl = [&](int kt) { return Z + (size_t)kt * BK * ld + c0; };
-        gemm_mainloop<T, decltype(al), decltype(bl), 0, IdentityCol, NoHooks, QF>(acc, smem, D / BK, al, D, bl, ld);
+        gemm_mainloop<T, decltype(al), decltype(bl), IdentityCol, NoHooks, QF>(acc, smem, D / BK, al, D, bl, ld);
     }
     if constexpr (BT) read_bias16<T>(btab, wm, half, bias);
-    else if constexpr (PREC == 2) load_bias();
+    else if constexpr (PREC == 2) load_bias16<T>(bqkv + rt * 128, wm, half, bias);
 
     if (rt < 2) {
 #pragma unroll
@@ -110,7 +100,8 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel
         else store_tile_via_lds<T>(acc, smem, Qbuf + (size_t)rt * 128 * ld + c0, ld, [](int, float v) { return v; });
         return;
     }
-    // ---- K_h / V_h tile -> LDS -> KV partial ----
+    // ---- K_h / V_h tile -> LDS -> KV partial ----  (twin of the block in qkv_kv_sp_kernel: keep the two in step; gatsspg_epilogue.h says why
+    // it is not one helper)
     const int h = rt - 2;
     const TileSeg ts = tile_seg(L, c0, T::BN);
     constexpr int TS = T::BN + 4;  // LDS row stride (floats) of the [128][64] K/V tile: b128-read conflict-free
@@ -444,8 +435,8 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
                                                    const float* __restrict__ ksumT,
                                                    float* __restrict__ U, float* __restrict__ statpart, float* __restrict__ stats,
                                                    int* __restrict__ statcnt, ColLayout L, unsigned long long* trace) {
+    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp0_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if constexpr (PREC >= 3) fp16_saturate_mode();
     const unsigned long long t_entry = trace ? wall_clock64() : 0;
     const unsigned long long c_entry = trace ? clock64() : 0;
     int rt, ct;
@@ -457,24 +448,15 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
     const float* A = W0 + (size_t)rt * T::BM * 512;
     const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) % T::WAVES_MN;   // (K-split tiles: wave within its group)
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
-    // requested before the main loop (see qkv_kv_kernel); the six-term and the fp16 loops have no 16 registers to park it in
-    // (128-VGPR budget of two 8-wave workgroups per CU) and fetch it after the loop
+    // requested before the main loop (see qkv_kv_kernel); the six-term loop has no 16 registers to park it in
+    // (128-VGPR budget of two 8-wave workgroups per CU) and fetches it after the loop
     float bias[T::TM][16];
-    auto load_bias = [&]() {
-#pragma unroll
-        for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const vf4 b4 = ldg4(b0 + rt * T::BM + (wm * T::TM + tm) * 32 + 8 * k + 4 * half);
-                bias[tm][4 * k + 0] = b4[0]; bias[tm][4 * k + 1] = b4[1]; bias[tm][4 * k + 2] = b4[2]; bias[tm][4 * k + 3] = b4[3];
-            }
-    };
     float* btab = smem + smem_floats_mainloop<T, PREC>() + AttnFoldHooks::ZP_FLOATS;   // BT: bias through an LDS table (see qkv_kv_kernel)
     if constexpr (BT) {
         static_assert(T::BM == 128 && T::KS == 1, "half a piece of bias values, one wave group");
         if ((tid >> 6) == 0 && lane < 32) glds16(b0 + rt * T::BM + 4 * lane, btab);
     } else if constexpr (PREC < 2) {
-        load_bias();
+        load_bias16<T>(b0 + rt * T::BM, wm, half, bias);
     }
     f32x16 acc[T::TM][T::TN];
     zero_acc(acc);
@@ -486,13 +468,13 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
     auto bl = [&](int kt) { return (kt < 8 ? Z + (size_t)kt * BK * ld : Qbuf + (size_t)(kt - 8) * BK * ld) + c0; };
     AttnFoldHooks hooks;
     hooks.init(ksumT + (size_t)ts.seg * H * DH, smem + smem_floats_mainloop<T, PREC>(), wn);
-    if constexpr (PREC == 1 || PREC >= 3) {
+    if constexpr (PREC == 1) {
         const size_t ro = (size_t)rt * T::BM * BK;   // slab-major planes (see qkv_kv_kernel); M_t planes in the same layout
         const unsigned short* Mh = Mpl + (size_t)ts.seg * 3 * MPL_PLANE + ro;
         auto ah = [&](int kt) { return kt < 8 ? Whi + ro + (size_t)kt * 512 * BK : Mh + (size_t)(kt - 8) * 512 * BK; };
         auto alo = [&](int kt) { return kt < 8 ? Wlo + ro + (size_t)kt * 512 * BK : Mh + MPL_PLANE + (size_t)(kt - 8) * 512 * BK; };
-        gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), AttnFoldHooks, (PREC >= 3), (PREC == 4 ? 4 : 3)>(
-            acc, reinterpret_cast<unsigned short*>(smem), 512 / BK, ah, alo, BK, bl, ld, &hooks);
+        gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), AttnFoldHooks>(acc, reinterpret_cast<unsigned short*>(smem), 512 / BK, ah,
+                                                                                       alo, BK, bl, ld, &hooks);
     } else if constexpr (PREC == 2) {
         const size_t ro = (size_t)rt * T::BM * BK;
         const unsigned short* Mh = Mpl + (size_t)ts.seg * 3 * MPL_PLANE + ro;
@@ -504,13 +486,12 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
             },
             BK, bl, ld, &hooks);
     } else {
-        gemm_mainloop<T, decltype(al), decltype(bl), 0, IdentityCol, AttnFoldHooks, QF>(acc, smem, 512 / BK, al, 512, bl, ld,
-                                                                                                          IdentityCol(), &hooks);
+        gemm_mainloop<T, decltype(al), decltype(bl), IdentityCol, AttnFoldHooks, QF>(acc, smem, 512 / BK, al, 512, bl, ld, IdentityCol(), &hooks);
     }
     acc[0][0] = hooks.kept;
     ksplit_reduce<T>(acc, smem);
     if constexpr (BT) read_bias16<T>(btab, wm, half, bias);
-    else if constexpr (PREC >= 2) load_bias();
+    else if constexpr (PREC == 2) load_bias16<T>(b0 + rt * T::BM, wm, half, bias);
     const unsigned long long t_loop = trace ? wall_clock64() : 0;
     constexpr int TS = T::BN + 1;
     float* Tl = smem;  // [BM][BN + 1]
@@ -525,38 +506,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
                 Tl[row * TS + col] = acc[tm][tn][r] + bias[tm][r];
             }
     __syncthreads();
-    {   // per-row (sum, centred sum of squares) of the real columns of each 64-column tile: THREADS / BM lanes per row,
-        // each a fixed contiguous column range, combined by shuffles (fixed order).  One pass, shifted by the first
-        // column of the row (a pivot within a few std of the mean), so M2 = sum d^2 - (sum d)^2 / n does not cancel even
-        // when |mean| >> std; stat_final merges the tiles with Chan's formula.
-        constexpr int LPR = T::THREADS / T::BM;    // lanes per row
-        constexpr int LPS = LPR / TPW;             // lanes per (row, 64-column tile)
-        constexpr int CPL = MLP0_BN / LPS;         // columns per lane
-        static_assert(LPS >= 1, "at least one lane per row and 64-column tile");
-        const int row = tid / LPR, q = tid % LPR, sub = q / LPS, part = q % LPS;
-        const int valid = min(max(ts.valid - sub * MLP0_BN, 0), MLP0_BN);
-        const float pivot = Tl[row * TS + sub * MLP0_BN];
-        const float* tr = Tl + row * TS + sub * MLP0_BN + part * CPL;
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int m = 0; m < CPL; ++m) {
-            const float t = tr[m];                                           // unconditional LDS read (a guarded one becomes a
-            const float d = (part * CPL + m < valid) ? t - pivot : 0.f;      // branch + s_waitcnt per element), masked afterwards
-            s1 += d;
-            s2 += d * d;
-        }
-#pragma unroll
-        for (int o = 1; o < LPS; o <<= 1) {
-            s1 += __shfl_xor(s1, o);
-            s2 += __shfl_xor(s2, o);
-        }
-        if (part == 0) {
-            const float nv = (float)valid;
-            const size_t t64 = (size_t)ct * TPW + sub;
-            stat_partial_store(statpart + (t64 * 2 + 0) * 512 + rt * T::BM + row, nv * pivot + s1);                      // sum
-            stat_partial_store(statpart + (t64 * 2 + 1) * 512 + rt * T::BM + row, nv > 0.f ? s2 - s1 * s1 / nv : 0.f);   // M2
-        }
-    }
+    mlp0_tile_statistics<T, TS, false>(Tl, statpart, ts.valid, rt, ct);   // per-tile InstanceNorm partials (gatsspg_epilogue.h)
     // the partial stores above go first; the tile's own stores follow them and may still be in flight when the ticket is drawn
     asm volatile("" ::: "memory");
     // then the tile leaves through LDS as 16-byte stores: 16 lanes cover one 256-byte row segment
@@ -658,8 +608,8 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void mlp3_kernel(c
                                                    const unsigned short* __restrict__ Wl2,
                                                    const float* __restrict__ U, const float* __restrict__ stats,
                                                    float* __restrict__ Z, ColLayout L) {
+    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp3_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if constexpr (PREC >= 3) fp16_saturate_mode();
     int rt, ct;
     constexpr int MT = 256 / T::BM;
     constexpr int TPW = T::BN / 64;   // 64-column tiles per column tile of this kernel
@@ -692,14 +642,13 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void mlp3_kernel(c
     auto bl = [&](int kt) { return U + (size_t)kt * BK * ld + c0; };
     auto xm = [&](int kt) { return mean + kt * BK; };
     auto xr = [&](int kt) { return rstd + kt * BK; };
-    if constexpr (PREC == 1 || PREC >= 3) {
+    if constexpr (PREC == 1) {
         const size_t ro = (size_t)rt * T::BM * BK;   // slab-major planes (see qkv_kv_kernel)
         auto ah = [&](int kt) { return Whi + ro + (size_t)kt * 256 * BK; };
         auto alo = [&](int kt) { return Wlo + ro + (size_t)kt * 256 * BK; };
         auto bx1 = [](float v, float2 ms) { return fmaxf((v - ms.x) * ms.y, 0.f); };
-        gemm_mainloop_bf3_ex<T, decltype(ah), decltype(alo), decltype(bl), decltype(xm), decltype(xr), decltype(bx1), true, NoHooks,
-                             (PREC >= 3), (PREC == 4 ? 4 : 3)>(acc, reinterpret_cast<unsigned short*>(smem), 512 / BK, ah, alo, BK, bl, ld, xm,
-                                                               xr, bx1);
+        gemm_mainloop_bf3_ex<T, decltype(ah), decltype(alo), decltype(bl), decltype(xm), decltype(xr), decltype(bx1), true>(
+            acc, reinterpret_cast<unsigned short*>(smem), 512 / BK, ah, alo, BK, bl, ld, xm, xr, bx1);
     } else if constexpr (PREC == 2) {
         const size_t ro = (size_t)rt * T::BM * BK;
         auto ap = [&](int kt, int pl) { return (pl == 0 ? Whi : pl == 1 ? Wlo : Wl2) + ro + (size_t)kt * 256 * BK; };
@@ -742,13 +691,7 @@ __global__ __launch_bounds__(FinalTile::THREADS) void final_proj_norm_kernel(con
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
     float bias[T::TM][16];   // requested before the main loop
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const vf4 b4 = ldg4(bf + (wave * T::TM + tm) * 32 + 8 * k + 4 * half);
-            bias[tm][4 * k + 0] = b4[0]; bias[tm][4 * k + 1] = b4[1]; bias[tm][4 * k + 2] = b4[2]; bias[tm][4 * k + 3] = b4[3];
-        }
+    load_bias16<T>(bf, wave, half, bias);
     f32x16 acc[T::TM][T::TN];
     zero_acc(acc);
     gemm_mainloop<T>(
@@ -845,68 +788,8 @@ __global__ __launch_bounds__(T::THREADS) void score_exp_kernel(const float* __re
     gemm_mainloop<T>(
         acc, smem, D / BK, [&](int kt) { return Ap + kt * BK; }, D,
         [&](int kt) { return Bp + (size_t)kt * BK * ld; }, ld);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
-    constexpr int TS = T::BN + 1;
-    float* Tl = smem;  // [128][65]
-    float* cf = conf + (size_t)frame * L.n1 * L.n2;
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (wm * T::TM + tm) * 32 + mfma_row(r, half);
-            const int col = wn * 32 + l31;
-            const int gi = rt * T::BM + row, gj = ct * T::BN + col;
-            const float sc = acc[tm][0][r] / scale;
-            Tl[row * TS + col] = (gi < L.n1 && gj < L.n2) ? (RAW ? sc : expf(sc)) : 0.f;
-        }
-    __syncthreads();
-    // the tile leaves through LDS: 16 lanes cover one 256-byte row segment (16-byte stores when the rows of conf are
-    // 16-byte aligned, i.e. n2 % 4 == 0 and an aligned base; otherwise 4-byte stores, 64 lanes per row segment)
-    if ((L.n2 & 3) == 0 && (reinterpret_cast<uintptr_t>(cf) & 15) == 0) {
-        for (int idx = tid; idx < T::BM * (T::BN / 4); idx += T::THREADS) {
-            const int row = idx / (T::BN / 4), c4 = (idx % (T::BN / 4)) * 4;
-            const int gi = rt * T::BM + row, gj = ct * T::BN + c4;
-            if (gi < L.n1 && gj < L.n2) {
-                const float* t = Tl + row * TS + c4;
-                vf4 v = {t[0], t[1], t[2], t[3]};
-                *reinterpret_cast<vf4*>(cf + (size_t)gi * L.n2 + gj) = v;
-            }
-        }
-    } else {
-        for (int idx = tid; idx < T::BM * T::BN; idx += T::THREADS) {
-            const int row = idx / T::BN, col = idx % T::BN;
-            const int gi = rt * T::BM + row, gj = ct * T::BN + col;
-            if (gi < L.n1 && gj < L.n2) cf[(size_t)gi * L.n2 + gj] = Tl[row * TS + col];
-        }
-    }
-    if constexpr (!RAW) {
-        // row sums: THREADS / BM lanes per row; column sums: one wave per THREADS / 64-th of the rows (conflict-free
-        // column walks); fixed order throughout
-        constexpr int LPR = T::THREADS / T::BM, CPL = T::BN / LPR;
-        const int row = tid / LPR, hp = tid % LPR;
-        const float* tr = Tl + row * TS + hp * CPL;
-        float s = 0.f;
-#pragma unroll 8
-        for (int m = 0; m < CPL; ++m) s += tr[m];
-#pragma unroll
-        for (int o = 1; o < LPR; o <<= 1) s += __shfl_xor(s, o);
-        if (hp == 0 && rt * T::BM + row < L.n1p) rowpart[((size_t)frame * nct + ct) * L.n1p + rt * T::BM + row] = s;
-        constexpr int NQ = T::THREADS / T::BN, RPQ = T::BM / NQ;   // NQ row groups of RPQ rows, one thread per (group, column)
-        const int c = tid % T::BN, qp = tid / T::BN;
-        float t = 0.f;
-#pragma unroll 8
-        for (int m = 0; m < RPQ; ++m) t += Tl[(qp * RPQ + m) * TS + c];
-        __syncthreads();
-        Tl[qp * T::BN + c] = t;   // re-use the tile head for the NQ x BN part sums
-        __syncthreads();
-        if (tid < T::BN) {
-            float tot = 0.f;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) tot += Tl[q * T::BN + tid];
-            colpart[((size_t)frame * nrt + rt) * L.n2p + ct * T::BN + tid] = tot;
-        }
-    }
+    // staged tile [128][65]
+    score_epilogue<T, T::BN + 1, false, RAW, false>(acc, smem, conf, rowpart, colpart, L, frame, rt, ct, nrt, nct, 1.f, scale);
 }
 
 // =====================================================================================================
@@ -1029,21 +912,6 @@ void launch_split_weights(float* packed, unsigned short* packedb, hipStream_t s)
 // host-side launchers
 // ------------------------------------------------------------------------------------------------------
 
-// Kernels whose dynamic LDS request exceeds the 64 KiB default need the limit raised once per device.  The once-flag
-// lives in a function template instantiated per KERNEL (the kernel is a non-type template argument), so two variants
-// that merely share a signature never share it.
-template <auto Kernel>
-void allow_big_lds() {
-    static bool done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024 - 2048);
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-}
-
 // Shape thresholds between two product kernels: named defaults here, read from the environment only by a tuning build (tuning_knob).
 // fp32 qkv_kv / mlp0: launches of more than DIET_MIN_TILES 64-column tiles take the register-diet forms -- quarter fragments + bias through an
 // LDS table: mlp0 94 VGPRs (from 126), qkv_kv 80 (from 98), zero scratch, bit-identical results -- smaller launches the two-half fragment loop.
@@ -1065,8 +933,8 @@ static void launch_qkv_t(const float* Wqkv, const float* bqkv, const unsigned sh
     const int NT = active_tiles(w.L);
     allow_big_lds<qkv_kv_kernel<T, PREC, BT, DS, QF>>();
     GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_kernel<T, PREC, BT, DS, QF>), dim3(xcd_grid(6, NT)), dim3(T::THREADS), (smem_bytes<T, PREC>() + 512 * BT), s,
-                   Wqkv, bqkv, wb ? wb + (PREC >= 3 ? AttnWB::QKV_H16 : AttnWB::QKV_HI) : nullptr,
-                   wb ? wb + (PREC >= 3 ? AttnWB::QKV_L16 : AttnWB::QKV_LO) : nullptr, wb ? wb + AttnWB::QKV_LO2 : nullptr, w.Z,
+                   Wqkv, bqkv, wb ? wb + AttnWB::QKV_HI : nullptr,
+                   wb ? wb + AttnWB::QKV_LO : nullptr, wb ? wb + AttnWB::QKV_LO2 : nullptr, w.Z,
                    w.Q, w.kvpart, w.L);
 }
 
@@ -1107,7 +975,7 @@ static void launch_mlp0_t(const float* W0, const float* b0, const unsigned short
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
     GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, PREC, BT, QF, SF>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS),
                    (smem_bytes<T, PREC>() + sizeof(float) * AttnFoldHooks::ZP_FLOATS + 512 * BT), s, W0, b0,
-                   wb ? wb + (PREC >= 3 ? AttnWB::W0_H16 : AttnWB::W0_HI) : nullptr, wb ? wb + (PREC >= 3 ? AttnWB::W0_L16 : AttnWB::W0_LO) : nullptr,
+                   wb ? wb + AttnWB::W0_HI : nullptr, wb ? wb + AttnWB::W0_LO : nullptr,
                    wb ? wb + AttnWB::W0_LO2 : nullptr, w.Z, w.Q, w.Mop, w.Mpl, w.ksumT, w.U,
                    w.statpart, w.stats, nullptr, w.L, g_trace);
 }
@@ -1117,8 +985,8 @@ static void launch_mlp3_t(const float* W3, const float* b3, const unsigned short
     allow_big_lds<mlp3_kernel<T, PREC, DS>>();
     const int NT = active_tiles(w.L) / (T::BN / 64);
     GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, PREC, DS>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS),
-                   (smem_bytes<T, PREC>()), s, W3, b3, wb ? wb + (PREC >= 3 ? AttnWB::W3_H16 : AttnWB::W3_HI) : nullptr,
-                   wb ? wb + (PREC >= 3 ? AttnWB::W3_L16 : AttnWB::W3_LO) : nullptr, wb ? wb + AttnWB::W3_LO2 : nullptr, w.U,
+                   (smem_bytes<T, PREC>()), s, W3, b3, wb ? wb + AttnWB::W3_HI : nullptr,
+                   wb ? wb + AttnWB::W3_LO : nullptr, wb ? wb + AttnWB::W3_LO2 : nullptr, w.U,
                    w.stats, w.Z, w.L);
 }
 

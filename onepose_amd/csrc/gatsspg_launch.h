@@ -39,6 +39,21 @@ inline void hook_after(ProfileHook* h, int kid, hipStream_t s) {
 // (DIET_MIN_TILES, SMALL_NT3, SP_MLP0_WIDE_MIN / _MAX, SP_NST2).  Compile-time alternatives are A/B-timed as two builds (tools/ab_libs.py).
 int tuning_knob(const char* name, int dflt);
 
+// Kernels whose dynamic LDS request exceeds the 64 KiB default need the limit raised once per device.  The once-flag
+// lives in a function template instantiated per KERNEL (the kernel is a non-type template argument), so two variants
+// that merely share a signature never share it.
+template <auto Kernel>
+void allow_big_lds() {
+    static bool done[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !done[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024 - 2048);
+        if (dev >= 0 && dev < 64) done[dev] = true;
+    }
+}
+
 // gatsspg_gemm_kernels.hip
 #ifdef GATSSPG_PROFILING_BUILD
 extern unsigned long long* g_trace;  // per-workgroup timeline buffer of mlp0_kernel (nullptr = off)

@@ -1,8 +1,9 @@
 // The three big GEMMs of an attention layer on the split-16-bit main loop of gemm_split_glds.h (round 4): qkv_kv, mlp.0 (merge and
 // the linear-attention apply folded in) and mlp.3, for the arithmetics GATSSPG_FLAG_PREC_FP16X4 / _FP16X3 (always) and _BF16X3 /
-// _BF16X6.  Same maths, same buffers and the same epilogues as the fp32 kernels of gatsspg_gemm_kernels.hip
+// _BF16X6.  Same maths, same buffers and the same epilogues (gatsspg_epilogue.h) as the fp32 kernels of gatsspg_gemm_kernels.hip
 // (GATs_SuperGlue.py:69-128); what differs is how the operands reach the matrix pipe.
 #include "gemm_split_glds.h"
+#include "gatsspg_epilogue.h"
 #include "gatsspg_launch.h"
 
 namespace gatsspg {
@@ -13,17 +14,6 @@ static constexpr unsigned long long* g_trace = nullptr;   // (profiling builds: 
 #else
 #define SP_TRACE_ON(ptr) ((ptr) != nullptr)
 #endif
-
-template <auto Kernel>
-static void allow_big_lds_sp() {
-    static bool done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-}
 
 // plain hooks: no side work; the first product of the K loop starts from zero (FRESH0) or from the caller's accumulators
 template <bool FRESH0>
@@ -39,18 +29,6 @@ struct SpPlainHooks {
     __device__ __forceinline__ void in_step(f32x16 (&)[TM]) {}
 };
 
-// this lane's 16 bias values per 32-row MFMA tile (rows 8 k + 4 half + 0..3: four 16-byte loads)
-template <class T>
-__device__ __forceinline__ void load_bias16(const float* b, int row0, int wm, int half, float (&bias)[T::TM][16]) {
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const vf4 b4 = ldg4(b + row0 + (wm * T::TM + tm) * 32 + 8 * k + 4 * half);
-            bias[tm][4 * k + 0] = b4[0]; bias[tm][4 * k + 1] = b4[1]; bias[tm][4 * k + 2] = b4[2]; bias[tm][4 * k + 3] = b4[3];
-        }
-}
-
 // =====================================================================================================
 // K1  QKV projection + KV / ksum partials (qkv_kv_kernel of gatsspg_gemm_kernels.hip on the split loop).
 //     128 x 64 tile on 4 waves (64 x 32 per wave), two stages (48 KiB): three workgroups per CU, so the 756 tiles of the headline
@@ -58,23 +36,6 @@ __device__ __forceinline__ void load_bias16(const float* b, int row0, int wm, in
 // =====================================================================================================
 template <int MODE>
 using QkvSpTile = SpTile<128, 2, 2, 2, MODE>;
-
-// A plain output tile straight from the accumulators: in the 32 x 32 C layout a lane's 16 values of one product sit in ONE column
-// (lane & 31) and 16 rows, so each dword store instruction covers two rows x 32 consecutive columns = two full 128-byte lines --
-// no LDS round trip, no barrier in front of the stores (store_tile_via_lds: 32 scalar LDS writes, a barrier, 8 row reads, 8 16-byte stores).
-template <class T, class F>
-__device__ __forceinline__ void store_tile_direct(const f32x16 (&acc)[T::TM][T::TN], float* dst, int ld, F f) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
-    float* d = dst + wn * 32 + l31;
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (wm * T::TM + tm) * 32 + mfma_row(r, half);
-            d[(size_t)row * ld] = f(row, acc[tm][0][r]);
-        }
-}
 
 // fp16 modes on the slot schedule (SCHED 4); the bias through an LDS table, the Q tiles stored straight from the accumulators
 template <class T>
@@ -114,10 +75,11 @@ __global__ __launch_bounds__(T::THREADS, 3) void qkv_kv_sp_kernel(const float* _
         for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][0][r] = elu1_select(fmaf(acc[tm][0][r], inv, bias[tm][r])) + 1.f;
-        store_tile_direct<T>(acc, Qbuf + (size_t)rt * 128 * ld + c0, ld, [](int, float v) { return v; });
+        store_tile_regs<T>(acc, Qbuf + (size_t)rt * 128 * ld + c0, ld, [](int, float v) { return v; });
         return;
     }
-    // ---- K_h / V_h tile -> LDS -> KV partial (second MFMA pass, fp32: exact like the fp32 kernel's)
+    // ---- K_h / V_h tile -> LDS -> KV partial (second MFMA pass, fp32: exact like the fp32 kernel's; twin of the block in qkv_kv_kernel: keep
+    // the two in step, gatsspg_epilogue.h says why it is not one helper)
     const int h = rt - 2;
     const TileSeg ts = tile_seg(L, c0, T::BN);
     constexpr int TS = T::BN + 4;
@@ -329,42 +291,8 @@ __global__ __launch_bounds__(T::THREADS, (T::TM == 4 ? 1 : (T::WAVES == 4 && T::
     if (SP_TRACE_ON(trace)) tr.t[10] = __builtin_readcyclecounter();   // last fold + bias + tile written to LDS
     __syncthreads();
     if (SP_TRACE_ON(trace)) tr.t[11] = __builtin_readcyclecounter();
-    auto tile_statistics = [&]() {   // per-row (sum, pivot-shifted centred sum of squares) of the real columns of each 64-column tile (mlp0_kernel's form)
-        constexpr int LPR = T::THREADS / T::BM;    // lanes per row
-        constexpr int LPS = LPR / TPW;             // lanes per (row, 64-column tile)
-        constexpr int CPL = MLP0_BN / LPS;         // columns per lane
-        static_assert(LPS >= 1, "at least one lane per row and 64-column tile");
-        const int row = tid / LPR, q = tid % LPR, sub = q / LPS, part = q % LPS;
-        const int valid = min(max(ts.valid - sub * MLP0_BN, 0), MLP0_BN);
-        const float pivot = Tl[row * TS + sub * MLP0_BN];
-        const float* trow = Tl + row * TS + sub * MLP0_BN + part * CPL;
-        // the LPR lanes of a row start a multiple of 32 banks apart and rows are 4 banks apart: lane (row, q) starts its walk
-        // q + LPR * ((row >> 3) mod (4 / LPR)) columns into its range, so that the 32 lanes of a read (32 / LPR rows) cover the 32 banks once
-        static_assert(TS % 32 == 4, "walk skew of the statistics reads");
-        static_assert(CPL == 32 && (LPR == 4 || LPR == 2), "walk skew of the statistics reads");
-        const int skew = q + (LPR == 2 ? 2 * ((row >> 3) & 1) : 0);
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int m0 = 0; m0 < CPL; ++m0) {
-            const int m = (m0 + skew) % CPL;
-            const float t = trow[m];
-            const float d = (part * CPL + m < valid) ? t - pivot : 0.f;
-            s1 += d;
-            s2 += d * d;
-        }
-#pragma unroll
-        for (int o = 1; o < LPS; o <<= 1) {
-            s1 += __shfl_xor(s1, o);
-            s2 += __shfl_xor(s2, o);
-        }
-        if (part == 0) {
-            const float nv = (float)valid;
-            const size_t t64 = (size_t)ct * TPW + sub;
-            stat_partial_store(statpart + (t64 * 2 + 0) * 512 + rt * T::BM + row, nv * pivot + s1);                      // sum
-            stat_partial_store(statpart + (t64 * 2 + 1) * 512 + rt * T::BM + row, nv > 0.f ? s2 - s1 * s1 / nv : 0.f);   // M2
-        }
-    };
-    // the tile leaves through LDS as 16-byte stores: 16 lanes cover one 256-byte row segment
+    // the tile leaves through LDS as 16-byte stores: 16 lanes cover one 256-byte row segment.  (A lambda, as the statistics were before they
+    // moved to gatsspg_epilogue.h: written as a plain loop the 128-column kernel takes 76 instead of 77 SGPRs.)
     auto tile_stores = [&]() {
 #pragma unroll
         for (int idx = tid; idx < T::BM * (T::BN / 4); idx += T::THREADS) {
@@ -373,8 +301,8 @@ __global__ __launch_bounds__(T::THREADS, (T::TM == 4 ? 1 : (T::WAVES == 4 && T::
             *reinterpret_cast<vf4*>(U + (size_t)(rt * T::BM + row) * ld + c0 + c4) = v;
         }
     };
-    // the partial stores go first; the tile's own stores follow them
-    tile_statistics();
+    // per-tile InstanceNorm partials with the walk skew (mlp0_tile_statistics); the partial stores go first, the tile's own stores follow them
+    mlp0_tile_statistics<T, TS, true>(Tl, statpart, ts.valid, rt, ct);
     asm volatile("" ::: "memory");
     tile_stores();
     if (SP_TRACE_ON(trace)) tr.t[12] = __builtin_readcyclecounter();   // tile stores issued
@@ -448,7 +376,7 @@ __global__ __launch_bounds__(T::THREADS, (T::NST == 2 ? 3 : 2)) void mlp3_sp_ker
     f32x16 acc[T::TM][T::TN];
     {
         float bias[T::TM][16];   // (four 16-byte loads per 32-row tile instead of sixteen broadcast dword loads)
-        load_bias16<T>(b3, rt * T::BM, wm, half, bias);
+        load_bias16<T>(b3 + rt * T::BM, wm, half, bias);
 #pragma unroll
         for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
@@ -468,7 +396,7 @@ __global__ __launch_bounds__(T::THREADS, (T::NST == 2 ? 3 : 2)) void mlp3_sp_ker
     };
     gemm_mainloop_sp<T, 512 / BK, decltype(apl), decltype(bsl), SpPlainHooks<false>, InstNormBx, 4, decltype(pre)>(
         reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld, hooks, bx, nullptr, pre, false, 64);
-    store_tile_direct<T>(acc, Z + (size_t)rt * T::BM * ld + c0, ld, [inv](int, float v) { return v * inv; });
+    store_tile_regs<T>(acc, Z + (size_t)rt * T::BM * ld + c0, ld, [inv](int, float v) { return v * inv; });
 }
 
 // =====================================================================================================
@@ -506,63 +434,9 @@ __global__ __launch_bounds__(T::THREADS, 3) void score_exp_sp_kernel(const unsig
     gemm_mainloop_sp<T, D / BK, decltype(apl), decltype(bsl), SpPlainHooks<true>, SpNoBx, SS>(reinterpret_cast<f32x16(&)[T::TM]>(acc), smem_c, apl, bsl, ld,
                                                                                                 hooks, nobx);
     const float inv = T::F16 ? 1.f / (T::ACT_SCALE * T::ACT_SCALE) : 1.f;   // both operands carry the scale
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
-    constexpr int TS = T::BN + 4;   // conflict-free 16-byte row reads (see mlp0_sp_kernel)
+    constexpr int TS = T::BN + 4;   // staged tile [128][68]: conflict-free 16-byte row reads (see mlp0_sp_kernel)
     static_assert(T::BM * TS * 4 <= T::RING_BYTES, "the output tile is staged in the ring");
-    float* Tl = smem;  // [128][68]
-    float* cf = conf + (size_t)frame * L.n1 * L.n2;
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (wm * T::TM + tm) * 32 + mfma_row(r, half);
-            const int col = wn * 32 + l31;
-            const int gi = rt * T::BM + row, gj = ct * T::BN + col;
-            const float sc = (acc[tm][0][r] * inv) / scale;
-            Tl[row * TS + col] = (gi < L.n1 && gj < L.n2) ? expf(sc) : 0.f;
-        }
-    __syncthreads();
-    if ((L.n2 & 3) == 0 && (reinterpret_cast<uintptr_t>(cf) & 15) == 0) {
-        for (int idx = tid; idx < T::BM * (T::BN / 4); idx += T::THREADS) {
-            const int row = idx / (T::BN / 4), c4 = (idx % (T::BN / 4)) * 4;
-            const int gi = rt * T::BM + row, gj = ct * T::BN + c4;
-            if (gi < L.n1 && gj < L.n2) *reinterpret_cast<vf4*>(cf + (size_t)gi * L.n2 + gj) = *reinterpret_cast<const vf4*>(Tl + row * TS + c4);
-        }
-    } else {
-        for (int idx = tid; idx < T::BM * T::BN; idx += T::THREADS) {
-            const int row = idx / T::BN, col = idx % T::BN;
-            const int gi = rt * T::BM + row, gj = ct * T::BN + col;
-            if (gi < L.n1 && gj < L.n2) cf[(size_t)gi * L.n2 + gj] = Tl[row * TS + col];
-        }
-    }
-    {   // row sums: THREADS / BM lanes per row; column sums: THREADS / BN row groups, one thread per (group, column); fixed order
-        constexpr int LPR = T::THREADS / T::BM, CPL = T::BN / LPR;
-        static_assert(LPR == 2 && CPL == 32, "walk skew of the row sums (rows 4 banks apart, the two lanes of a row 32 banks apart)");
-        const int row = tid / LPR, hp = tid % LPR;
-        const float* tr = Tl + row * TS + hp * CPL;
-        const int skew = hp + 2 * ((row >> 3) & 1);
-        float s = 0.f;
-#pragma unroll 8
-        for (int m = 0; m < CPL; ++m) s += tr[(m + skew) % CPL];
-#pragma unroll
-        for (int o = 1; o < LPR; o <<= 1) s += __shfl_xor(s, o);
-        if (hp == 0 && rt * T::BM + row < L.n1p) rowpart[((size_t)frame * nct + ct) * L.n1p + rt * T::BM + row] = s;
-        constexpr int NQ = T::THREADS / T::BN, RPQ = T::BM / NQ;
-        const int c = tid % T::BN, qp = tid / T::BN;
-        float t = 0.f;
-#pragma unroll 8
-        for (int m = 0; m < RPQ; ++m) t += Tl[(qp * RPQ + m) * TS + c];
-        __syncthreads();
-        Tl[qp * T::BN + c] = t;
-        __syncthreads();
-        if (tid < T::BN) {
-            float tot = 0.f;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) tot += Tl[q * T::BN + tid];
-            colpart[((size_t)frame * nrt + rt) * L.n2p + ct * T::BN + tid] = tot;
-        }
-    }
+    score_epilogue<T, TS, true, false, true>(acc, smem, conf, rowpart, colpart, L, frame, rt, ct, nrt, nct, inv, scale);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -571,7 +445,7 @@ __global__ __launch_bounds__(T::THREADS, 3) void score_exp_sp_kernel(const unsig
 template <int MODE>
 static void launch_score_sp_t(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk) {
     using T = ScoreSpTile<MODE>;
-    allow_big_lds_sp<score_exp_sp_kernel<T>>();
+    allow_big_lds<score_exp_sp_kernel<T>>();
     GATSSPG_LAUNCH(hk, KID_SCORE_EXP, s, (score_exp_sp_kernel<T>), dim3(xcd_grid(w.L.n1p / T::BM, w.L.n2p / T::BN), w.L.b), dim3(T::THREADS),
                    (size_t)T::RING_BYTES, s, w.MDTp, w.MD, conf, w.rowpart, w.colpart, w.L, scale);
 }
@@ -610,7 +484,7 @@ template <int MODE>
 static void launch_qkv_sp_t(const float* sc, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     using T = QkvSpTile<MODE>;
     const PlaneSet p = planes(wb, AttnWB::QKV_H16, AttnWB::QKV_L16);
-    allow_big_lds_sp<qkv_kv_sp_kernel<T>>();
+    allow_big_lds<qkv_kv_sp_kernel<T>>();
     GATSSPG_LAUNCH(hk, KID_QKV_KV, s, qkv_kv_sp_kernel<T>, dim3(xcd_grid(6, active_tiles(w.L))), dim3(T::THREADS), (size_t)T::RING_BYTES + 1024, s,
                    sc, bqkv, p.p0, p.p1, p.p1, w.Z, w.Q, w.kvpart, w.L);
 }
@@ -623,7 +497,7 @@ template <class T>
 static void launch_mlp0_sp_t(const float* sc, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const PlaneSet p = planes(wb, AttnWB::W0_H16, AttnWB::W0_L16);
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
-    allow_big_lds_sp<mlp0_sp_kernel<T>>();
+    allow_big_lds<mlp0_sp_kernel<T>>();
     GATSSPG_LAUNCH(hk, KID_MLP0, s, mlp0_sp_kernel<T>, dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 2048, s, sc, b0,
                    p.p0, p.p1, p.p1, w.Z, w.Q, w.Mpl, w.ksumT, w.zsc, w.U, w.statpart, w.stats, nullptr, w.L, g_trace);
 }
@@ -639,7 +513,7 @@ void launch_mlp0_sp(const float* sc, const float* b0, const unsigned short* wb, 
 
 template <class T>
 static void launch_mlp3_sp_v(const float* sc, const float* b3, const PlaneSet& p, int NT, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    allow_big_lds_sp<mlp3_sp_kernel<T>>();
+    allow_big_lds<mlp3_sp_kernel<T>>();
     GATSSPG_LAUNCH(hk, KID_MLP3, s, mlp3_sp_kernel<T>, dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s, sc, b3,
                    p.p0, p.p1, p.p1, w.U, w.stats, w.Z, w.L);
 }

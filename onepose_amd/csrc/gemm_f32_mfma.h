@@ -83,76 +83,17 @@ __device__ __forceinline__ vf4 ldg4u_off(const float* base, unsigned byte_off) {
 }
 
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Main-loop hooks of the mlp.0 kernel with the linear-attention apply folded in (GATs_SuperGlue.py:78-79,101,113,122):
-//   u = W0a x + sum_h z_h (.) (M_h Qf_h) + b,   M_h = (W0b Wm)[:, head h] KV_h  (kv_final_kernel),   Qf = elu(q) + 1,
-//   z_h[n] = 1 / (sum_d Qf_h[d][n] ksum_h[d] + 1e-6).
-// The K loop runs over [x ; Qf] (16 slabs of 32): slabs 0..7 accumulate the x part, slabs 8 + 2h, 9 + 2h the product of
-// head h into a zeroed accumulator, which is folded into the kept sum with the per-column z_h (a per-lane scalar in the
-// 32x32 MFMA C layout) when the pair ends.  The denominators come from the staged Qf values themselves: every thread
-// multiplies the 4 consecutive k rows of ONE column it sees (fp32 loop: from the LDS slab being computed; split-bf16
-// loops: the registers it is about to split) with the source's ksum, the two slabs of a head are added in the thread, the
-// eight per-wave partials go to LDS and are summed in wave order at the fold: fixed order, no atomics.
-// Requires a 64-column tile on 8 waves (thread = (k group = wave, column = lane)) and one 32x32 MFMA tile per wave.
-// ---------------------------------------------------------------------------------------------------------------------
+// Main-loop hooks: side work of a kernel inside the K loop (the matcher's AttnFoldHooks, gatsspg_epilogue.h); none by default.
 struct NoHooks {
     static constexpr bool ENABLED = false;
 };
-struct AttnFoldHooks {
-    static constexpr bool ENABLED = true;
-    static constexpr int SPLIT = 8;          // first slab of the head phase
-    static constexpr int ZP_FLOATS = 2 * 8 * 64;
-    const float* ks;                         // ksum of the source segment, [4][64] (global, wave-uniform reads)
-    float* zp;                               // LDS [2 (head parity)][8 waves][64 columns]
-    f32x16 kept;                             // x part + folded heads
-    float carry;                             // this thread's partial of the first slab of the current head
-    int wave, lane, col;                     // col = this lane's column in the MFMA C layout (wn * 32 + l31)
-    __device__ __forceinline__ void init(const float* ksum_src, float* zp_lds, int wn) {
-        ks = ksum_src; zp = zp_lds; carry = 0.f;
-        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        lane = threadIdx.x & 63;
-        col = wn * 32 + (lane & 31);
-    }
-    // j = slab index within the head phase (0..7); v0..v3 = rows 4 * wave .. + 3 of that slab, column `lane` of the tile
-    __device__ __forceinline__ void partial(int j, float v0, float v1, float v2, float v3) {
-        const int h = j >> 1;
-        const float* k = ks + h * 64 + (j & 1) * 32 + wave * 4;
-        float p = v0 * k[0];
-        p = fmaf(v1, k[1], p);
-        p = fmaf(v2, k[2], p);
-        p = fmaf(v3, k[3], p);
-        if (j & 1) zp[((h & 1) * 8 + wave) * 64 + lane] = carry + p;
-        else carry = p;
-    }
-    // called after the barrier that ends the slab pair (i, i + 1)
-    __device__ __forceinline__ void pair_end(int i, f32x16& acc) {
-        if (i < SPLIT - 2) return;
-        if (i == SPLIT - 2) {
-            kept = acc;
-        } else {
-            const int h = (i - SPLIT) >> 1;
-            const float* zr = zp + (h & 1) * 8 * 64 + col;
-            float d = zr[0];
-#pragma unroll
-            for (int w = 1; w < 8; ++w) d += zr[w * 64];
-            const float z = 1.f / (d + 1e-6f);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) kept[r] = fmaf(z, acc[r], kept[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    }
-};
-
-// ABLATE (profiling only, wrong results): 1 = no global loads in the steady-state loop,
-//   2 = no global loads and no LDS writes, 3 = steady-state loop cut to one step pair,
-//   6 = every load of a wave hits the same 1 KiB (always L1-hot)
+// (the profiling ablations of this loop -- no loads, no LDS writes, L1-hot loads, one step pair -- are gone: profiles/r05d_trace_mlp0_*)
 // QF (quarter fragments, one 32x32 MFMA tile per wave only): the operand fragments of a slab are read in four quarters of 4 k-steps (one
 //   ds_read_b128 of A + four ds_read_b32 of B each) into TWO alternating register sets instead of two halves of 8: 16 live fragment
 //   registers instead of 32.  Same MFMAs in the same order (bit-identical results); the point is the register budget -- mlp0_kernel
 //   drops from 126 to <= 112 VGPRs, so that a 64-register wave of ANOTHER frame's HBM-bound kernel fits beside two of its workgroups
 //   on a SIMD (DESIGN 12 item 5, round-5 judge item 2).
-template <class T, class ASlab, class BSlab, class XSlabA, class XSlabB, class BXform, bool HAS_AUX, int ABLATE = 0,
+template <class T, class ASlab, class BSlab, class XSlabA, class XSlabB, class BXform, bool HAS_AUX,
           class BCol = IdentityCol, class Hooks = NoHooks, int QF = 0>
 __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], float* smem, int KT, ASlab a_slab, int lda,
                                                  BSlab b_slab, int ldb, XSlabA x_mean, XSlabB x_rstd, BXform bxform,
@@ -166,7 +107,7 @@ __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], fl
     const int kg = wave / T::WAVES_MN, wq = wave % T::WAVES_MN;   // K-split group, wave within the output tiling
     const int wm = wq / T::WN, wn = wq % T::WN;
     const int half = lane >> 5, l31 = lane & 31;
-    static_assert(T::KS == 1 || (ABLATE == 0 && !T::AKM), "K split: plain row-major fp32 loop only");
+    static_assert(T::KS == 1 || !T::AKM, "K split: plain row-major fp32 loop only");
 
     // loop-invariant per-thread byte offsets (global) and LDS float offsets of the staging slots
     unsigned a_goff[T::A_VEC], b_goff[T::B_VEC], x_goff[T::B_VEC];
@@ -207,13 +148,12 @@ __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], fl
     // piece q of the staging loads of slab kt: q < A_VEC -> A piece, else B piece (+ its per-row aux)
     constexpr int NPIECE = T::A_VEC + T::B_VEC;
     auto gload_piece = [&](int kt, int q, vf4(&ra)[T::A_VEC], vf4(&rb)[T::B_VEC], float2(&rx)[T::B_VEC]) {
-        const int ks = ABLATE == 6 ? 0 : kt;
         if (q < T::A_VEC) {
-            ra[q] = ldg4_off(a_slab(ks), ABLATE == 6 ? 16u * lane : a_goff[q]);   // 6: always L1-hot (profiling)
+            ra[q] = ldg4_off(a_slab(kt), a_goff[q]);
         } else {
             const int p = q - T::A_VEC;
-            if constexpr (T::BU) rb[p] = ldg4u_off(b_slab(ks), b_goff[p]);
-            else rb[p] = ldg4_off(b_slab(ks), ABLATE == 6 ? 16u * lane : b_goff[p]);
+            if constexpr (T::BU) rb[p] = ldg4u_off(b_slab(kt), b_goff[p]);
+            else rb[p] = ldg4_off(b_slab(kt), b_goff[p]);
             if constexpr (HAS_AUX)
                 rx[p] = make_float2(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(x_mean(kt)) + x_goff[p]),
                                     *reinterpret_cast<const float*>(reinterpret_cast<const char*>(x_rstd(kt)) + x_goff[p]));
@@ -287,7 +227,7 @@ __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], fl
         __builtin_amdgcn_sched_barrier(0);
         mfma4(a0, b0, 2, 2);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (ABLATE <= 1 || ABLATE == 6) swrite(nxt, ra, rb, rx);   // gap 2 (frees the register set)
+        swrite(nxt, ra, rb, rx);                                  // gap 2 (frees the register set)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < 6; ++g) {                             // MFMA groups 3..8, gaps 3..7 between them
@@ -295,11 +235,9 @@ __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], fl
             else mfma4(a1, b1, 2 * (g - 2), 2);
             __builtin_amdgcn_sched_barrier(0);
             if (g < GAPS) {
-                if constexpr (ABLATE == 0 || ABLATE == 6) {
 #pragma unroll
-                    for (int q = 0; q < NPIECE; ++q)
-                        if (q % GAPS == g) gload_piece(kt_load, q, ra, rb, rx);
-                }
+                for (int q = 0; q < NPIECE; ++q)
+                    if (q % GAPS == g) gload_piece(kt_load, q, ra, rb, rx);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -336,7 +274,7 @@ __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], fl
         __builtin_amdgcn_sched_barrier(0);
         mfma2(a0, b0, 2);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (ABLATE <= 1 || ABLATE == 6) swrite(nxt, ra, rb, rx);   // gap 2 (frees the staging set)
+        swrite(nxt, ra, rb, rx);                                  // gap 2 (frees the staging set)
         read_q(2, a0, b0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -350,11 +288,9 @@ __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], fl
             __builtin_amdgcn_sched_barrier(0);
             if (g == 1) read_q(3, a1, b1);
             if (g < GAPS) {
-                if constexpr (ABLATE == 0 || ABLATE == 6) {
 #pragma unroll
-                    for (int q = 0; q < NPIECE; ++q)
-                        if (q % GAPS == g) gload_piece(kt_load, q, ra, rb, rx);
-                }
+                for (int q = 0; q < NPIECE; ++q)
+                    if (q % GAPS == g) gload_piece(kt_load, q, ra, rb, rx);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -406,10 +342,9 @@ __device__ __forceinline__ void gemm_mainloop_ex(f32x16 (&acc)[T::TM][T::TN], fl
     // Slab indices are clamped (the last loads / writes are redundant but harmless); KT is even for every GEMM
     // here (2, 8, 16 slabs); the body is branch-free and the step pair is unrolled so both register sets are
     // statically indexed (hipcc would otherwise sink the loads into a conditional block next to their use).
-    const int KTL = ABLATE == 3 ? 2 : KT;
     // (a static s_setprio 1 for the younger half of the workgroup -- the guide's two-waves-per-SIMD tip for attention loops -- was
     //  A/B-timed here: 1234 -> 1187 frames/s in flight, 1024 -> 978 one at a time, mlp0 40.0 -> 42.7 us event-timed; not kept)
-    for (int i = 0; i < KTL; i += 2) {
+    for (int i = 0; i < KT; i += 2) {
         if constexpr (T::KS == 2) step_ks(buf0, buf1, i, min(i + 3, last), ra0, rb0, rx0);
         else if constexpr (QF) step_qf(buf0, buf1, i, min(i + 3, last), ra0, rb0, rx0);
         else step(buf0, buf1, i, min(i + 3, last), ra0, rb0, rx0);
@@ -523,17 +458,19 @@ struct Bf3Layout {
 // a_hi(kt) / a_lo(kt): bf16 plane pointers of A slab kt (&A[row0][kt*32], row stride lda elements).
 // b_slab(kt): fp32 pointer &B[kt*32][col0], row stride ldb.  x_mean / x_rstd / bxform: per-k-row aux values applied to
 // the B values before the split (mlp.3: InstanceNorm + ReLU on the operand load).
-// F16: the two planes of each operand hold fp16 terms (fp16_split2) and the products run on v_mfma_f32_32x32x16_f16; layouts,
-// staging and pipeline are those of the bf16 form (16-bit elements either way).
-// NP = 4 (F16 only): the lo x lo product is kept as well (fp16x4).
+// TERMS: TERMS_BF16X3, or TERMS_FP16X4: the two planes of each operand hold fp16 terms (fp16_split2), the products run on
+// v_mfma_f32_32x32x16_f16 and the lo x lo product is kept as well; layouts, staging and pipeline are those of the bf16 form (16-bit
+// elements either way).  (The SuperPoint convolutions are the only fp16x4 user: the matcher's fp16 modes run on gemm_split_glds.h.)
 // BCol: tile column -> element offset from the B slab pointer (identity, or the image-patch map of the SuperPoint convolutions; the B
 // loads of this loop are dword loads, so column-shifted / 4-byte-aligned views (T::BU) need nothing else).
+constexpr int TERMS_BF16X3 = 0, TERMS_FP16X4 = 1;
 template <class T, class AHi, class ALo, class BSlab, class XSlabA, class XSlabB, class BXform, bool HAS_AUX, class Hooks = NoHooks,
-          bool F16 = false, int NP = 3, class BCol = IdentityCol>
+          int TERMS = TERMS_BF16X3, class BCol = IdentityCol>
 __device__ __forceinline__ void gemm_mainloop_bf3_ex(f32x16 (&acc)[T::TM][T::TN], unsigned short* smem, int KT, AHi a_hi, ALo a_lo,
                                                      int lda, BSlab b_slab, int ldb, XSlabA x_mean, XSlabB x_rstd, BXform bxform,
                                                      Hooks* hooks = nullptr, BCol bcolmap = BCol()) {
     static_assert(!T::AKM, "row-major A");
+    static_assert(TERMS == TERMS_BF16X3 || TERMS == TERMS_FP16X4, "bf16x3 or fp16x4");
     using LY = Bf3Layout<T>;
     if constexpr (Hooks::ENABLED)
         static_assert(T::BN == 64 && T::THREADS == 512 && T::TM == 1 && T::TN == 1 && LY::KPT == 4, "fold hooks: 64-column tile, 8 waves");
@@ -602,7 +539,7 @@ __device__ __forceinline__ void gemm_mainloop_bf3_ex(f32x16 (&acc)[T::TM][T::TN]
                 v0 = bxform(v0, rx[j]);
                 v1 = bxform(v1, rx[j + 1]);
             }
-            if constexpr (F16) fp16_split2(v0, v1, h[j / 2], l[j / 2]);
+            if constexpr (TERMS == TERMS_FP16X4) fp16_split2(v0, v1, h[j / 2], l[j / 2]);
             else bf16_split2(v0, v1, h[j / 2], l[j / 2]);
         }
         if constexpr (KPT == 8) {
@@ -643,10 +580,9 @@ __device__ __forceinline__ void gemm_mainloop_bf3_ex(f32x16 (&acc)[T::TM][T::TN]
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn) {
-                    if constexpr (F16) {
+                    if constexpr (TERMS == TERMS_FP16X4) {
                         auto h8 = [](bf16x8 v) { return __builtin_bit_cast(f16x8, v); };   // the registers hold fp16 terms in this mode
-                        if constexpr (NP == 4)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(al[s][tm]), h8(bl[s][tn]), acc[tm][tn], 0, 0, 0);
+                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(al[s][tm]), h8(bl[s][tn]), acc[tm][tn], 0, 0, 0);
                         acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(al[s][tm]), h8(bh[s][tn]), acc[tm][tn], 0, 0, 0);
                         acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(ah[s][tm]), h8(bl[s][tn]), acc[tm][tn], 0, 0, 0);
                         acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(ah[s][tm]), h8(bh[s][tn]), acc[tm][tn], 0, 0, 0);
@@ -889,11 +825,11 @@ __device__ __forceinline__ void gemm_mainloop_bf6_ex(f32x16 (&acc)[T::TM][T::TN]
 struct NoXform1 {
     __device__ __forceinline__ float operator()(float v, float2) const { return v; }
 };
-template <class T, class AHi, class ALo, class BSlab, class Hooks = NoHooks, bool F16 = false, int NP = 3, class BCol = IdentityCol>
+template <class T, class AHi, class ALo, class BSlab, class Hooks = NoHooks, int TERMS = TERMS_BF16X3, class BCol = IdentityCol>
 __device__ __forceinline__ void gemm_mainloop_bf3(f32x16 (&acc)[T::TM][T::TN], unsigned short* smem, int KT, AHi a_hi, ALo a_lo,
                                                   int lda, BSlab b_slab, int ldb, Hooks* hooks = nullptr, BCol bcolmap = BCol()) {
     auto nox = [](int) { return static_cast<const float*>(nullptr); };
-    gemm_mainloop_bf3_ex<T, AHi, ALo, BSlab, decltype(nox), decltype(nox), NoXform1, false, Hooks, F16, NP, BCol>(
+    gemm_mainloop_bf3_ex<T, AHi, ALo, BSlab, decltype(nox), decltype(nox), NoXform1, false, Hooks, TERMS, BCol>(
         acc, smem, KT, a_hi, a_lo, lda, b_slab, ldb, nox, nox, NoXform1(), hooks, bcolmap);
 }
 
@@ -906,11 +842,11 @@ __device__ __forceinline__ void gemm_mainloop_bf6(f32x16 (&acc)[T::TM][T::TN], u
 }
 
 // convenience wrapper without per-row aux / transform
-template <class T, class ASlab, class BSlab, int ABLATE = 0, class BCol = IdentityCol, class Hooks = NoHooks, int QF = 0>
+template <class T, class ASlab, class BSlab, class BCol = IdentityCol, class Hooks = NoHooks, int QF = 0>
 __device__ __forceinline__ void gemm_mainloop(f32x16 (&acc)[T::TM][T::TN], float* smem, int KT, ASlab a_slab, int lda,
                                               BSlab b_slab, int ldb, BCol bcol = BCol(), Hooks* hooks = nullptr) {
     auto nox = [](int) { return static_cast<const float*>(nullptr); };
-    gemm_mainloop_ex<T, ASlab, BSlab, decltype(nox), decltype(nox), NoXform, false, ABLATE, BCol, Hooks, QF>(
+    gemm_mainloop_ex<T, ASlab, BSlab, decltype(nox), decltype(nox), NoXform, false, BCol, Hooks, QF>(
         acc, smem, KT, a_slab, lda, b_slab, ldb, nox, nox, NoXform(), bcol, hooks);
 }
 
@@ -921,21 +857,6 @@ __device__ __forceinline__ void glds16(const void* g, void* lds) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds, 16, 0,
                                      0);
 }
-// A lane's 16 bias values per 32-row MFMA tile (rows 8 k + 4 half + 0..3) from an LDS table of the workgroup's BM bias values.  The table is
-// filled by HALF an LDS-DMA piece (32 lanes x 16 bytes) requested at kernel entry -- older than every operand load of the main loop, so the
-// loop's own waits and barriers cover and publish it -- and read behind the loop: no bias registers across the loop, no per-lane global loads
-// in front of the first operand requests (frames in flight: +3..4 % on the split loop, profiles/r04_ab_live_bias_table.txt).
-template <class T>
-__device__ __forceinline__ void read_bias16(const float* tab, int wm, int half, float (&bias)[T::TM][16]) {
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const vf4 b4 = *reinterpret_cast<const vf4*>(tab + (wm * T::TM + tm) * 32 + 8 * k + 4 * half);
-            bias[tm][4 * k + 0] = b4[0]; bias[tm][4 * k + 1] = b4[1]; bias[tm][4 * k + 2] = b4[2]; bias[tm][4 * k + 3] = b4[3];
-        }
-}
-
 // f(row, v) is applied on the way in; dst points at the tile origin, ld is its row stride; both 16-byte aligned.
 // smem must be free (the main loop ends on a barrier) and hold BM * (BN + 4) floats.
 template <class T, class F>
@@ -991,86 +912,6 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// InstanceNorm statistics fused into the mlp.0 launch (replaces the stat_final_kernel launch between mlp.0 and mlp.3): the LAST
-// workgroup of a (segment, row tile) to finish turns the per-tile partials of its rows into mean / rstd.
-//   * every workgroup leaves its partials with write-through (agent-scope) stores, waits for them (vmcnt(0) + barrier) and draws a
-//     ticket from the (segment, row tile) counter with one relaxed agent-scope atomic -- no L2 write-back fence (guide G16, sc1 form);
-//   * the workgroup that draws the last ticket reads ALL partials of its rows with agent-scope loads and merges them exactly like
-//     stat_final_kernel did (Chan's formula in double precision, tile ranges summed in tile order, ranges combined in range order):
-//     the result does not depend on WHICH workgroup is last nor on the order of arrival -- run-to-run bit-identical;
-//   * the counters are zeroed by kv_final_kernel (always enqueued before mlp.0 on the same segments) and reset by the reducer.
-// smem: 2 * THREADS doubles + one int, free at the call.  stats: [seg][2][512] (mean, 1 / sqrt(var + 1e-5)), GATs_SuperGlue.py:126.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int STATCNT_PER_SEG = 8;   // row tiles of mlp.0 per segment (512 / 64 at most)
-__device__ __forceinline__ void stat_partial_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// PENDING: vector-memory instructions this thread issued AFTER its partial stores (the tile's own stores), which may stay in flight
-template <class T, int PENDING>
-__device__ __forceinline__ void stat_last_block(const float* statpart, float* stats, int* cnt, const ColLayout& L, const TileSeg& ts, int rt,
-                                                void* smem_v) {
-    constexpr int BM = T::BM, PARTS = T::THREADS / BM;
-    static_assert(T::THREADS % BM == 0 && 512 / BM <= STATCNT_PER_SEG, "row tile / counter layout");
-    double* red = reinterpret_cast<double*>(smem_v);   // [2][PARTS][BM]
-    int* flag = reinterpret_cast<int*>(red + 2 * PARTS * BM);
-    const int tid = threadIdx.x;
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory");   // this wave's partial stores (and everything before them) have been acknowledged
-    __syncthreads();                                                  // ... every wave's; nobody still uses the staged tile in LDS
-    if (tid == 0) {
-        const int nwg = (ts.side ? L.n2p : L.n1p) / T::BN;
-        const int old = __hip_atomic_fetch_add(cnt + ts.seg * STATCNT_PER_SEG + rt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag = old == nwg - 1;
-    }
-    __syncthreads();
-    if (!*flag) return;   // block-uniform
-    const int row = tid % BM, part = tid / BM;
-    const int t0 = (ts.frame * L.np + (ts.side ? L.n1p : 0)) / MLP0_BN;
-    const int nt = (ts.side ? L.n2p : L.n1p) / MLP0_BN;
-    const int n = ts.side ? L.n2 : L.n1;
-    const int per = (nt + PARTS - 1) / PARTS;
-    const int tb = part * per, te = min(nt, tb + per);
-    const int ch = rt * BM + row;
-    double S = 0.0, QP = 0.0;
-    constexpr int CH = 32;   // tiles per round trip: this workgroup is the last one running in its group, so latency is all that counts
-    for (int tt = tb; tt < te; tt += CH) {   // 2 x 32 loads in flight at a time on clamped addresses
-        float xs[CH], xm[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const size_t tile = (size_t)(t0 + min(tt + u, nt - 1));
-            xs[u] = __hip_atomic_load(statpart + (tile * 2 + 0) * 512 + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            xm[u] = __hip_atomic_load(statpart + (tile * 2 + 1) * 512 + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int t = tt + u;
-            const int nv = min(MLP0_BN, n - t * MLP0_BN);   // real columns of tile t of this segment (<= 0: pad-only tile)
-            if (t < te && nv > 0) {
-                const double st = (double)xs[u], mt = (double)xm[u];
-                const double inv = nv == MLP0_BN ? 1.0 / MLP0_BN : 1.0 / nv;
-                S += st;
-                QP += mt + st * st * inv;
-            }
-        }
-    }
-    red[(0 * PARTS + part) * BM + row] = S;
-    red[(1 * PARTS + part) * BM + row] = QP;
-    __syncthreads();
-    if (part == 0) {
-        S = red[row];
-        QP = red[PARTS * BM + row];
-#pragma unroll
-        for (int p = 1; p < PARTS; ++p) {
-            S += red[p * BM + row];
-            QP += red[(PARTS + p) * BM + row];
-        }
-        const double mean = S / n;
-        double var = (QP - S * mean) / n;
-        if (var < 0.0) var = 0.0;
-        stats[((size_t)ts.seg * 2 + 0) * 512 + ch] = (float)mean;
-        stats[((size_t)ts.seg * 2 + 1) * 512 + ch] = (float)(1.0 / sqrt(var + 1e-5));
-    }
-    if (tid == 0) __hip_atomic_store(cnt + ts.seg * STATCNT_PER_SEG + rt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // XCD-aware block -> (row tile, column tile) map (cdna guide T1): workgroup id g is dispatched
 // to XCD g % 8; give each XCD whole column tiles and walk that tile's row tiles back to back so
 // the B panel [K x BN] is fetched into one XCD's L2 once and re-used by all M/BM row tiles.
@@ -1092,14 +933,6 @@ __device__ __forceinline__ bool xcd_tile_map_g(int MT, int NT, int gs, int& rt, 
     const int cs = slot / MT;
     ct = ((((cs >> gs) << 3) + xcd) << gs) + (cs & ((1 << gs) - 1));
     return ct < NT;
-}
-
-__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
-// same values, branch-free: both sides are evaluated and selected (epilogues that apply elu to 16-32 accumulator values per
-// lane: a divergent branch per value serialises whatever sits next to it)
-__device__ __forceinline__ float elu1_select(float x) {
-    const float e = expm1f(fminf(x, 0.f));
-    return x > 0.f ? x : e;
 }
 
 }  // namespace gatsspg

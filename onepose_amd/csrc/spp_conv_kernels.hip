@@ -20,7 +20,7 @@ using gatsspg::f32x16;
 using gatsspg::GemmTile;
 using gatsspg::mfma_row;
 
-// PREC: 0 = fp32 MFMA main loop; 4 = four-term split-fp16 (gemm_mainloop_bf3, F16, NP = 4: two fp16 terms per operand, all four
+// PREC: 0 = fp32 MFMA main loop; 4 = four-term split-fp16 (gemm_mainloop_bf3, TERMS_FP16X4: two fp16 terms per operand, all four
 // products on v_mfma_f32_32x32x16_f16 -- fp32-class results, a quarter of the matrix-pipe time; weights pre-split at pack time,
 // activations split in the loop)
 template <class T, int PREC = 0>
@@ -172,12 +172,12 @@ __global__ __launch_bounds__(T::THREADS) void conv_gemm_kernel(const float* __re
         auto alo = [&](int kt) { return Pl + (size_t)kt * rows * BK; };
         unsigned short* sm16 = reinterpret_cast<unsigned short*>(smem);
         if constexpr (PATCH)
-            gatsspg::gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), gatsspg::NoHooks, true, 4, PatchCol>(
+            gatsspg::gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), gatsspg::NoHooks, gatsspg::TERMS_FP16X4, PatchCol>(
                 acc, sm16, KT, ah, alo, BK, bl, ldt, nullptr, PatchCol{HALF, Wp});
         else
-            gatsspg::gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), gatsspg::NoHooks, true, 4>(acc, sm16, KT, ah, alo, BK, bl, ldt);
+            gatsspg::gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), gatsspg::NoHooks, gatsspg::TERMS_FP16X4>(acc, sm16, KT, ah, alo, BK, bl, ldt);
     } else {
-        if constexpr (PATCH) gatsspg::gemm_mainloop<T, decltype(al), decltype(bl), 0, PatchCol>(acc, smem, KT, al, TAPS * CIN, bl, ldt, PatchCol{HALF, Wp});
+        if constexpr (PATCH) gatsspg::gemm_mainloop<T, decltype(al), decltype(bl), PatchCol>(acc, smem, KT, al, TAPS * CIN, bl, ldt, PatchCol{HALF, Wp});
         else gatsspg::gemm_mainloop<T>(acc, smem, KT, al, TAPS * CIN, bl, ldt);
     }
 
@@ -271,10 +271,10 @@ __global__ __launch_bounds__(T::THREADS) void conv_pool_kernel(const float* __re
         const unsigned short* Pl = Ph + (size_t)rows * (9 * CIN);
         auto ah = [&](int kt) { return Ph + (size_t)kt * rows * BK; };
         auto alo = [&](int kt) { return Pl + (size_t)kt * rows * BK; };
-        gatsspg::gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), gatsspg::NoHooks, true, 4, PatchCol>(
+        gatsspg::gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), gatsspg::NoHooks, gatsspg::TERMS_FP16X4, PatchCol>(
             acc, reinterpret_cast<unsigned short*>(smem), KT, ah, alo, BK, bl, ldt, nullptr, PatchCol{64, Wp});
     } else {
-        gatsspg::gemm_mainloop<T, decltype(al), decltype(bl), 0, PatchCol>(acc, smem, KT, al, 9 * CIN, bl, ldt, PatchCol{64, Wp});
+        gatsspg::gemm_mainloop<T, decltype(al), decltype(bl), PatchCol>(acc, smem, KT, al, 9 * CIN, bl, ldt, PatchCol{64, Wp});
     }
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
