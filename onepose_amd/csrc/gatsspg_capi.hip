@@ -1,6 +1,5 @@
 // C ABI of libgatsspg_hip.so (declared in include/gatsspg.h).  Thin: argument checks, workspace
 // carve-up, kernel enqueue on the caller's stream.  No allocation, no synchronisation.
-#include <string.h>
 
 #include "../../include/gatsspg.h"
 #include "gatsspg_launch.h"
@@ -21,17 +20,23 @@ int check_dims(int b, int n1, int n2, int num_leaf) {
     return 0;
 }
 
+// the one place where the ABI's flag bits become an Arith
+int arith_of_flags(int flags, Arith& a) {
+    constexpr int PREC_BITS = GATSSPG_FLAG_PREC_BF16X3 | GATSSPG_FLAG_PREC_BF16X6 | GATSSPG_FLAG_PREC_FP16X3 | GATSSPG_FLAG_PREC_FP16X4;
+    if (flags & ~(GATSSPG_FLAG_INCLUDE_SELF | GATSSPG_FLAG_ADDITIONAL | GATSSPG_FLAG_WITH_LINEAR_TRANSFORM | PREC_BITS))
+        return fail(1, "unknown bits in flags (0x%x)", flags);
+    constexpr int BIT[] = {0, GATSSPG_FLAG_PREC_BF16X3, GATSSPG_FLAG_PREC_BF16X6, GATSSPG_FLAG_PREC_FP16X3, GATSSPG_FLAG_PREC_FP16X4};   // by Arith
+    for (int i = FP32; i <= FP16X4; ++i)
+        if ((flags & PREC_BITS) == BIT[i]) { a = Arith(i); return 0; }
+    return fail(1, "GATSSPG_FLAG_PREC_BF16X3, _BF16X6, _FP16X3 and _FP16X4 are exclusive");
+}
+
 int check_ws(const void* ws, size_t ws_bytes, int b, int n1, int n2, int num_leaf, Workspace& w, int flags = 0) {
     if (int e = check_dims(b, n1, n2, num_leaf)) return e;
     if (!ws) return fail(1, "workspace pointer is null");
     if (reinterpret_cast<uintptr_t>(ws) & 15) return fail(1, "workspace must be 16-byte aligned");
-    constexpr int PREC_BITS = GATSSPG_FLAG_PREC_BF16X3 | GATSSPG_FLAG_PREC_BF16X6 | GATSSPG_FLAG_PREC_FP16X3 | GATSSPG_FLAG_PREC_FP16X4;
-    if (flags & ~(GATSSPG_FLAG_INCLUDE_SELF | GATSSPG_FLAG_ADDITIONAL | GATSSPG_FLAG_WITH_LINEAR_TRANSFORM | PREC_BITS))
-        return fail(1, "unknown bits in flags (0x%x)", flags);
-    const int pb = flags & PREC_BITS;
-    if (pb & (pb - 1)) return fail(1, "GATSSPG_FLAG_PREC_BF16X3, _BF16X6, _FP16X3 and _FP16X4 are exclusive");
     w = carve_workspace(const_cast<void*>(ws), b, n1, n2);
-    w.prec = (flags & GATSSPG_FLAG_PREC_BF16X6) ? 2 : (flags & GATSSPG_FLAG_PREC_BF16X3) ? 1 : (flags & GATSSPG_FLAG_PREC_FP16X3) ? 3 : (flags & GATSSPG_FLAG_PREC_FP16X4) ? 4 : 0;
+    if (int e = arith_of_flags(flags, w.prec)) return e;
     if (ws_bytes < w.bytes) return fail(1, "workspace too small: %zu < %zu bytes", ws_bytes, w.bytes);
     return 0;
 }
@@ -41,40 +46,50 @@ int check_ws(const void* ws, size_t ws_bytes, int b, int n1, int n2, int num_lea
 // reference's 0.07 gives 14.3) and one pass over S yields both normalisers.  Smaller scale factors take the
 // max-subtracting path (raw scores -> row/column maxima and shifted sums -> finalize), which has the full range of
 // torch.softmax (GATs_SuperGlue.py:218).
-int check_scale(float scale_factor) {
-    if (!(scale_factor > 0.f)) return fail(1, "scale_factor must be positive");
-    return 0;
-}
+int check_scale(float scale_factor) { return scale_factor > 0.f ? 0 : fail(1, "scale_factor must be positive"); }
 inline int softmax_shifted(float scale_factor) { return scale_factor < 0.0125f ? 1 : 0; }
-
-const float* attn_w(const float* packed, int layer) { return packed + PW_ATTN + (size_t)layer * AttnW::SIZE; }
-const unsigned short* attn_wb(const float* packed, int layer) {
-    return reinterpret_cast<const unsigned short*>(packed + PW_TOTAL) + (size_t)layer * AttnWB::SIZE;
-}
-const float* gats_w(const float* packed, int layer) { return packed + PW_GATS + (size_t)layer * GatsW::SIZE; }
 
 // h3 / dq: fused state load (see launch_gats); only valid when gats_fuses_state_load() says so
 void enqueue_gats(const float* packed, int layer, const float* desc2d_db, int num_leaf, int flags, const Workspace& w,
                   hipStream_t s, ProfileHook* hk = nullptr, const float* h3 = nullptr, const float* dq = nullptr,
                   const float* cached_logits = nullptr) {
-    const float* g = gats_w(packed, layer);
+    const GatsLayer g = gats_layer(packed, layer);
     if (flags & GATSSPG_FLAG_WITH_LINEAR_TRANSFORM) {
         // pre-activation aggregate -> MSG (free between attention layers), then elu(W^T pre (+h))
-        launch_gats(g + GatsW::U1, g + GatsW::U2, desc2d_db, num_leaf, flags, w.MSG, w, s, hk);
+        launch_gats(g, desc2d_db, num_leaf, flags, w.MSG, w, s, hk);
         const int add_h = (flags & GATSSPG_FLAG_INCLUDE_SELF) && (flags & GATSSPG_FLAG_ADDITIONAL);
-        launch_gats_wlt(g + GatsW::W, w.MSG, w, add_h, s, hk);
+        launch_gats_wlt(g, w.MSG, w, add_h, s, hk);
     } else {
-        launch_gats(g + GatsW::U1, g + GatsW::U2, desc2d_db, num_leaf, flags, w.Z, w, s, hk, h3, dq, cached_logits);
+        launch_gats(g, desc2d_db, num_leaf, flags, w.Z, w, s, hk, h3, dq, cached_logits);
     }
 }
 
 void enqueue_attn(const float* packed, int layer, int kind, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr) {
-    const float* a = attn_w(packed, layer);
-    const unsigned short* ab = attn_wb(packed, layer);
-    launch_qkv_kv(a + AttnW::WQKV, a + AttnW::BQKV, ab, w, s, hk);
-    launch_kv_final(a + AttnW::W0, w, kind == GATSSPG_LAYER_CROSS, nullptr, s, hk);
-    launch_mlp(a + AttnW::W0, a + AttnW::B0, a + AttnW::W3, a + AttnW::B3, ab, w, s, hk);
+    const AttnLayer a = attn_layer(packed, layer);
+    launch_qkv_kv(a, w, s, hk);
+    launch_kv_final(a, w, kind == GATSSPG_LAYER_CROSS, nullptr, s, hk);
+    launch_mlp(a, w, s, hk);
 }
+
+// rounds t0..3 of ['GATs', 'self', 'cross'] (GATs_SuperGlue.py:162).  h3 / dq: the fused state load of round 0 (enqueue_gats), or null;
+// ll: the cached leaf logits of rounds 1..3, ll_layer floats apart (DbCache::LL), or null
+void enqueue_rounds(const float* packed, int t0, const float* desc2d_db, int num_leaf, int flags, const Workspace& w, hipStream_t s,
+                    ProfileHook* hk, const float* h3, const float* dq, const float* ll, size_t ll_layer) {
+    for (int t = t0; t < 4; ++t) {
+        enqueue_gats(packed, t, desc2d_db, num_leaf, flags, w, s, hk, t ? nullptr : h3, t ? nullptr : dq, t && ll ? ll + (size_t)(t - 1) * ll_layer : nullptr);
+        enqueue_attn(packed, 2 * t, GATSSPG_LAYER_SELF, w, s, hk);
+        enqueue_attn(packed, 2 * t + 1, GATSSPG_LAYER_CROSS, w, s, hk);
+    }
+}
+
+// final projection (packed == nullptr: already done, w.MD / w.MDT hold the descriptors), score, dual softmax and match
+void enqueue_tail(const float* packed, const Workspace& w, float scale_factor, float match_threshold, const MatchOut& out, hipStream_t s, ProfileHook* hk) {
+    const int shifted = softmax_shifted(scale_factor);
+    if (packed) launch_final_proj_norm(packed + PW_FINAL_W, packed + PW_FINAL_B, w, s, hk);
+    launch_score_exp(w, out.conf, scale_factor, shifted, s, hk);
+    launch_dual_softmax_match(w, out, shifted, match_threshold, s, hk);
+}
+int check_out(const MatchOut& o) { return o.conf && o.matches0 && o.matches1 && o.mscores0 && o.mscores1 ? 0 : fail(1, "null output pointer"); }
 
 // ---- database cache: everything of the first three GNN layers that depends only on the
 //      per-object 3D database.  Layout (floats): Y2 [b][256][n2] | QY [b][256][n2] | kvY [b][4][KVP] |
@@ -103,28 +118,20 @@ Workspace windowed(const Workspace& w, int side) {
 }
 
 int forward_impl(const float* packed, const float* desc2d_query, const float* desc3d_db, const float* desc2d_db, int b,
-                 int n1, int n2, int num_leaf, int flags, float scale_factor, float match_threshold, float* conf,
-                 int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, void* ws, size_t ws_bytes,
-                 void* stream, ProfileHook* hk) {
+                 int n1, int n2, int num_leaf, int flags, float scale_factor, float match_threshold, const MatchOut& out,
+                 void* ws, size_t ws_bytes, void* stream, ProfileHook* hk) {
     Workspace w;
     if (int e = check_ws(ws, ws_bytes, b, n1, n2, num_leaf, w, flags)) return e;
     if (!packed || !desc2d_query || !desc3d_db || !desc2d_db) return fail(1, "null input pointer");
-    if (!conf || !matches0 || !matches1 || !mscores0 || !mscores1) return fail(1, "null output pointer");
+    if (int e = check_out(out)) return e;
     if (int e = check_scale(scale_factor)) return e;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the state load is fused into the first GATs launch where that kernel supports it (num_leaf == 8, no linear transform)
     const bool fused_load = gats_fuses_state_load(num_leaf, flags, w);
     if (!fused_load) launch_load_state(desc2d_query, desc3d_db, w, s, hk);
-    for (int t = 0; t < 4; ++t) {  // ['GATs', 'self', 'cross'] * 4, GATs_SuperGlue.py:162
-        if (t == 0 && fused_load) enqueue_gats(packed, t, desc2d_db, num_leaf, flags, w, s, hk, desc3d_db, desc2d_query);
-        else enqueue_gats(packed, t, desc2d_db, num_leaf, flags, w, s, hk);
-        enqueue_attn(packed, 2 * t, GATSSPG_LAYER_SELF, w, s, hk);
-        enqueue_attn(packed, 2 * t + 1, GATSSPG_LAYER_CROSS, w, s, hk);
-    }
-    const int shifted = softmax_shifted(scale_factor);
-    launch_final_proj_norm(packed + PW_FINAL_W, packed + PW_FINAL_B, w, s, hk);
-    launch_score_exp(w, conf, scale_factor, shifted, s, hk);
-    launch_dual_softmax_match(w, conf, scale_factor, shifted, match_threshold, matches0, matches1, mscores0, mscores1, s, hk);
+    enqueue_rounds(packed, 0, desc2d_db, num_leaf, flags, w, s, hk, fused_load ? desc3d_db : nullptr,
+                   fused_load ? desc2d_query : nullptr, nullptr, 0);
+    enqueue_tail(packed, w, scale_factor, match_threshold, out, s, hk);
     return check_launch(1, "forward");
 }
 }  // namespace
@@ -205,13 +212,11 @@ int gatsspg_score_dual_softmax_match(int b, int n1, int n2, int num_leaf, float 
                                      float* conf, int64_t* matches0, int64_t* matches1, float* mscores0,
                                      float* mscores1, void* ws, size_t ws_bytes, void* stream) {
     Workspace w;
+    const MatchOut out = {conf, matches0, matches1, mscores0, mscores1};
     if (int e = check_ws(ws, ws_bytes, b, n1, n2, num_leaf, w)) return e;
-    if (!conf || !matches0 || !matches1 || !mscores0 || !mscores1) return fail(1, "null output pointer");
+    if (int e = check_out(out)) return e;
     if (int e = check_scale(scale_factor)) return e;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int shifted = softmax_shifted(scale_factor);
-    launch_score_exp(w, conf, scale_factor, shifted, s);
-    launch_dual_softmax_match(w, conf, scale_factor, shifted, match_threshold, matches0, matches1, mscores0, mscores1, s);
+    enqueue_tail(nullptr, w, scale_factor, match_threshold, out, static_cast<hipStream_t>(stream), nullptr);
     return check_launch(1, "score_dual_softmax_match");
 }
 
@@ -220,7 +225,7 @@ int gatsspg_forward(const float* packed, const float* desc2d_query, const float*
                     int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, void* ws, size_t ws_bytes,
                     void* stream) {
     return forward_impl(packed, desc2d_query, desc3d_db, desc2d_db, b, n1, n2, num_leaf, flags, scale_factor,
-                        match_threshold, conf, matches0, matches1, mscores0, mscores1, ws, ws_bytes, stream, nullptr);
+                        match_threshold, {conf, matches0, matches1, mscores0, mscores1}, ws, ws_bytes, stream, nullptr);
 }
 
 int gatsspg_forward_profiled(const float* packed, const float* desc2d_query, const float* desc3d_db,
@@ -230,14 +235,9 @@ int gatsspg_forward_profiled(const float* packed, const float* desc2d_query, con
                              void* ev_start, void* ev_stop) {
     if (kernel_id < 0 || kernel_id >= KID_COUNT) return fail(1, "kernel_id %d out of range", kernel_id);
     if (!ev_start || !ev_stop) return fail(1, "null event");
-    ProfileHook hk;
-    memset(&hk, 0, sizeof(hk));
-    hk.kernel_id = kernel_id;
-    hk.occurrence = occurrence;
-    hk.start = static_cast<hipEvent_t>(ev_start);
-    hk.stop = static_cast<hipEvent_t>(ev_stop);
+    ProfileHook hk = {kernel_id, occurrence, static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop), {}};
     if (int e = forward_impl(packed, desc2d_query, desc3d_db, desc2d_db, b, n1, n2, num_leaf, flags, scale_factor,
-                             match_threshold, conf, matches0, matches1, mscores0, mscores1, ws, ws_bytes, stream, &hk))
+                             match_threshold, {conf, matches0, matches1, mscores0, mscores1}, ws, ws_bytes, stream, &hk))
         return e;
     if (hk.seen[kernel_id] <= occurrence) return fail(1, "kernel %d was launched %d times, occurrence %d never ran", kernel_id, hk.seen[kernel_id], occurrence);
     return 0;
@@ -266,16 +266,16 @@ int gatsspg_prepare_database(const float* packed, const float* desc3d_db, const 
     launch_load_state(nullptr, desc3d_db, w, s);
     enqueue_gats(packed, 0, desc2d_db, num_leaf, flags, w, s);              // gnn.layers.0 (3D side only by nature)
     enqueue_attn(packed, 0, GATSSPG_LAYER_SELF, wy, s);                     // gnn.layers.1, 3D side
-    const float* a1 = attn_w(packed, 1);
-    launch_qkv_kv(a1 + AttnW::WQKV, a1 + AttnW::BQKV, attn_wb(packed, 1), wy, s);   // gnn.layers.2: 3D-side Q, KV, ksum
-    launch_kv_final(a1 + AttnW::W0, wy, 1, nullptr, s);                             //   (the final sums land in w.kvfin)
+    const AttnLayer a1 = attn_layer(packed, 1);
+    launch_qkv_kv(a1, wy, s);                                               // gnn.layers.2: 3D-side Q, KV, ksum
+    launch_kv_final(a1, wy, 1, nullptr, s);                                 //   (the final sums land in w.kvfin)
     launch_store_state(w.Z, nullptr, c.Y2, w, s);
     launch_store_state(w.Q, nullptr, c.QY, w, s);
     if (hipMemcpy2DAsync(c.kvY, sizeof(float) * H * KVP, w.kvfin + (size_t)H * KVP, sizeof(float) * 2 * H * KVP,
                          sizeof(float) * H * KVP, b, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return fail(1, "prepare_database: copy of the KV sums failed");
     if (gats_caches_leaf_logits(num_leaf, flags))   // leaf . u1 of the three GATs layers still to come
-        launch_gats_leaf_logits(gats_w(packed, 1) + GatsW::U1, GatsW::SIZE, 3, desc2d_db, c.LL, w, s);
+        launch_gats_leaf_logits(gats_layer(packed, 1), 3, desc2d_db, c.LL, w, s);
     return check_launch(1, "prepare_database");
 }
 
@@ -284,9 +284,10 @@ int gatsspg_forward_cached(const float* packed, const float* desc2d_query, const
                            float match_threshold, float* conf, int64_t* matches0, int64_t* matches1, float* mscores0,
                            float* mscores1, void* ws, size_t ws_bytes, void* stream) {
     Workspace w;
+    const MatchOut out = {conf, matches0, matches1, mscores0, mscores1};
     if (int e = check_ws(ws, ws_bytes, b, n1, n2, num_leaf, w, flags)) return e;
     if (!packed || !desc2d_query || !desc2d_db || !cache) return fail(1, "null input pointer");
-    if (!conf || !matches0 || !matches1 || !mscores0 || !mscores1) return fail(1, "null output pointer");
+    if (int e = check_out(out)) return e;
     if (int e = check_scale(scale_factor)) return e;
     const DbCache c = carve_cache(const_cast<void*>(cache), b, n2);
     if (cache_bytes < c.bytes) return fail(1, "database cache too small: %zu < %zu bytes", cache_bytes, c.bytes);
@@ -294,22 +295,14 @@ int gatsspg_forward_cached(const float* packed, const float* desc2d_query, const
     const Workspace wx = windowed(w, 0);
     launch_load_state(desc2d_query, c.Y2, w, s);                            // state = [X0 | cached Y2]
     enqueue_attn(packed, 0, GATSSPG_LAYER_SELF, wx, s);                     // gnn.layers.1, query side only
-    const float* a1 = attn_w(packed, 1);
-    launch_qkv_kv(a1 + AttnW::WQKV, a1 + AttnW::BQKV, attn_wb(packed, 1), wx, s);   // gnn.layers.2: query-side Q, KV, ksum
+    const AttnLayer a1 = attn_layer(packed, 1);
+    launch_qkv_kv(a1, wx, s);                                               // gnn.layers.2: query-side Q, KV, ksum
     launch_load_columns(nullptr, c.QY, w.Q, w, s);                          // 3D-side Q from the cache
-    launch_kv_final(a1 + AttnW::W0, w, 1, c.kvY, s);                        // query-side sums from the partials, 3D-side sums from the cache
-    launch_mlp(a1 + AttnW::W0, a1 + AttnW::B0, a1 + AttnW::W3, a1 + AttnW::B3, attn_wb(packed, 1), w, s);
-    const bool cached_logits = gats_caches_leaf_logits(num_leaf, flags);
-    for (int t = 1; t < 4; ++t) {
-        enqueue_gats(packed, t, desc2d_db, num_leaf, flags, w, s, nullptr, nullptr, nullptr,
-                     cached_logits ? c.LL + (size_t)(t - 1) * c.ll_layer : nullptr);
-        enqueue_attn(packed, 2 * t, GATSSPG_LAYER_SELF, w, s);
-        enqueue_attn(packed, 2 * t + 1, GATSSPG_LAYER_CROSS, w, s);
-    }
-    const int shifted = softmax_shifted(scale_factor);
-    launch_final_proj_norm(packed + PW_FINAL_W, packed + PW_FINAL_B, w, s);
-    launch_score_exp(w, conf, scale_factor, shifted, s);
-    launch_dual_softmax_match(w, conf, scale_factor, shifted, match_threshold, matches0, matches1, mscores0, mscores1, s);
+    launch_kv_final(a1, w, 1, c.kvY, s);                                    // query-side sums from the partials, 3D-side sums from the cache
+    launch_mlp(a1, w, s);
+    enqueue_rounds(packed, 1, desc2d_db, num_leaf, flags, w, s, nullptr, nullptr, nullptr,
+                   gats_caches_leaf_logits(num_leaf, flags) ? c.LL : nullptr, c.ll_layer);
+    enqueue_tail(packed, w, scale_factor, match_threshold, out, s, nullptr);
     return check_launch(1, "forward_cached");
 }
 

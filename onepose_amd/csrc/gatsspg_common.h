@@ -132,10 +132,44 @@ struct AttnWB {
 constexpr size_t PWB_TOTAL = 8 * AttnWB::SIZE;                   // bf16 elements
 constexpr size_t PACKED_BYTES = sizeof(float) * PW_TOTAL + sizeof(unsigned short) * PWB_TOTAL;
 
+// Host-side views of one layer of the blob: what the launchers take instead of pointers into it.
+struct WPlanes { const unsigned short *hi, *lo, *lo2, *h16, *l16; };   // the 16-bit planes of one operator
+struct AttnLayer {
+    const float* w;             // the layer's AttnW block
+    const unsigned short* wb;   // the layer's AttnWB block
+    const float* WQKV() const { return w + AttnW::WQKV; }
+    const float* BQKV() const { return w + AttnW::BQKV; }
+    const float* W0() const { return w + AttnW::W0; }
+    const float* B0() const { return w + AttnW::B0; }
+    const float* W3() const { return w + AttnW::W3; }
+    const float* B3() const { return w + AttnW::B3; }
+    const float* SC() const { return w + AttnW::SC; }
+    WPlanes qkv_planes() const { return {wb + AttnWB::QKV_HI, wb + AttnWB::QKV_LO, wb + AttnWB::QKV_LO2, wb + AttnWB::QKV_H16, wb + AttnWB::QKV_L16}; }
+    WPlanes w0_planes() const { return {wb + AttnWB::W0_HI, wb + AttnWB::W0_LO, wb + AttnWB::W0_LO2, wb + AttnWB::W0_H16, wb + AttnWB::W0_L16}; }
+    WPlanes w3_planes() const { return {wb + AttnWB::W3_HI, wb + AttnWB::W3_LO, wb + AttnWB::W3_LO2, wb + AttnWB::W3_H16, wb + AttnWB::W3_L16}; }
+};
+struct GatsLayer {
+    const float* w;             // the layer's GatsW block
+    const float* U1() const { return w + GatsW::U1; }
+    const float* U2() const { return w + GatsW::U2; }
+    const float* W() const { return w + GatsW::W; }
+};
+inline AttnLayer attn_layer(const float* packed, int layer) {
+    return {packed + PW_ATTN + (size_t)layer * AttnW::SIZE, reinterpret_cast<const unsigned short*>(packed + PW_TOTAL) + (size_t)layer * AttnWB::SIZE};
+}
+inline GatsLayer gats_layer(const float* packed, int layer) { return {packed + PW_GATS + (size_t)layer * GatsW::SIZE}; }
+
+// The arithmetic of a call's qkv_kv / mlp0 / mlp3 main loops, from the GATSSPG_FLAG_PREC_* bit of its flags: exact fp32 MFMA, three- / six-term
+// split-bf16, three- / four-term split-fp16.  The values are kernel and template arguments (PREC of the register-staged kernels: FP32..BF16X6;
+// MODE of the split-loop tiles: BF16X6..FP16X4) and with that part of the kernel names: they do not change.
+enum Arith : int { FP32 = 0, BF16X3 = 1, BF16X6 = 2, FP16X3 = 3, FP16X4 = 4 };
+constexpr bool is_fp16(Arith a) { return a >= FP16X3; }                // also: the three GEMMs run on the split loop (gatsspg_split_kernels.hip)
+constexpr bool needs_operator_planes(Arith a) { return a != FP32; }   // mlp0 multiplies 16-bit planes of the message operator (Workspace::Mpl), not Mop
+
 // ---- workspace carve-up ---------------------------------------------------------------------------
 struct Workspace {
     ColLayout L;
-    int prec;          // 0: fp32 MFMA; 1: three-term split-bf16 (bf16x3), 2: six-term (bf16x6), 3 / 4: three- / four-term split-fp16 (fp16x3, fp16x4) main loops in qkv_kv / mlp0 / mlp3 (from the call's flags)
+    Arith prec;        // from the call's flags
     int nt64;          // ld / 64 column tiles
     int nseg;          // 2*b
     int sc_nct, sc_nrt;   // score kernel tiles per frame (n2p/SC_BN, n1p/SC_BM)
@@ -148,7 +182,7 @@ struct Workspace {
     // linear attention folded into mlp.0 (kv_final_kernel -> mlp0_kernel): per TARGET segment t the operator
     // M_t = (W0b Wm)[:, head h] KV_h(source) for the four heads [512][4 x 64], and the source's ksum.
     float *Mop;                      // [b][512][512]: segment 2f at columns 256..511, segment 2f+1 at columns 0..255 of frame f's block
-    unsigned short *Mpl;             // split-bf16 planes of M_t (prec != 0): [nseg][3][8 slabs][512][32]
+    unsigned short *Mpl;             // 16-bit planes of M_t (needs_operator_planes): [nseg][3][8 slabs][512][32]
     float *ksumT;                    // [nseg][4][64]
     float *zsc;                      // [nseg][4]: per head, fold factor of the target segment's operator planes = (scale of the W0 planes) / (scale of Mpl_h), a power of two
     float *rowpart, *colpart, *rs, *cs;
@@ -166,7 +200,7 @@ __host__ __device__ inline const float* mop_seg(const float* Mop, int seg) {
 inline Workspace carve_workspace(void* base, int b, int n1, int n2) {
     Workspace w;
     w.L = make_layout(b, n1, n2);
-    w.prec = 0;
+    w.prec = FP32;
     const ColLayout& L = w.L;
     w.nt64 = L.ld / 64;
     w.nseg = 2 * b;

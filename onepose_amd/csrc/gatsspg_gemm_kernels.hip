@@ -10,12 +10,12 @@ namespace gatsspg {
 // dynamic LDS of a main loop (operand stages; the epilogues re-use it)
 template <class T, int PREC = 0>
 constexpr size_t smem_bytes() {
-    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6: the fp16 modes run on the kernels of gatsspg_split_kernels.hip");
+    static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6: the fp16 modes run on the kernels of gatsspg_split_kernels.hip");
     size_t b = sizeof(float) * T::SMEM_FLOATS;
-    if constexpr (PREC == 1) {
+    if constexpr (PREC == BF16X3) {
         if (Bf3Layout<T>::SMEM_BYTES > b) b = Bf3Layout<T>::SMEM_BYTES;
     }
-    if constexpr (PREC == 2) {
+    if constexpr (PREC == BF16X6) {
         if (Bf6Layout<T>::SMEM_BYTES > b) b = Bf6Layout<T>::SMEM_BYTES;
     }
     return b;
@@ -35,19 +35,19 @@ constexpr int smem_floats_mainloop() { return (int)(smem_bytes<T, PREC>() / size
 using QkvTileW8 = GemmTile<128, QKV_BN, 4, 2, false>;     // both arithmetics: 8 waves, one 32x32 MFMA tile each (fp32: 38.0 vs 40.1 us on 4 waves)
 // (split-bf16 on 4 waves, 64x32 per wave: 31.2 vs 24.6 us; removed with the QKV_BTILE knob)
 
-// PREC = 0: exact fp32 MFMA.  PREC = 1 / 2: three- / six-term split-bf16 main loop on the pre-split weight planes Whi / Wlo (/ Wl2).
+// PREC (an Arith, FP32..BF16X6) = FP32: exact fp32 MFMA.  BF16X3 / BF16X6: three- / six-term split-bf16 main loop on the pre-split weight planes Whi / Wlo (/ Wl2).
 // (forcing 80 VGPRs so that three 8-wave workgroups fit a CU -- the 756 tiles of the headline shape then fit 768 slots in one
 // round -- was measured: kernel -2 %, frames/s in flight unchanged; not kept)
 // DS: the Q tiles leave straight from the accumulators (store_tile_regs) instead of through an LDS staging tile
 // QF: quarter-fragment main loop (gemm_f32_mfma.h; fp32 arithmetic only)
 template <class T, int PREC = 0, int BT = 0, int DS = 0, int QF = 0>
-__global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel(const float* __restrict__ Wqkv, const float* __restrict__ bqkv,
+__global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void qkv_kv_kernel(const float* __restrict__ Wqkv, const float* __restrict__ bqkv,
                                                             const unsigned short* __restrict__ Whi,
                                                             const unsigned short* __restrict__ Wlo,
                                                             const unsigned short* __restrict__ Wl2,
                                                             const float* __restrict__ Z, float* __restrict__ Qbuf,
                                                             float* __restrict__ kvpart, ColLayout L) {
-    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6 (the fp16 modes: qkv_kv_sp_kernel)");
+    static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: qkv_kv_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
     if (!xcd_tile_map(6, active_tiles(L), rt, ct)) return;
@@ -65,19 +65,19 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel
     if constexpr (BT) {
         static_assert(T::BM == 128 && T::KS == 1, "half a piece of bias values, one wave group");
         if ((tid >> 6) == 0 && lane < 32) glds16(bqkv + rt * 128 + 4 * lane, btab);
-    } else if constexpr (PREC != 2) {
+    } else if constexpr (PREC != BF16X6) {
         load_bias16<T>(bqkv + rt * 128, wm, half, bias);
     }
     f32x16 acc[T::TM][T::TN];
     zero_acc(acc);
-    if constexpr (PREC == 1) {
+    if constexpr (PREC == BF16X3) {
         // weight planes are slab-major ([K/32][rows][32], split_weights_kernel): a 128 x 32 slab is 8 KB of consecutive bytes
         const size_t ro = (size_t)rt * 128 * BK;
         auto ah = [&](int kt) { return Whi + ro + (size_t)kt * 768 * BK; };
         auto alo = [&](int kt) { return Wlo + ro + (size_t)kt * 768 * BK; };
         auto bl = [&](int kt) { return Z + (size_t)kt * BK * ld + c0; };
         gemm_mainloop_bf3<T>(acc, reinterpret_cast<unsigned short*>(smem), D / BK, ah, alo, BK, bl, ld);
-    } else if constexpr (PREC == 2) {
+    } else if constexpr (PREC == BF16X6) {
         const size_t ro = (size_t)rt * 128 * BK;
         gemm_mainloop_bf6<T>(
             acc, reinterpret_cast<unsigned short*>(smem), D / BK,
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void qkv_kv_kernel
         gemm_mainloop<T, decltype(al), decltype(bl), IdentityCol, NoHooks, QF>(acc, smem, D / BK, al, D, bl, ld);
     }
     if constexpr (BT) read_bias16<T>(btab, wm, half, bias);
-    else if constexpr (PREC == 2) load_bias16<T>(bqkv + rt * 128, wm, half, bias);
+    else if constexpr (PREC == BF16X6) load_bias16<T>(bqkv + rt * 128, wm, half, bias);
 
     if (rt < 2) {
 #pragma unroll
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
     __shared__ float opsum[16];      // per wave: sum over its tiles of the tile's largest key-sum bound (bound data, slots 0..3)
     __shared__ float opmax[16];      // per wave: max |V| over the source segment's tiles (slots 4..7)
     constexpr int KVF_ROWS = 512 / KVF_RS;
-    if (prec >= 3) fp16_saturate_mode();
+    if (prec >= FP16X3) fp16_saturate_mode();
     const int tid = threadIdx.x;
     const int el = tid & 63, part = tid >> 6;
     const bool ksum_block = blockIdx.x == 16 * KVF_RS;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
     // the bound data of the source's tiles (requested in front of the reduction's loads, consumed behind them); computed in EVERY arithmetic:
     // the ksum block stores the reduced slots with kvfin, and a cache prepared in fp32 must serve the fp16 modes
     float ksb = 0.f, vmx = 0.f;   // ksb: sum over the tiles of the tile's largest key-sum bound (>= max_w sum_tiles slot_w >= max_d ksum[d])
-    const bool need_bound = prec >= 3 || ksum_block;   // (block-uniform) fp32 / bf16 launches: only the block that stores kvfin reduces it
+    const bool need_bound = prec >= FP16X3 || ksum_block;   // (block-uniform) fp32 / bf16 launches: only the block that stores kvfin reduces it
     if (need_bound)
     for (int t = tid; t < nt; t += 1024) {
         const float4* mp = reinterpret_cast<const float4*>(base + (size_t)t * H * KVP) + MAX4;
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
         }
     }
     float mscale = 1.f, zfold = 1.f;
-    if (prec >= 3) {
+    if (prec >= FP16X3) {
         (void)nsrc;
         const float bound = sc[4 + h] * ksb * vmx;
         int e = 0;
@@ -378,14 +378,14 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
     const float o0 = qq ? acc[1][0] : acc[0][0], o1 = qq ? acc[1][1] : acc[0][1], o2 = qq ? acc[1][2] : acc[0][2],
                 o3 = qq ? acc[1][3] : acc[0][3];
     const int c = h * DH + 4 * db;   // first of this block's 4 columns of M_t
-    if (prec == 0) {
+    if (!needs_operator_planes(Arith(prec))) {
         vf4 v = {o0, o1, o2, o3};
         // (write-through / non-temporal forms of this store -- sc1, sc0 sc1, nt -- were A/B-timed: no difference)
         *reinterpret_cast<vf4*>(mop_seg(Mop, tseg) + (size_t)row * MOP_LD + c) = v;
     } else {
         // split planes in the slab-major layout of the weight planes: (m, k) at ((k / 32) * 512 + m) * 32 + k % 32
         unsigned p0a, p1a, p2a = 0, p0b, p1b, p2b = 0;
-        if (prec >= 3) {   // fp16 terms of the scaled operator
+        if (prec >= FP16X3) {   // fp16 terms of the scaled operator
             fp16_split2(o0 * mscale, o1 * mscale, p0a, p1a);
             fp16_split2(o2 * mscale, o3 * mscale, p0b, p1b);
         } else {
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
         unsigned short* pl = Mpl + (size_t)tseg * 3 * MPL_PLANE + ((size_t)(c >> 5) * 512 + row) * 32 + (c & 31);
         *reinterpret_cast<u32x2*>(pl) = (u32x2){p0a, p0b};
         *reinterpret_cast<u32x2*>(pl + MPL_PLANE) = (u32x2){p1a, p1b};
-        if (prec == 2) *reinterpret_cast<u32x2*>(pl + 2 * MPL_PLANE) = (u32x2){p2a, p2b};
+        if (prec == BF16X6) *reinterpret_cast<u32x2*>(pl + 2 * MPL_PLANE) = (u32x2){p2a, p2b};
     }
 }
 
@@ -427,7 +427,7 @@ static constexpr unsigned long long* g_trace = nullptr;
 // SF: the fused InstanceNorm reducer (stat_last_block) is compiled in, never taken (statcnt = nullptr; the retired STAT_FUSED form).  Only
 //     the split-bf16 instantiations keep it, to keep their code (launch_mlp0_t); in fp32 its 64 staging registers set the count (118 of 126).
 template <class T, int PREC = 0, int BT = 0, int QF = 0, int SF = 0>
-__global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void mlp0_kernel(const float* __restrict__ W0, const float* __restrict__ b0,
+__global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1)) void mlp0_kernel(const float* __restrict__ W0, const float* __restrict__ b0,
                                                    const unsigned short* __restrict__ Whi, const unsigned short* __restrict__ Wlo,
                                                    const unsigned short* __restrict__ Wl2,
                                                    const float* __restrict__ Z, const float* __restrict__ Qbuf,
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
                                                    const float* __restrict__ ksumT,
                                                    float* __restrict__ U, float* __restrict__ statpart, float* __restrict__ stats,
                                                    int* __restrict__ statcnt, ColLayout L, unsigned long long* trace) {
-    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp0_sp_kernel)");
+    static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp0_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const unsigned long long t_entry = trace ? wall_clock64() : 0;
     const unsigned long long c_entry = trace ? clock64() : 0;
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
     if constexpr (BT) {
         static_assert(T::BM == 128 && T::KS == 1, "half a piece of bias values, one wave group");
         if ((tid >> 6) == 0 && lane < 32) glds16(b0 + rt * T::BM + 4 * lane, btab);
-    } else if constexpr (PREC < 2) {
+    } else if constexpr (PREC < BF16X6) {
         load_bias16<T>(b0 + rt * T::BM, wm, half, bias);
     }
     f32x16 acc[T::TM][T::TN];
@@ -468,14 +468,14 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
     auto bl = [&](int kt) { return (kt < 8 ? Z + (size_t)kt * BK * ld : Qbuf + (size_t)(kt - 8) * BK * ld) + c0; };
     AttnFoldHooks hooks;
     hooks.init(ksumT + (size_t)ts.seg * H * DH, smem + smem_floats_mainloop<T, PREC>(), wn);
-    if constexpr (PREC == 1) {
+    if constexpr (PREC == BF16X3) {
         const size_t ro = (size_t)rt * T::BM * BK;   // slab-major planes (see qkv_kv_kernel); M_t planes in the same layout
         const unsigned short* Mh = Mpl + (size_t)ts.seg * 3 * MPL_PLANE + ro;
         auto ah = [&](int kt) { return kt < 8 ? Whi + ro + (size_t)kt * 512 * BK : Mh + (size_t)(kt - 8) * 512 * BK; };
         auto alo = [&](int kt) { return kt < 8 ? Wlo + ro + (size_t)kt * 512 * BK : Mh + MPL_PLANE + (size_t)(kt - 8) * 512 * BK; };
         gemm_mainloop_bf3<T, decltype(ah), decltype(alo), decltype(bl), AttnFoldHooks>(acc, reinterpret_cast<unsigned short*>(smem), 512 / BK, ah,
                                                                                        alo, BK, bl, ld, &hooks);
-    } else if constexpr (PREC == 2) {
+    } else if constexpr (PREC == BF16X6) {
         const size_t ro = (size_t)rt * T::BM * BK;
         const unsigned short* Mh = Mpl + (size_t)ts.seg * 3 * MPL_PLANE + ro;
         gemm_mainloop_bf6<T>(
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= 2 ? 4 : 1)) void
     acc[0][0] = hooks.kept;
     ksplit_reduce<T>(acc, smem);
     if constexpr (BT) read_bias16<T>(btab, wm, half, bias);
-    else if constexpr (PREC == 2) load_bias16<T>(b0 + rt * T::BM, wm, half, bias);
+    else if constexpr (PREC == BF16X6) load_bias16<T>(b0 + rt * T::BM, wm, half, bias);
     const unsigned long long t_loop = trace ? wall_clock64() : 0;
     constexpr int TS = T::BN + 1;
     float* Tl = smem;  // [BM][BN + 1]
@@ -603,12 +603,12 @@ using Mlp3TileS = GemmTile<64, 64, 2, 2, false, false, 2>;   // fp32, launches t
 
 // DS: the output tile leaves straight from the accumulators (store_tile_regs; plain 128 x 64 / 64 x 64 tiles, not the K-split one)
 template <class T, int PREC = 0, int DS = 0>
-__global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void mlp3_kernel(const float* __restrict__ W3, const float* __restrict__ b3,
+__global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void mlp3_kernel(const float* __restrict__ W3, const float* __restrict__ b3,
                                                    const unsigned short* __restrict__ Whi, const unsigned short* __restrict__ Wlo,
                                                    const unsigned short* __restrict__ Wl2,
                                                    const float* __restrict__ U, const float* __restrict__ stats,
                                                    float* __restrict__ Z, ColLayout L) {
-    static_assert(PREC >= 0 && PREC <= 2, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp3_sp_kernel)");
+    static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp3_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
     constexpr int MT = 256 / T::BM;
@@ -642,14 +642,14 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void mlp3_kernel(c
     auto bl = [&](int kt) { return U + (size_t)kt * BK * ld + c0; };
     auto xm = [&](int kt) { return mean + kt * BK; };
     auto xr = [&](int kt) { return rstd + kt * BK; };
-    if constexpr (PREC == 1) {
+    if constexpr (PREC == BF16X3) {
         const size_t ro = (size_t)rt * T::BM * BK;   // slab-major planes (see qkv_kv_kernel)
         auto ah = [&](int kt) { return Whi + ro + (size_t)kt * 256 * BK; };
         auto alo = [&](int kt) { return Wlo + ro + (size_t)kt * 256 * BK; };
         auto bx1 = [](float v, float2 ms) { return fmaxf((v - ms.x) * ms.y, 0.f); };
         gemm_mainloop_bf3_ex<T, decltype(ah), decltype(alo), decltype(bl), decltype(xm), decltype(xr), decltype(bx1), true>(
             acc, reinterpret_cast<unsigned short*>(smem), 512 / BK, ah, alo, BK, bl, ld, xm, xr, bx1);
-    } else if constexpr (PREC == 2) {
+    } else if constexpr (PREC == BF16X6) {
         const size_t ro = (size_t)rt * T::BM * BK;
         auto ap = [&](int kt, int pl) { return (pl == 0 ? Whi : pl == 1 ? Wlo : Wl2) + ro + (size_t)kt * 256 * BK; };
         auto bx1 = [](float v, float2 ms) { return fmaxf((v - ms.x) * ms.y, 0.f); };
@@ -676,14 +676,14 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= 2 ? 4 : 1)) void mlp3_kernel(c
 // =====================================================================================================
 using FinalTile = GemmTile<256, 32, 8, 1, false>;   // 8 waves x one 32x32 tile (4 waves x 64x32 left one wave per SIMD: 15.0 us)
 
-// planes_prec: 0, or the arithmetic (2 bf16x6 / 4 fp16x4) whose 16-bit planes of the query descriptors (MDTp, slab-major over all b * n1p
+// planes_prec: 0, or the arithmetic (BF16X6 / FP16X4) whose 16-bit planes of the query descriptors (MDTp, slab-major over all b * n1p
 // rows; fp16: of 2^SCORE_SPLIT_SCALE_LOG2 x) the split score contraction reads as its A operand
 __global__ __launch_bounds__(FinalTile::THREADS) void final_proj_norm_kernel(const float* __restrict__ Wf, const float* __restrict__ bf,
                                                               const float* __restrict__ Z, float* __restrict__ MD,
                                                               float* __restrict__ MDT, unsigned short* __restrict__ MDTp,
                                                               int planes_prec, ColLayout L) {
     using T = FinalTile;
-    if (planes_prec >= 3) fp16_saturate_mode();
+    if (planes_prec >= FP16X3) fp16_saturate_mode();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ float npart[T::WM][32];
     const int ct = blockIdx.x;
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(FinalTile::THREADS) void final_proj_norm_kernel(con
             // ((k / 32) * R + m) * 32 + k % 32, R = b * n1p rows
             const size_t R = (size_t)L.b * L.n1p;
             const size_t m0 = (size_t)ts.frame * L.n1p + (c0 - ts.seg_start);
-            const float sc = planes_prec >= 3 ? (float)(1 << SCORE_SPLIT_SCALE_LOG2) : 1.f;
+            const float sc = planes_prec >= FP16X3 ? (float)(1 << SCORE_SPLIT_SCALE_LOG2) : 1.f;
 #pragma unroll
             for (int idx = tid; idx < 32 * 32; idx += T::THREADS) {
                 const int pt = idx >> 5, slab = (idx >> 2) & 7, q = idx & 3;
@@ -746,13 +746,13 @@ __global__ __launch_bounds__(FinalTile::THREADS) void final_proj_norm_kernel(con
                 unsigned p0[4], p1[4], p2[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    if (planes_prec >= 3) { fp16_split2(v[2 * e] * sc, v[2 * e + 1] * sc, p0[e], p1[e]); p2[e] = 0; }
+                    if (planes_prec >= FP16X3) { fp16_split2(v[2 * e] * sc, v[2 * e + 1] * sc, p0[e], p1[e]); p2[e] = 0; }
                     else bf16_split3(v[2 * e], v[2 * e + 1], p0[e], p1[e], p2[e]);
                 }
                 unsigned short* d0 = MDTp + ((size_t)slab * R + m0 + pt) * 32 + q * 8;
                 *reinterpret_cast<u32x4*>(d0) = (u32x4){p0[0], p0[1], p0[2], p0[3]};
                 *reinterpret_cast<u32x4*>(d0 + R * D) = (u32x4){p1[0], p1[1], p1[2], p1[3]};
-                if (planes_prec == 2) *reinterpret_cast<u32x4*>(d0 + 2 * R * D) = (u32x4){p2[0], p2[1], p2[2], p2[3]};
+                if (planes_prec == BF16X6) *reinterpret_cast<u32x4*>(d0 + 2 * R * D) = (u32x4){p2[0], p2[1], p2[2], p2[3]};
             }
         }
     }
@@ -928,39 +928,32 @@ static int diet_min_tiles() { return tuning_knob("DIET_MIN_TILES", DIET_MIN_TILE
 //  per frame (profiles/r04_ab_live_fp32_dma.txt))
 
 template <class T, int PREC, int BT = 0, int DS = 0, int QF = 0>
-static void launch_qkv_t(const float* Wqkv, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s,
-                         ProfileHook* hk) {
+static void launch_qkv_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const int NT = active_tiles(w.L);
+    const WPlanes p = a.qkv_planes();
     allow_big_lds<qkv_kv_kernel<T, PREC, BT, DS, QF>>();
     GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_kernel<T, PREC, BT, DS, QF>), dim3(xcd_grid(6, NT)), dim3(T::THREADS), (smem_bytes<T, PREC>() + 512 * BT), s,
-                   Wqkv, bqkv, wb ? wb + AttnWB::QKV_HI : nullptr,
-                   wb ? wb + AttnWB::QKV_LO : nullptr, wb ? wb + AttnWB::QKV_LO2 : nullptr, w.Z,
-                   w.Q, w.kvpart, w.L);
+                   a.WQKV(), a.BQKV(), p.hi, p.lo, p.lo2, w.Z, w.Q, w.kvpart, w.L);
 }
 
 // The fp16 modes run on the LDS-DMA loop (their planes carry the pack-time scale that only those kernels undo); the bf16 modes stay on the
 // first form.  (The bf16 modes on the LDS-DMA loop, A/B-timed on one box, profiles/r04_split_loop_ab.txt: bf16x3 1866 vs 1842 frames/s in
 // flight, bf16x6 1397 vs 1285 -- the three-plane stage makes the DMA loop 1.5x the LDS traffic; removed.)
-void launch_qkv_kv(const float* Wqkv, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s,
-                   ProfileHook* hk) {
-    if (w.prec >= 3) {
-        // Wqkv is the first member of the layer's AttnW block: its scales sit at AttnW::SC from there
-        launch_qkv_kv_sp(Wqkv - AttnW::WQKV + AttnW::SC, bqkv, wb, w, s, hk);
-        return;
-    }
-    if (w.prec == 1) launch_qkv_t<QkvTileW8, 1>(Wqkv, bqkv, wb, w, s, hk);
-    else if (w.prec == 2) launch_qkv_t<QkvTileW8, 2>(Wqkv, bqkv, wb, w, s, hk);
-    else if (active_tiles(w.L) > diet_min_tiles()) launch_qkv_t<QkvTileW8, 0, 1, 1, 1>(Wqkv, bqkv, wb, w, s, hk);   // quarter fragments + bias table (80 VGPRs)
-    else launch_qkv_t<QkvTileW8, 0, 0, 1>(Wqkv, bqkv, wb, w, s, hk);   // small launches: the two-half fragment loop
+void launch_qkv_kv(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    if (is_fp16(w.prec)) launch_qkv_kv_sp(a, w, s, hk);
+    else if (w.prec == BF16X3) launch_qkv_t<QkvTileW8, BF16X3>(a, w, s, hk);
+    else if (w.prec == BF16X6) launch_qkv_t<QkvTileW8, BF16X6>(a, w, s, hk);
+    else if (active_tiles(w.L) > diet_min_tiles()) launch_qkv_t<QkvTileW8, FP32, 1, 1, 1>(a, w, s, hk);   // quarter fragments + bias table (80 VGPRs)
+    else launch_qkv_t<QkvTileW8, FP32, 0, 1>(a, w, s, hk);   // small launches: the two-half fragment loop
 }
 
-void launch_kv_final(const float* W0, const Workspace& w, int cross, const float* kv_src, hipStream_t s, ProfileHook* hk) {
+void launch_kv_final(const AttnLayer& a, const Workspace& w, int cross, const float* kv_src, hipStream_t s, ProfileHook* hk) {
     // one workgroup per d block since round 4: every partial read once (interleaved A/B, profiles/r04_ab_live_kv_final.txt: kernel
     // 11.4 -> 10.5 us event-timed, +0.7 ... +1.6 % frames/s in flight at the three shapes, bit-identical results; the two-row-part form is removed).
     // (round 6: the projection split in two launches so that kv_final runs beside the Q tiles -- 1264 vs 1266 frames/s in flight,
     //  profiles/r06e_*, r06f_* -- and a narrow 512-thread form -- 11.85 vs 11.22 us, profiles/r06c_ab_live_kvf_narrow_*.txt -- both removed)
-    GATSSPG_LAUNCH(hk, KID_KV_FINAL, s, kv_final_kernel<1>, dim3(17, w.nseg * H), dim3(1024), 0, s, w.kvpart, kv_src, w.kvfin, W0, w.Mop, w.Mpl,
-                   w.ksumT, w.zsc, w.statcnt, W0 - AttnW::W0 + AttnW::SC, w.L, cross, w.prec, 0);
+    GATSSPG_LAUNCH(hk, KID_KV_FINAL, s, kv_final_kernel<1>, dim3(17, w.nseg * H), dim3(1024), 0, s, w.kvpart, kv_src, w.kvfin, a.W0(), w.Mop, w.Mpl,
+                   w.ksumT, w.zsc, w.statcnt, a.SC(), w.L, cross, (int)w.prec, 0);
 }
 
 // SF: the fused InstanceNorm reducer (stat_last_block) compiled in as a branch that never runs (statcnt = nullptr).  The split-bf16
@@ -968,53 +961,46 @@ void launch_kv_final(const float* W0, const Workspace& w, int cross, const float
 // 12-byte spill -- they stay exactly the round-5 kernels.  (Finishing the statistics in the last workgroups instead of the stat_final launch:
 // 1231 vs 1232 frames/s in flight, 5.3 us longer mlp0 for the 4.8 us launch it saves, profiles/r04_stat_fused_ab.txt; removed.)
 template <class T, int PREC, int BT = 0, int QF = 0>
-static void launch_mlp0_t(const float* W0, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s,
-                          ProfileHook* hk) {
-    constexpr int SF = PREC != 0;
+static void launch_mlp0_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    constexpr int SF = PREC != FP32;
+    const WPlanes p = a.w0_planes();
     allow_big_lds<mlp0_kernel<T, PREC, BT, QF, SF>>();
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
     GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, PREC, BT, QF, SF>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS),
-                   (smem_bytes<T, PREC>() + sizeof(float) * AttnFoldHooks::ZP_FLOATS + 512 * BT), s, W0, b0,
-                   wb ? wb + AttnWB::W0_HI : nullptr, wb ? wb + AttnWB::W0_LO : nullptr,
-                   wb ? wb + AttnWB::W0_LO2 : nullptr, w.Z, w.Q, w.Mop, w.Mpl, w.ksumT, w.U,
-                   w.statpart, w.stats, nullptr, w.L, g_trace);
+                   (smem_bytes<T, PREC>() + sizeof(float) * AttnFoldHooks::ZP_FLOATS + 512 * BT), s, a.W0(), a.B0(), p.hi, p.lo, p.lo2, w.Z, w.Q,
+                   w.Mop, w.Mpl, w.ksumT, w.U, w.statpart, w.stats, nullptr, w.L, g_trace);
 }
 template <class T, int PREC, int DS = 0>
-static void launch_mlp3_t(const float* W3, const float* b3, const unsigned short* wb, const Workspace& w, hipStream_t s,
-                          ProfileHook* hk) {
+static void launch_mlp3_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    const WPlanes p = a.w3_planes();
     allow_big_lds<mlp3_kernel<T, PREC, DS>>();
     const int NT = active_tiles(w.L) / (T::BN / 64);
     GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, PREC, DS>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS),
-                   (smem_bytes<T, PREC>()), s, W3, b3, wb ? wb + AttnWB::W3_HI : nullptr,
-                   wb ? wb + AttnWB::W3_LO : nullptr, wb ? wb + AttnWB::W3_LO2 : nullptr, w.U,
-                   w.stats, w.Z, w.L);
+                   (smem_bytes<T, PREC>()), s, a.W3(), a.B3(), p.hi, p.lo, p.lo2, w.U, w.stats, w.Z, w.L);
 }
 
-void launch_mlp(const float* W0, const float* b0, const float* W3, const float* b3, const unsigned short* wb, const Workspace& w,
-                hipStream_t s, ProfileHook* hk) {
+void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     // (profiling ablations of the fp32 main loop -- no global loads, no LDS writes, cache-hot panels, L1-hot loads, the loop cut to its
     //  fixed cost -- were timed in round 5, profiles/r05d_trace_mlp0_*; removed)
     static const int small_nt3 = tuning_knob("SMALL_NT3", SMALL_NT3);
-    const bool sp = w.prec >= 3;
-    const float* sc = W0 - AttnW::W0 + AttnW::SC;
-    if (sp) launch_mlp0_sp(sc, b0, wb, w, s, hk);
-    else if (w.prec == 1) launch_mlp0_t<Mlp0TileW8, 1>(W0, b0, wb, w, s, hk);
-    else if (w.prec == 2) launch_mlp0_t<Mlp0TileW8, 2>(W0, b0, wb, w, s, hk);
-    else if (active_tiles(w.L) > diet_min_tiles()) launch_mlp0_t<Mlp0TileW8, 0, 1, 1>(W0, b0, wb, w, s, hk);   // quarter fragments + bias table (94 VGPRs)
-    else launch_mlp0_t<Mlp0TileW8, 0>(W0, b0, wb, w, s, hk);   // small launches: the two-half fragment loop (126 VGPRs)
+    if (is_fp16(w.prec)) launch_mlp0_sp(a, w, s, hk);
+    else if (w.prec == BF16X3) launch_mlp0_t<Mlp0TileW8, BF16X3>(a, w, s, hk);
+    else if (w.prec == BF16X6) launch_mlp0_t<Mlp0TileW8, BF16X6>(a, w, s, hk);
+    else if (active_tiles(w.L) > diet_min_tiles()) launch_mlp0_t<Mlp0TileW8, FP32, 1, 1>(a, w, s, hk);   // quarter fragments + bias table (94 VGPRs)
+    else launch_mlp0_t<Mlp0TileW8, FP32>(a, w, s, hk);   // small launches: the two-half fragment loop (126 VGPRs)
     // the InstanceNorm reducer is a launch of its own (see launch_mlp0_t)
     GATSSPG_LAUNCH(hk, KID_STAT_FINAL, s, stat_final_kernel<MLP0_BN>, dim3(w.nseg, 8), dim3(1024), 0, s, w.statpart, w.stats, w.L);
-    if (sp) launch_mlp3_sp(sc, b3, wb, w, s, hk);
-    else if (w.prec == 1) launch_mlp3_t<Mlp3TileTallW8, 1>(W3, b3, wb, w, s, hk);
-    else if (w.prec == 2) launch_mlp3_t<Mlp3TileTallW8, 2>(W3, b3, wb, w, s, hk);
-    else if (active_tiles(w.L) <= small_nt3) launch_mlp3_t<Mlp3TileS, 0>(W3, b3, wb, w, s, hk);
-    else launch_mlp3_t<Mlp3TileTallW8, 0, 1>(W3, b3, wb, w, s, hk);
+    if (is_fp16(w.prec)) launch_mlp3_sp(a, w, s, hk);
+    else if (w.prec == BF16X3) launch_mlp3_t<Mlp3TileTallW8, BF16X3>(a, w, s, hk);
+    else if (w.prec == BF16X6) launch_mlp3_t<Mlp3TileTallW8, BF16X6>(a, w, s, hk);
+    else if (active_tiles(w.L) <= small_nt3) launch_mlp3_t<Mlp3TileS, FP32>(a, w, s, hk);
+    else launch_mlp3_t<Mlp3TileTallW8, FP32, 1>(a, w, s, hk);
 }
 
 void launch_final_proj_norm(const float* Wf, const float* bf, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     allow_big_lds<final_proj_norm_kernel>();
     GATSSPG_LAUNCH(hk, KID_FINAL_PROJ, s, final_proj_norm_kernel, dim3(w.L.ld / FinalTile::BN), dim3(FinalTile::THREADS),
-                   (smem_bytes<FinalTile>()), s, Wf, bf, w.Z, w.MD, w.MDT, w.MDTp, score_on_split_loop(w.prec, 0) ? w.prec : 0, w.L);
+                   (smem_bytes<FinalTile>()), s, Wf, bf, w.Z, w.MD, w.MDT, w.MDTp, score_on_split_loop(w.prec, 0) ? (int)w.prec : 0, w.L);
 }
 
 int score_tile_rows() { return SC_BM; }
@@ -1031,7 +1017,7 @@ static void launch_score_t(const Workspace& w, float* conf, float scale, hipStre
 // The fp32-class split modes (bf16x6: operands split exactly; fp16x4: the exact product of 22-bit operands) also run the score
 // contraction on the 16-bit pipe; the three-term modes keep the fp32 MFMA here (their 2^-16 / dropped-term error would sit directly on
 // the logits of the dual softmax).  The max-subtracting path (tiny scale factors) stays fp32 as well.  (profiles/r04_score_split_ab.txt)
-bool score_on_split_loop(int prec, int shifted) { return !shifted && (prec == 2 || prec == 4); }
+bool score_on_split_loop(Arith prec, int shifted) { return !shifted && (prec == BF16X6 || prec == FP16X4); }
 
 void launch_score_exp(const Workspace& w, float* conf, float scale, int shifted, hipStream_t s, ProfileHook* hk) {
     if (score_on_split_loop(w.prec, shifted)) return launch_score_exp_sp(w, conf, scale, s, hk);
@@ -1039,9 +1025,9 @@ void launch_score_exp(const Workspace& w, float* conf, float scale, int shifted,
     else launch_score_t<ScoreTileW8, false>(w, conf, scale, s, hk);
 }
 
-void launch_gats_wlt(const float* W, const float* P, const Workspace& w, int add_h, hipStream_t s, ProfileHook* hk) {
+void launch_gats_wlt(const GatsLayer& g, const float* P, const Workspace& w, int add_h, hipStream_t s, ProfileHook* hk) {
     const int NT = w.L.ld / WltTile::BN;
-    GATSSPG_LAUNCH(hk, KID_GATS_WLT, s, gats_wlt_kernel, dim3(xcd_grid(4, NT)), dim3(256), (smem_bytes<WltTile>()), s, W, P, w.Z,
+    GATSSPG_LAUNCH(hk, KID_GATS_WLT, s, gats_wlt_kernel, dim3(xcd_grid(4, NT)), dim3(256), (smem_bytes<WltTile>()), s, g.W(), P, w.Z,
                    w.L, add_h);
 }
 

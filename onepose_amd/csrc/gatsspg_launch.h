@@ -58,22 +58,19 @@ void allow_big_lds() {
 #ifdef GATSSPG_PROFILING_BUILD
 extern unsigned long long* g_trace;  // per-workgroup timeline buffer of mlp0_kernel (nullptr = off)
 #endif
-// packedb: the split-bf16 weight planes of this layer (AttnWB offsets), used when w.prec == 1
-void launch_qkv_kv(const float* Wqkv, const float* bqkv, const unsigned short* packedb, const Workspace& w, hipStream_t s,
-                   ProfileHook* hk = nullptr);
+void launch_qkv_kv(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);   // a: attn_layer(packed, layer)
 // KV / ksum sums of every active SOURCE segment + the message operators M_t of their TARGET segments (cross: the other side of
-// the frame) for mlp.0.  W0: the layer's packed mlp.0 operator [512][512].  kv_src: nullptr, or (amortised mode) the cached final
-// KV sums [b][4][KVP] of the 3D-side sources, used instead of the partials.
-void launch_kv_final(const float* W0, const Workspace& w, int cross, const float* kv_src, hipStream_t s, ProfileHook* hk = nullptr);
-void launch_mlp(const float* W0, const float* b0, const float* W3, const float* b3, const unsigned short* packedb,
-                const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
-// gatsspg_split_kernels.hip: the same three GEMMs on the LDS-DMA split-16-bit loop (gemm_split_glds.h); sc = the layer's AttnW::SC
-void launch_qkv_kv_sp(const float* sc, const float* bqkv, const unsigned short* packedb, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
-void launch_mlp0_sp(const float* sc, const float* b0, const unsigned short* packedb, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
-void launch_mlp3_sp(const float* sc, const float* b3, const unsigned short* packedb, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
+// the frame) for mlp.0.  kv_src: nullptr, or (amortised mode) the cached final KV sums [b][4][KVP] of the 3D-side sources, used
+// instead of the partials.
+void launch_kv_final(const AttnLayer& a, const Workspace& w, int cross, const float* kv_src, hipStream_t s, ProfileHook* hk = nullptr);
+void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
+// gatsspg_split_kernels.hip: the same three GEMMs on the LDS-DMA split-16-bit loop (gemm_split_glds.h), for is_fp16(w.prec)
+void launch_qkv_kv_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
+void launch_mlp0_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
+void launch_mlp3_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
 // score contraction + exp on the split loop (fp32-class modes only: bf16x6, fp16x4): A = the 16-bit planes of the query descriptors
 // written by final_proj_norm_kernel (w.MDTp), B = the fp32 3D descriptors.  Same outputs and partial layout as launch_score_exp.
-bool score_on_split_loop(int prec, int shifted);
+bool score_on_split_loop(Arith prec, int shifted);
 void launch_score_exp_sp(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk = nullptr);
 constexpr int SCORE_SPLIT_SCALE_LOG2 = 10;   // unit-norm descriptors (|x| <= 1) are multiplied by 2^10 before the fp16 split
 void launch_final_proj_norm(const float* Wf, const float* bf, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
@@ -81,7 +78,7 @@ void launch_final_proj_norm(const float* Wf, const float* bf, const Workspace& w
 void launch_score_exp(const Workspace& w, float* conf, float scale, int shifted, hipStream_t s, ProfileHook* hk = nullptr);
 int score_tile_rows();   // rows / columns of a score tile = what one column / row partial sums over (conf_finalize needs the counts)
 int score_tile_cols();
-void launch_gats_wlt(const float* W, const float* P, const Workspace& w, int add_h, hipStream_t s, ProfileHook* hk = nullptr);
+void launch_gats_wlt(const GatsLayer& g, const float* P, const Workspace& w, int add_h, hipStream_t s, ProfileHook* hk = nullptr);
 void launch_split_weights(float* packed, unsigned short* packedb, hipStream_t s);   // also writes the fp16 plane scales (AttnW::SC) into `packed`
 
 // gatsspg_stream_kernels.hip
@@ -91,19 +88,17 @@ void launch_load_columns(const float* c2, const float* c3, float* dst, const Wor
 void launch_store_state(const float* src, float* out2d, float* out3d, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
 // h3: where the layer reads the 3D-point descriptors from: nullptr = the state Z; otherwise the caller's compact
 // [b,256,n2] tensor (first layer of a forward: the state load is fused, `dq` is copied into the 2D side by spare workgroups)
-void launch_gats(const float* u1, const float* u2, const float* leaves, int num_leaf, int flags, float* dst,
-                 const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr, const float* h3 = nullptr,
-                 const float* dq = nullptr, const float* cached_logits = nullptr);
+void launch_gats(const GatsLayer& g, const float* leaves, int num_leaf, int flags, float* dst, const Workspace& w, hipStream_t s,
+                 ProfileHook* hk = nullptr, const float* h3 = nullptr, const float* dq = nullptr, const float* cached_logits = nullptr);
 // per-object cache of the leaf logits (amortised mode): [nlayers][b][tiles][32] floats, gats_leaf_logit_floats per layer;
 // launch_gats(..., cached_logits = that layer's block) then skips the leaf . u1 products
 bool gats_caches_leaf_logits(int num_leaf, int flags);
 size_t gats_leaf_logit_floats(int b, int n2);
-void launch_gats_leaf_logits(const float* u1_first, int u1_stride, int nlayers, const float* leaves, float* cl,
-                             const Workspace& w, hipStream_t s);
+void launch_gats_leaf_logits(const GatsLayer& first, int nlayers, const float* leaves, float* cl, const Workspace& w, hipStream_t s);   // first of nlayers consecutive layers
 // true if launch_gats can take h3 / dq for this configuration (fused state load)
 bool gats_fuses_state_load(int num_leaf, int flags, const Workspace& w);
-void launch_dual_softmax_match(const Workspace& w, float* conf, float scale, int shifted, float match_threshold,
-                               int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, hipStream_t s,
+struct MatchOut { float* conf; int64_t *matches0, *matches1; float *mscores0, *mscores1; };   // the five outputs of a forward (include/gatsspg.h)
+void launch_dual_softmax_match(const Workspace& w, const MatchOut& out, int shifted, float match_threshold, hipStream_t s,
                                ProfileHook* hk = nullptr);
 void launch_pack_weights(const void* raw_struct_host, float* packed, hipStream_t s);
 size_t kenc_scratch_bytes(int b, int n);

@@ -1,6 +1,6 @@
 // The three big GEMMs of an attention layer on the split-16-bit main loop of gemm_split_glds.h (round 4): qkv_kv, mlp.0 (merge and
-// the linear-attention apply folded in) and mlp.3, for the arithmetics GATSSPG_FLAG_PREC_FP16X4 / _FP16X3 (always) and _BF16X3 /
-// _BF16X6.  Same maths, same buffers and the same epilogues (gatsspg_epilogue.h) as the fp32 kernels of gatsspg_gemm_kernels.hip
+// the linear-attention apply folded in) and mlp.3, for the fp16 arithmetics (FP16X3 / FP16X4); the score contraction of BF16X6 and
+// FP16X4 runs on the same loop.  Same maths, same buffers and the same epilogues (gatsspg_epilogue.h) as the fp32 kernels of gatsspg_gemm_kernels.hip
 // (GATs_SuperGlue.py:69-128); what differs is how the operands reach the matrix pipe.
 #include "gemm_split_glds.h"
 #include "gatsspg_epilogue.h"
@@ -450,8 +450,8 @@ static void launch_score_sp_t(const Workspace& w, float* conf, float scale, hipS
                    (size_t)T::RING_BYTES, s, w.MDTp, w.MD, conf, w.rowpart, w.colpart, w.L, scale);
 }
 void launch_score_exp_sp(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk) {
-    if (w.prec == 2) launch_score_sp_t<2>(w, conf, scale, s, hk);
-    else launch_score_sp_t<4>(w, conf, scale, s, hk);
+    if (w.prec == BF16X6) launch_score_sp_t<BF16X6>(w, conf, scale, s, hk);
+    else launch_score_sp_t<FP16X4>(w, conf, scale, s, hk);
 }
 
 // The product runs the fp16 modes on the slot schedule (SCHED 4, gemm_split_glds.h) with the bias through an LDS table and the Q / mlp3 tiles
@@ -475,65 +475,60 @@ static bool mlp0_sp_wide(const ColLayout& L) {
 //  registers instead of 192; and XCD-paired column tiles beside the 128-column mlp0 tile: no effect, 1912 vs 1908.  profiles/r05c_ab_live_ut_xcd_direct.txt;
 //  both removed.  ColLayout::xgs stays 0: the kernels still read it, so that their code is unchanged.)
 
-struct PlaneSet {
-    const unsigned short *p0, *p1;
-};
-static PlaneSet planes(const unsigned short* wb, size_t h16, size_t l16) { return {wb + h16, wb + l16}; }
-
 template <int MODE>
-static void launch_qkv_sp_t(const float* sc, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+static void launch_qkv_sp_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     using T = QkvSpTile<MODE>;
-    const PlaneSet p = planes(wb, AttnWB::QKV_H16, AttnWB::QKV_L16);
+    const WPlanes p = a.qkv_planes();
     allow_big_lds<qkv_kv_sp_kernel<T>>();
     GATSSPG_LAUNCH(hk, KID_QKV_KV, s, qkv_kv_sp_kernel<T>, dim3(xcd_grid(6, active_tiles(w.L))), dim3(T::THREADS), (size_t)T::RING_BYTES + 1024, s,
-                   sc, bqkv, p.p0, p.p1, p.p1, w.Z, w.Q, w.kvpart, w.L);
+                   a.SC(), a.BQKV(), p.h16, p.l16, p.l16, w.Z, w.Q, w.kvpart, w.L);
 }
-void launch_qkv_kv_sp(const float* sc, const float* bqkv, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    if (w.prec == 3) launch_qkv_sp_t<3>(sc, bqkv, wb, w, s, hk);
-    else launch_qkv_sp_t<4>(sc, bqkv, wb, w, s, hk);
+void launch_qkv_kv_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    if (w.prec == FP16X3) launch_qkv_sp_t<FP16X3>(a, w, s, hk);
+    else launch_qkv_sp_t<FP16X4>(a, w, s, hk);
 }
 
 template <class T>
-static void launch_mlp0_sp_t(const float* sc, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    const PlaneSet p = planes(wb, AttnWB::W0_H16, AttnWB::W0_L16);
+static void launch_mlp0_sp_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    const WPlanes p = a.w0_planes();
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
     allow_big_lds<mlp0_sp_kernel<T>>();
-    GATSSPG_LAUNCH(hk, KID_MLP0, s, mlp0_sp_kernel<T>, dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 2048, s, sc, b0,
-                   p.p0, p.p1, p.p1, w.Z, w.Q, w.Mpl, w.ksumT, w.zsc, w.U, w.statpart, w.stats, nullptr, w.L, g_trace);
+    GATSSPG_LAUNCH(hk, KID_MLP0, s, mlp0_sp_kernel<T>, dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 2048, s, a.SC(), a.B0(),
+                   p.h16, p.l16, p.l16, w.Z, w.Q, w.Mpl, w.ksumT, w.zsc, w.U, w.statpart, w.stats, nullptr, w.L, g_trace);
 }
 template <int MODE>
-static void launch_mlp0_sp_m(const float* sc, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    if (mlp0_sp_wide(w.L)) launch_mlp0_sp_t<Mlp0SpTileW<MODE>>(sc, b0, wb, w, s, hk);
-    else launch_mlp0_sp_t<Mlp0SpTileN<MODE>>(sc, b0, wb, w, s, hk);
+static void launch_mlp0_sp_m(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    if (mlp0_sp_wide(w.L)) launch_mlp0_sp_t<Mlp0SpTileW<MODE>>(a, w, s, hk);
+    else launch_mlp0_sp_t<Mlp0SpTileN<MODE>>(a, w, s, hk);
 }
-void launch_mlp0_sp(const float* sc, const float* b0, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    if (w.prec == 3) launch_mlp0_sp_m<3>(sc, b0, wb, w, s, hk);
-    else launch_mlp0_sp_m<4>(sc, b0, wb, w, s, hk);
+void launch_mlp0_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    if (w.prec == FP16X3) launch_mlp0_sp_m<FP16X3>(a, w, s, hk);
+    else launch_mlp0_sp_m<FP16X4>(a, w, s, hk);
 }
 
 template <class T>
-static void launch_mlp3_sp_v(const float* sc, const float* b3, const PlaneSet& p, int NT, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+static void launch_mlp3_sp_v(const AttnLayer& a, int NT, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    const WPlanes p = a.w3_planes();
     allow_big_lds<mlp3_sp_kernel<T>>();
-    GATSSPG_LAUNCH(hk, KID_MLP3, s, mlp3_sp_kernel<T>, dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s, sc, b3,
-                   p.p0, p.p1, p.p1, w.U, w.stats, w.Z, w.L);
+    GATSSPG_LAUNCH(hk, KID_MLP3, s, mlp3_sp_kernel<T>, dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s, a.SC(), a.B3(),
+                   p.h16, p.l16, p.l16, w.U, w.stats, w.Z, w.L);
 }
 template <int MODE>
-static void launch_mlp3_sp_t(const float* sc, const float* b3, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+static void launch_mlp3_sp_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     using T = Mlp3SpTile<MODE>;
     using T2 = Mlp3SpTile2<MODE>;
-    const PlaneSet p = planes(wb, AttnWB::W3_H16, AttnWB::W3_L16);
     const int NT = active_tiles(w.L) / (T::BN / 64);
     // more than one round of the three-stage ring's two workgroups per CU (batched frames, N_3D = 20000): the two-stage ring's three
     // per CU turn 1.46 rounds into one at 8 frames per step (fp16x4-b8: 0.565 vs 0.571 ms per frame, profiles/r04_ab_live_b8_tiles.txt).
     // Tuning builds: GATSSPG_SP_NST2 >= 0 forces the choice (bit 1 = two-stage ring).
     const int nst2 = tuning_knob("SP_NST2", -1);
     const bool two_stage = nst2 >= 0 ? (nst2 & 2) != 0 : (256 / T2::BM) * NT > 512;
-    if (two_stage) launch_mlp3_sp_v<T2>(sc, b3, p, NT, w, s, hk);
-    else launch_mlp3_sp_v<T>(sc, b3, p, NT, w, s, hk);
+    if (two_stage) launch_mlp3_sp_v<T2>(a, NT, w, s, hk);
+    else launch_mlp3_sp_v<T>(a, NT, w, s, hk);
 }
-void launch_mlp3_sp(const float* sc, const float* b3, const unsigned short* wb, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    if (w.prec == 3) launch_mlp3_sp_t<3>(sc, b3, wb, w, s, hk);
-    else launch_mlp3_sp_t<4>(sc, b3, wb, w, s, hk);
+void launch_mlp3_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+    if (w.prec == FP16X3) launch_mlp3_sp_t<FP16X3>(a, w, s, hk);
+    else launch_mlp3_sp_t<FP16X4>(a, w, s, hk);
 }
 
 }  // namespace gatsspg

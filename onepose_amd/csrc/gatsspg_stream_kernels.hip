@@ -398,14 +398,14 @@ bool gats_caches_leaf_logits(int num_leaf, int flags) {
 }
 size_t gats_leaf_logit_floats(int b, int n2) { return (size_t)b * ((n2 + 3) / 4) * 32; }   // per layer
 
-void launch_gats_leaf_logits(const float* u1_first, int u1_stride, int nlayers, const float* leaves, float* cl,
-                             const Workspace& w, hipStream_t s) {
+void launch_gats_leaf_logits(const GatsLayer& first, int nlayers, const float* leaves, float* cl, const Workspace& w, hipStream_t s) {
     const int nt = (w.L.n2 + 3) / 4;
-    hipLaunchKernelGGL(gats_leaf_logits_kernel, dim3(nt, w.L.b), dim3(256), 0, s, u1_first, u1_stride, nlayers, leaves, cl, w.L, nt);
+    hipLaunchKernelGGL(gats_leaf_logits_kernel, dim3(nt, w.L.b), dim3(256), 0, s, first.U1(), (int)GatsW::SIZE, nlayers, leaves, cl, w.L, nt);
 }
 
-void launch_gats(const float* u1, const float* u2, const float* leaves, int num_leaf, int flags, float* dst,
-                 const Workspace& w, hipStream_t s, ProfileHook* hk, const float* h3, const float* dq, const float* cl) {
+void launch_gats(const GatsLayer& g, const float* leaves, int num_leaf, int flags, float* dst, const Workspace& w, hipStream_t s,
+                 ProfileHook* hk, const float* h3, const float* dq, const float* cl) {
+    const float *u1 = g.U1(), *u2 = g.U2();
     const int raw_out = (flags & GATSSPG_FLAG_WITH_LINEAR_TRANSFORM) ? 1 : 0;
     if (num_leaf == 8) {
         const int nt = (w.L.n2 + 3) / 4;
@@ -810,10 +810,9 @@ __global__ __launch_bounds__(256) void softmax_colstat_kernel(const float* __res
     cs[(size_t)f * L.n2p + j] = s;
 }
 
-void launch_dual_softmax_match(const Workspace& w, float* conf, float scale, int shifted, float thr, int64_t* matches0,
-                               int64_t* matches1, float* mscores0, float* mscores1, hipStream_t s, ProfileHook* hk) {
+void launch_dual_softmax_match(const Workspace& w, const MatchOut& out, int shifted, float thr, hipStream_t s, ProfileHook* hk) {
     const ColLayout& L = w.L;
-    (void)scale;
+    float* conf = out.conf;
     const dim3 gf(w.cf_nch, w.cf_nst, L.b);
     const int nrt = (L.n1p + score_tile_rows() - 1) / score_tile_rows();
     const int nct = L.n2p / score_tile_cols();
@@ -837,7 +836,7 @@ void launch_dual_softmax_match(const Workspace& w, float* conf, float scale, int
 #undef GATSSPG_FINALIZE
     const dim3 g1((L.n1p + L.n2p) / MT_ITEMS, L.b);
     GATSSPG_LAUNCH(hk, KID_MATCH_TAIL, s, match_tail_kernel, g1, dim3(256), 0, s, w.rmax_v, w.rmax_i, w.cmax_v, w.cmax_i, thr,
-                   matches0, matches1, mscores0, mscores1, L, w.cf_nch, w.cf_nst);
+                   out.matches0, out.matches1, out.mscores0, out.mscores1, L, w.cf_nch, w.cf_nst);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -58,16 +58,17 @@ __device__ __forceinline__ void wait_dma_barrier_if(int on) {
 
 constexpr int FP16_ACT_SCALE_LOG2 = 4;   // activations are multiplied by 2^4 before the fp16 split (exact), range +-8188
 
-// MODE = Workspace::prec: 2 bf16x6 (the score contraction), 3 fp16x3, 4 fp16x4.  (The exact fp32 MFMA on this loop, MODE 0, was 8 % slower
+// MODE: an Arith, BF16X6 (the score contraction), FP16X3 or FP16X4.  (The exact fp32 MFMA on this loop, MODE 0, was 8 % slower
 // per frame than the register-staged fp32 loop: profiles/r04_ab_live_fp32_dma.txt; removed.)
 // ASL: log2 of the power of two the B operand (activations) is multiplied by before an fp16 split (ignored by the bf16 modes)
 template <int BM_, int WM_, int WN_, int NST_, int MODE_, int ASL_ = FP16_ACT_SCALE_LOG2>
 struct SpTile {
+    static_assert(MODE_ == BF16X6 || MODE_ == FP16X3 || MODE_ == FP16X4, "bf16x6, fp16x3 or fp16x4 (fp32 and bf16x3: gemm_f32_mfma.h)");
     static constexpr int BM = BM_, WM = WM_, WN = WN_, NST = NST_, MODE = MODE_;
     static constexpr int TM = BM / WM / 32, TN = 1, BN = 32 * WN;
     static constexpr int WAVES = WM * WN, WAVES_MN = WAVES, THREADS = 64 * WAVES, KS = 1;
-    static constexpr bool F16 = MODE >= 3;
-    static constexpr int PA = MODE == 2 ? 3 : 2;                  // planes per operand (16-bit terms)
+    static constexpr bool F16 = MODE >= FP16X3;
+    static constexpr int PA = MODE == BF16X6 ? 3 : 2;             // planes per operand (16-bit terms)
     static constexpr int ROW_BYTES = 64;                          // one LDS row = 32 k of one matrix row
     static constexpr int A_PLANE_BYTES = BM * ROW_BYTES;          // [BM][32], unpadded, swizzled
     static constexpr int A_BYTES = PA * A_PLANE_BYTES;
@@ -113,24 +114,23 @@ __device__ __forceinline__ void fp16_split2_mix(float a, float b, unsigned& hi, 
 // 8 fp32 values (consecutive k of one column) -> the PA 16-bit planes of an MFMA operand register.  scale (fp16 modes): an exact
 // power of two applied on the way (1: none).
 template <int MODE>
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&out)[MODE == 2 ? 3 : 2], float scale = 1.f) {
+__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&out)[MODE == BF16X6 ? 3 : 2], float scale = 1.f) {
     unsigned p[3][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        if constexpr (MODE >= 3) {
+        if constexpr (MODE >= FP16X3) {
             if (scale != 1.f) fp16_split2_scaled(v[2 * q], v[2 * q + 1], scale, p[0][q], p[1][q]);
             else fp16_split2_mix(v[2 * q], v[2 * q + 1], p[0][q], p[1][q]);
         }
-        else if constexpr (MODE == 1) bf16_split2(v[2 * q], v[2 * q + 1], p[0][q], p[1][q]);
         else bf16_split3(v[2 * q], v[2 * q + 1], p[0][q], p[1][q], p[2][q]);
     }
 #pragma unroll
-    for (int pl = 0; pl < (MODE == 2 ? 3 : 2); ++pl) out[pl] = __builtin_bit_cast(bf16x8, ((u32x4){p[pl][0], p[pl][1], p[pl][2], p[pl][3]}));
+    for (int pl = 0; pl < (MODE == BF16X6 ? 3 : 2); ++pl) out[pl] = __builtin_bit_cast(bf16x8, ((u32x4){p[pl][0], p[pl][1], p[pl][2], p[pl][3]}));
 }
 
 // the term products of one 32x32x16 block, small terms first (gemm_f32_mfma.h); FRESH: the first one starts from zero.
 template <int MODE, bool FRESH>
-__device__ __forceinline__ void mfma_terms(f32x16& c, const bf16x8 (&a)[MODE == 2 ? 3 : 2], const bf16x8 (&b)[MODE == 2 ? 3 : 2]) {
+__device__ __forceinline__ void mfma_terms(f32x16& c, const bf16x8 (&a)[MODE == BF16X6 ? 3 : 2], const bf16x8 (&b)[MODE == BF16X6 ? 3 : 2]) {
     f32x16 z;
 #pragma unroll
     for (int r = 0; r < 16; ++r) z[r] = 0.f;
@@ -141,8 +141,8 @@ __device__ __forceinline__ void mfma_terms(f32x16& c, const bf16x8 (&a)[MODE == 
     auto b16 = [](bf16x8 x, bf16x8 y, f32x16 acc) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc, 0, 0, 0);
     };
-    if constexpr (MODE >= 3) {
-        if constexpr (MODE == 4) {
+    if constexpr (MODE >= FP16X3) {
+        if constexpr (MODE == FP16X4) {
             c = f16(a[1], b[1], FRESH ? z : c);
             c = f16(a[1], b[0], c);
         } else {
@@ -150,10 +150,6 @@ __device__ __forceinline__ void mfma_terms(f32x16& c, const bf16x8 (&a)[MODE == 
         }
         c = f16(a[0], b[1], c);
         c = f16(a[0], b[0], c);
-    } else if constexpr (MODE == 1) {
-        c = b16(a[1], b[0], FRESH ? z : c);
-        c = b16(a[0], b[1], c);
-        c = b16(a[0], b[0], c);
     } else {
         c = b16(a[2], b[0], FRESH ? z : c);
         c = b16(a[0], b[2], c);
@@ -336,8 +332,8 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
         //   products (I, P0) m = 0 .. HM-1 : pair q of split (I, P1) under m = q HM/4 (hooks: the raw-value dot under m = 0, the head fold under m = HM/2)
         //   counted wait + barrier(I)
         //   products (I, P1) m = 0 .. HM-1 : DMA pieces + reads of slab I + 1 under m = 0, HM/4, HM-2; pair q of split (I + 1, P0) under m = HM-4+q
-        static_assert(MODE >= 3, "the slot schedule is written for the two-plane fp16 modes");
-        constexpr int NT = MODE == 4 ? 4 : 3, HM = TM * NT, QA = HM / 4, S0 = HM - 4, PP = 1;
+        static_assert(MODE >= FP16X3, "the slot schedule is written for the two-plane fp16 modes");
+        constexpr int NT = MODE == FP16X4 ? 4 : 3, HM = TM * NT, QA = HM / 4, S0 = HM - 4, PP = 1;
         static_assert(QA >= 1 && S0 >= 0, "four pairs per half step");
         constexpr int NSLOT = NST >= 3 ? 4 : 3;
         constexpr int E0 = (G + NSLOT - 1) / NSLOT, E1 = E0 + (G - E0 + NSLOT - 2) / (NSLOT - 1);
@@ -347,8 +343,8 @@ __device__ __forceinline__ void gemm_mainloop_sp(f32x16 (&acc)[T::TM], char* sme
             constexpr int I = decltype(Ic)::value, P = decltype(Pc)::value, M = decltype(Mc)::value, tm = M / NT, t = M % NT;
             f32x16(&dst)[TM] = hooks.template target<I, TM>(acc);
             // term order of mfma_terms (small terms first): fp16x4 (a1 b1) (a1 b0) (a0 b1) (a0 b0); fp16x3 (a1 b0) (a0 b1) (a0 b0)
-            constexpr int ap = MODE == 4 ? (t < 2 ? 1 : 0) : (t == 0 ? 1 : 0);
-            constexpr int bp = MODE == 4 ? ((t & 1) ? 0 : 1) : (t == 1 ? 1 : 0);
+            constexpr int ap = MODE == FP16X4 ? (t < 2 ? 1 : 0) : (t == 0 ? 1 : 0);
+            constexpr int bp = MODE == FP16X4 ? ((t & 1) ? 0 : 1) : (t == 1 ? 1 : 0);
             const f16x8 a = __builtin_bit_cast(f16x8, Af[P][tm][ap]);
             const f16x8 b = __builtin_bit_cast(f16x8, ((u32x4){Bw[P][bp][0], Bw[P][bp][1], Bw[P][bp][2], Bw[P][bp][3]}));
             if constexpr (t == 0 && Hooks::template fresh<I, P>()) {

@@ -60,6 +60,30 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
         _native.load()
 
 
+def test_python_constants_mirror_the_headers():
+    """_native.py repeats numbers that the C side owns: the GATSSPG_FLAG_* / GATSSPG_LAYER_* macros of include/gatsspg.h and the
+    KernelId enumerators of gatsspg_launch.h (the kernel_id of gatsspg_forward_profiled).  Parsed from the sources, compared by value."""
+    from onepose_amd import _native
+    header = open(os.path.join(ROOT, "include", "gatsspg.h")).read()
+    macros = {n: int(v, 0) for n, v in re.findall(r"^#define GATSSPG_((?:FLAG|LAYER)_[A-Z0-9_]+)\s+(0x[0-9a-fA-F]+|\d+)\s*$", header, flags=re.M)}
+    flags = sorted(n for n in macros if n.startswith("FLAG_"))
+    assert len(flags) == 7 and sorted(n for n in macros if n.startswith("LAYER_")) == ["LAYER_CROSS", "LAYER_SELF"]
+    for name, value in macros.items():
+        assert getattr(_native, name) == value, f"_native.{name} != GATSSPG_{name}"
+    prec = {n[len("FLAG_PREC_"):].lower(): macros[n] for n in flags if n.startswith("FLAG_PREC_")}
+    assert _native.PRECISIONS == {"fp32": 0, **prec}
+
+    launch = open(os.path.join(ROOT, "onepose_amd", "csrc", "gatsspg_launch.h")).read()
+    body = re.search(r"enum KernelId \{(.*?)\};", launch, flags=re.S).group(1)
+    kids = re.findall(r"KID_([A-Z0-9_]+) = (\d+)(\s*/\*\s*retired)?", body)
+    count = [int(v) for n, v, _ in kids if n == "COUNT"]
+    live = {int(v): n.lower() for n, v, retired in kids if n != "COUNT" and not retired}
+    assert count == [len(kids) - 1] and len(live) >= 13
+    assert sorted(_native.KERNEL_IDS.values()) == sorted(live), "KERNEL_IDS must cover exactly the non-retired kernel ids"
+    for name, kid in _native.KERNEL_IDS.items():
+        assert name.startswith(live[kid]), f"KERNEL_IDS[{name!r}] = {kid}, which is KID_{live[kid].upper()}"
+
+
 def test_product_libraries_never_read_the_environment(lib):
     """Precision and tile shapes are arguments / compile-time constants: the shipped libraries do not even import getenv
     (a stray GATSSPG_* variable in a user's shell cannot change numerics or code paths)."""
