@@ -1,5 +1,5 @@
 """Build libgatsspg_hip.so (matcher), libspp_hip.so (SuperPoint extractor), libpnp_hip.so (RANSAC-EPnP), libsuperglue_hip.so
-(SuperGlue 2D-2D matcher) and libdet_hip.so (2D object detector tail) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+(SuperGlue 2D-2D matcher), libdet_hip.so (2D object detector tail) and libmap_hip.so (object database builder) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m onepose_amd.build_ext [--force] [--remarks] [--profiling] [--tuning]
 
@@ -32,7 +32,7 @@ class Library:
         self.sources, self.headers, self.tuning = sources, headers, tuning
 
 
-# The SuperGlue and detector sources live in csrc/superglue/, csrc/detector/ and their include/ twins: source_hash() (top-level
+# The SuperGlue, detector and mapping sources live in csrc/superglue/, csrc/detector/, csrc/mapping/ and their include/ twins: source_hash() (top-level
 # files only) does not see them.
 LIBRARIES = (
     Library("gatsspg", ["gatsspg_gemm_kernels.hip", "gatsspg_split_kernels.hip", "gatsspg_stream_kernels.hip", "gatsspg_capi.hip"],
@@ -45,12 +45,15 @@ LIBRARIES = (
     Library("superglue", [os.path.join("superglue", "superglue.hip")], ["capi_common.h", _include("superglue", "superglue.h")]),
     Library("det", [os.path.join("detector", "detector.hip")],
             ["capi_common.h", "ransac_sample.h", _include("detector", "detector.h")]),
+    Library("map", [os.path.join("mapping", "mapping.hip")],
+            ["capi_common.h", "ransac_sample.h", _include("mapping", "mapping.h")]),
 )
 # views of the table under the names other modules use
-LIB_PATH, SPP_LIB_PATH, PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH = (lib.path for lib in LIBRARIES)
+LIB_PATH, SPP_LIB_PATH, PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH, MAP_LIB_PATH = (lib.path for lib in LIBRARIES)
 SOURCES = LIBRARIES[0].sources
 SG_SOURCES, SG_HEADERS = LIBRARIES[3].sources, LIBRARIES[3].headers
 DET_SOURCES, DET_HEADERS = LIBRARIES[4].sources, LIBRARIES[4].headers
+MAP_SOURCES, MAP_HEADERS = LIBRARIES[5].sources, LIBRARIES[5].headers
 
 
 def _hipcc():
@@ -90,7 +93,7 @@ def tuning_path(lib):
 
 
 def build(force=False, remarks=False, verbose=True, profiling=False, tuning=False, syntax_only=False):
-    """Compile every HIP source for gfx950 into onepose_amd/lib/lib{gatsspg,spp,pnp,superglue,det}_hip.so.
+    """Compile every HIP source for gfx950 into onepose_amd/lib/lib{gatsspg,spp,pnp,superglue,det,map}_hip.so.
     tuning / profiling builds go to lib*_tuning.so (environment knobs; profiling adds -DGATSSPG_PROFILING_BUILD: the timeline
     hooks) -- the package never loads those.  syntax_only: front-end check only."""
     os.makedirs(LIB_DIR, exist_ok=True)

@@ -351,3 +351,118 @@ def make_superglue_inputs(b, n0, n1, h, w, seed=1, planted=None, h1=None, w1=Non
             out["descriptors1"][i][:, p1[i]] = out["descriptors0"][i][:, p0[i]]
         out["planted0"], out["planted1"] = p0.astype(np.int64), p1.astype(np.int64)
     return out
+
+
+# ---- object database builder (run.py:80-163): a posed scan of a planted object ---------------------------------
+def make_box_corners(half=(0.1, 0.1, 0.1)):
+    """box3d_corners [8,3] in the reference's corner order as far as filter_points.py:43-45 uses it: the three edges
+    that leave corner 4 end at the corners 5, 0 and 7."""
+    hx, hy, hz = half
+    c4 = np.array([-hx, -hy, -hz])
+    ex, ey, ez = np.array([2 * hx, 0, 0]), np.array([0, 2 * hy, 0]), np.array([0, 0, 2 * hz])
+    c = np.zeros((8, 3))
+    c[4], c[5], c[0], c[7] = c4, c4 + ex, c4 + ey, c4 + ez
+    c[1], c[6], c[3], c[2] = c4 + ex + ey, c4 + ex + ez, c4 + ey + ez, c4 + ex + ey + ez
+    return c
+
+
+def make_ring_poses(n_views, rs, radius=0.5):
+    """World->camera poses [n,3,4] of cameras on a jittered ring around the origin, looking at it (x right, y down, z forward)."""
+    poses = []
+    for v in range(n_views):
+        az = 2 * np.pi * v / n_views + rs.uniform(-0.05, 0.05)
+        el = rs.uniform(0.2, 0.7)
+        r = radius * rs.uniform(0.9, 1.1)
+        c = r * np.array([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)])
+        z = -c / np.linalg.norm(c)
+        x = np.cross(z, np.array([0.0, 0.0, 1.0]))
+        x /= np.linalg.norm(x)
+        y = np.cross(z, x)
+        rot = np.stack([x, y, z])
+        poses.append(np.concatenate([rot, (-rot @ c)[:, None]], axis=1))
+    return np.stack(poses)
+
+
+def make_map_scene(n_points=300, n_views=12, hw=(96, 128), seed=0, noise_px=0.0, wrong_frac=0.0, dim=256, n_distract=20,
+                   pairs_per_view=3, dropout=0.2, outside_frac=0.0):
+    """A synthetic scan for the object database builder: points planted in a 20 cm box (``outside_frac`` of them outside it),
+    ``n_views`` posed pinhole views on a ring, per view the fp32 keypoints of the visible points (plus ``noise_px`` Gaussian
+    noise) and ``n_distract`` unmatched ones in random order, unit descriptors [dim, n_v], scores, and SuperGlue-like
+    ``matches0`` for each view and its next ``pairs_per_view`` neighbours, ``wrong_frac`` of them redirected to a wrong keypoint
+    more than 8 px away from the right one, whose own point projects more than 8 px away from the match's first keypoint.
+    -> dict(points, box, Ks [V,3,3], poses [V,3,4], features [V] of dict(keypoints, descriptors, scores), kp_point [V] (planted
+    point of each keypoint or -1), pair_matches [(i, j, matches0 int64 [n_i])], wrong [(pair, keypoint of i)])."""
+    rs = np.random.RandomState(seed)
+    h, w = hw
+    pts = rs.uniform(-0.08, 0.08, size=(n_points, 3))
+    n_out = int(round(outside_frac * n_points))
+    if n_out:
+        pts[:n_out, 2] = rs.uniform(0.11, 0.13, size=n_out)
+    poses = make_ring_poses(n_views, rs)
+    f = 2.2 * w
+    Ks = np.stack([np.array([[f + rs.uniform(-3, 3), 0, w / 2 + rs.uniform(-2, 2)], [0, f + rs.uniform(-3, 3), h / 2 + rs.uniform(-2, 2)],
+                             [0, 0, 1.0]]) for _ in range(n_views)])
+    base = rs.standard_normal((n_points, dim))
+    features, kp_point, proj = [], [], []
+    for v in range(n_views):
+        pc = pts @ poses[v, :, :3].T + poses[v, :, 3]
+        uv = np.stack([Ks[v, 0, 0] * pc[:, 0] / pc[:, 2] + Ks[v, 0, 2], Ks[v, 1, 1] * pc[:, 1] / pc[:, 2] + Ks[v, 1, 2]], axis=1)
+        uv = uv + rs.standard_normal(uv.shape) * noise_px
+        proj.append(uv)
+        vis = (uv[:, 0] > 1) & (uv[:, 0] < w - 2) & (uv[:, 1] > 1) & (uv[:, 1] < h - 2) & (rs.rand(n_points) > dropout)
+        ids = np.concatenate([np.nonzero(vis)[0], np.full(n_distract, -1)])
+        kp = np.concatenate([uv[vis], rs.uniform(2, [w - 3, h - 3], size=(n_distract, 2))])
+        perm = rs.permutation(len(ids))
+        ids, kp = ids[perm], kp[perm].astype(np.float32)
+        d = np.where(ids[:, None] >= 0, base[np.maximum(ids, 0)], 0) + 0.1 * rs.standard_normal((len(ids), dim))
+        d[ids < 0] = rs.standard_normal((int((ids < 0).sum()), dim))
+        d = (d / np.linalg.norm(d, axis=1, keepdims=True)).T.astype(np.float32)
+        features.append({"keypoints": kp, "descriptors": np.ascontiguousarray(d), "scores": rs.uniform(0.05, 1.0, len(ids)).astype(np.float32)})
+        kp_point.append(ids)
+    pairs = sorted({tuple(sorted((v, (v + k) % n_views))) for v in range(n_views) for k in range(1, pairs_per_view + 1)} - {(v, v) for v in range(n_views)})
+    pair_matches, wrong = [], []
+    for p, (i, j) in enumerate(pairs):
+        where_j = {int(q): k for k, q in enumerate(kp_point[j]) if q >= 0}
+        m0 = np.array([where_j.get(int(q), -1) if q >= 0 else -1 for q in kp_point[i]], np.int64)
+        for a in np.nonzero(m0 >= 0)[0]:
+            if rs.rand() < wrong_frac:
+                # more than 8 px from the right keypoint, and planted where its own point lies more than 8 px from keypoint a
+                right, qj = features[j]["keypoints"][m0[a]], kp_point[j]
+                other = np.abs(proj[i][np.maximum(qj, 0)] - features[i]["keypoints"][a]).max(axis=1) > 8.0
+                far = np.nonzero((np.abs(features[j]["keypoints"] - right).max(axis=1) > 8.0) & ((qj < 0) | other))[0]
+                if len(far):
+                    m0[a] = far[rs.randint(len(far))]
+                    wrong.append((p, int(a)))
+        pair_matches.append((i, j, m0))
+    return {"points": pts, "box": make_box_corners(), "Ks": Ks, "poses": poses, "features": features, "kp_point": kp_point,
+            "pair_matches": pair_matches, "wrong": wrong, "hw": hw}
+
+
+def make_map_model(seed=0, n_images=40, n_points=600, dim=16, hw=(96, 128)):
+    """A synthetic triangulated model for the post-processing stages of the database builder (what COLMAP hands to
+    filter_tkl / filter_points / feature_process): two sequences of posed images, points around the 20 cm box (a tenth outside,
+    a pair, a triple and a chain closer than 1 mm), tracks of 2..12 observations, per-image features of dimension ``dim``.
+    -> dict(poses [V,3,4], seq_ids, xyz [T,3] float64, track_offsets, obs_image, obs_kpt, features, box, max_num_kp3d)."""
+    rs = np.random.RandomState(seed)
+    poses = make_ring_poses(n_images, rs)
+    seq_ids = ["seq-1" if v < n_images // 2 else "seq-2" for v in range(n_images)]
+    xyz = rs.uniform(-0.09, 0.09, size=(n_points, 3))
+    xyz[rs.rand(n_points) < 0.1, 2] = 0.12
+    step = np.array([0.0007, 0.0, 0.0])
+    xyz[5] = xyz[2] + 0.3 * step
+    xyz[11], xyz[20] = xyz[7] + 0.3 * step, xyz[7] - 0.3 * step
+    xyz[14] = np.array([0.01, 0.02, 0.03])
+    xyz[17], xyz[25] = xyz[14] + step, xyz[14] + 2 * step
+    lengths = rs.randint(2, 13, size=n_points)
+    lengths[[2, 5, 7, 11, 20, 14, 17, 25]] = 12
+    obs_image = np.concatenate([np.sort(rs.permutation(n_images)[:m]) for m in lengths]).astype(np.int32)
+    per_image = np.bincount(obs_image, minlength=n_images)
+    n_kpts = per_image + rs.randint(3, 9, size=n_images)
+    slots = [list(rs.permutation(int(n))) for n in n_kpts]
+    obs_kpt = np.array([slots[v].pop() for v in obs_image], np.int32)
+    h, w = hw
+    features = [{"keypoints": rs.uniform(0, [w, h], size=(int(n), 2)).astype(np.float32),
+                 "descriptors": rs.standard_normal((dim, int(n))).astype(np.float32), "scores": rs.uniform(0.01, 1.0, int(n)).astype(np.float32)}
+                for n in n_kpts]
+    return {"poses": poses, "seq_ids": seq_ids, "xyz": xyz, "track_offsets": np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32),
+            "obs_image": obs_image, "obs_kpt": obs_kpt, "features": features, "box": make_box_corners(), "max_num_kp3d": int(0.6 * n_points)}
