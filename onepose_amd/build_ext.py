@@ -40,13 +40,13 @@ LIBRARIES = (
              _include("gatsspg.h")],
             tuning=True),
     Library("spp", ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"],
-            ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", _include("superpoint.h")], tuning=True),
-    Library("pnp", ["pnp_kernels.hip"], ["capi_common.h", "ransac_sample.h", _include("pnp.h")]),
+            ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", "wg_primitives.h", _include("superpoint.h")], tuning=True),
+    Library("pnp", ["pnp_kernels.hip"], ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("pnp.h")]),
     Library("superglue", [os.path.join("superglue", "superglue.hip")], ["capi_common.h", _include("superglue", "superglue.h")]),
     Library("det", [os.path.join("detector", "detector.hip")],
-            ["capi_common.h", "ransac_sample.h", _include("detector", "detector.h")]),
+            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h")]),
     Library("map", [os.path.join("mapping", "mapping.hip")],
-            ["capi_common.h", "ransac_sample.h", _include("mapping", "mapping.h")]),
+            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h")]),
 )
 # views of the table under the names other modules use
 LIB_PATH, SPP_LIB_PATH, PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH, MAP_LIB_PATH = (lib.path for lib in LIBRARIES)

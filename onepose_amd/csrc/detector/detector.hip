@@ -2,13 +2,14 @@
 // local_feature_2D_detector.py:85-147,160-186 and src/utils/data_utils.py:24-57,233-272).
 //
 // fp64 geometry on fp32 keypoints, like the reference's float64 cv2 results.  Small latency-bound work, no MFMA:
-//   det_gather_kernel  one workgroup per view: ordered compaction of the valid matches into (x0, y0, x1, y1) rows,
-//                      zeroes the view's inlier mask and its best-hypothesis key
-//   det_score_kernel   one wave per hypothesis (4 in turn per wave, 64 per workgroup): hash-sampled minimal set of 2 ->
-//                      partial affine -> inlier count over the view's matches held as fp32 in LDS (4096-match chunks);
+//   det_gather_kernel  one workgroup per view: ordered compaction of the valid matches into (x0, y0, x1, y1) rows
+//                      (wg::excl_scan), zeroes the view's inlier mask and its best-hypothesis key
+//   det_score_kernel   one wave per hypothesis (4 in turn per wave, 64 per workgroup): hash-sampled minimal set of 2
+//                      (sampling::distinct) -> partial affine -> inlier count over the view's matches held as fp32 in LDS
+//                      (4096-match chunks, wg::wave_sum);
 //                      best kept per view as one 64-bit (count, ~index) key with a vector atomicMax
 //   det_finish_kernel  one workgroup per view: mask of the winner, closed-form least-squares refit over its inliers with
-//                      a fixed-order reduction (two runs are bitwise equal), affine / info written
+//                      a fixed-order reduction (wg::tree_sum: two runs are bitwise equal), affine / info written
 //   det_vote_kernel    boxes of all views and the vote
 //   det_crop_kernel    the two warps of crop_img_by_bbox as one exact-integer bilinear resampling, and K_crop
 // No FMA contraction: tests/detector_oracle.py restates every expression in the same order in numpy (which never fuses),
@@ -19,6 +20,7 @@
 #include "../../../include/detector/detector.h"
 #include "../capi_common.h"
 #include "../ransac_sample.h"
+#include "../wg_primitives.h"
 
 #pragma clang fp contract(off)
 
@@ -29,15 +31,6 @@ constexpr int SCORE_THREADS = 1024;  // 16 waves
 constexpr int HYP_PER_WAVE = 4;
 constexpr int HYP_PER_BLOCK = SCORE_THREADS / 64 * HYP_PER_WAVE;
 constexpr int FIN_THREADS = 256;     // the refit's reduction order (oracle: REFIT_LANES)
-
-// two distinct indices in [0, n), n >= 2: successive hash draws, duplicates rejected (oracle: sample_indices)
-__device__ __forceinline__ void sample_pair(unsigned long long seed, int hyp, int n, int& i0, int& i1) {
-    unsigned long long ctr = 0;
-    i0 = sampling::draw(seed, hyp, ctr++, n);
-    do {
-        i1 = sampling::draw(seed, hyp, ctr++, n);
-    } while (i1 == i0);
-}
 
 struct Model {
     double a, b, tx, ty;
@@ -58,9 +51,9 @@ __device__ __forceinline__ bool model_from_pair(const float4 p, const float4 q, 
 }
 
 __device__ __forceinline__ bool hypothesis(const float4* __restrict__ pts, int n, unsigned long long seed, int hyp, Model& m) {
-    int i0, i1;
-    sample_pair(seed, hyp, n, i0, i1);
-    return model_from_pair(pts[i0], pts[i1], m);
+    int idx[2];
+    sampling::distinct(seed, hyp, n, idx);   // n >= 2
+    return model_from_pair(pts[idx[0]], pts[idx[1]], m);
 }
 
 __device__ __forceinline__ double residual2(const Model& m, const float4 p) {
@@ -77,7 +70,7 @@ __global__ __launch_bounds__(1024) void det_gather_kernel(const float* __restric
                                                           int* __restrict__ src_all, int* __restrict__ count,
                                                           unsigned long long* __restrict__ best, int32_t* __restrict__ mask_all) {
     __shared__ int wsum[16];
-    const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int v = blockIdx.x, tid = threadIdx.x;
     const size_t base_v = (size_t)v * cap0;
     int n = n0 ? n0[v] : n_host;
     n = n < 0 ? 0 : (n > cap0 ? cap0 : n);
@@ -88,21 +81,10 @@ __global__ __launch_bounds__(1024) void det_gather_kernel(const float* __restric
         if (i < n) m = matches0 ? matches0[base_v + i] : (long long)i;
         const int valid = m > -1 && m < (long long)n1;
         if (i < cap0) mask_all[base_v + i] = 0;
-        int inc = valid;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        __syncthreads();
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wave) before += wsum[w];
-            tot += wsum[w];
-        }
+        int tot;
+        const int pos = wg::excl_scan<1024>(valid, wsum, tot);
         if (valid) {
-            const int o = run + before + inc - 1;
+            const int o = run + pos;
             pts_all[base_v + o] = make_float4(kpts0[(base_v + i) * 2], kpts0[(base_v + i) * 2 + 1], kpts1[(size_t)m * 2],
                                               kpts1[(size_t)m * 2 + 1]);
             src_all[base_v + o] = i;
@@ -147,8 +129,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void det_score_kernel(const float4* 
     unsigned long long key = 0ull;
 #pragma unroll
     for (int k = 0; k < HYP_PER_WAVE; ++k) {
-        int c = cnt[k];
-        for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+        const int c = wg::wave_sum(cnt[k]);
         if (valid[k]) {
             const unsigned long long kk = ((unsigned long long)(unsigned)c << 32) | (unsigned long long)(~(unsigned)(h0 + k));
             key = kk > key ? kk : key;
@@ -157,26 +138,13 @@ __global__ __launch_bounds__(SCORE_THREADS) void det_score_kernel(const float4* 
     if (lane == 0 && key != 0ull) atomicMax(best + v, key);
 }
 
-// sum of red[q][0 .. FIN_THREADS) into red[q][0] for q < Q, in a fixed tree order
-template <int Q>
-__device__ __forceinline__ void tree_sum(double (*red)[FIN_THREADS], int t) {
-    __syncthreads();
-    for (int s = FIN_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int q = 0; q < Q; ++q) red[q][t] += red[q][t + s];
-        }
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(FIN_THREADS) void det_finish_kernel(const float4* __restrict__ pts_all, const int* __restrict__ src_all,
                                                                  const int* __restrict__ count,
                                                                  const unsigned long long* __restrict__ best, int cap0,
                                                                  int min_matches, double thr2, unsigned long long seed,
                                                                  double* __restrict__ affine, int32_t* __restrict__ mask_all,
                                                                  int32_t* __restrict__ info) {
-    __shared__ double red[4][FIN_THREADS];
+    __shared__ double red[4 * FIN_THREADS];
     __shared__ int redc[FIN_THREADS];
     const int v = blockIdx.x, t = threadIdx.x;
     const int n = count[v];
@@ -195,19 +163,18 @@ __global__ __launch_bounds__(FIN_THREADS) void det_finish_kernel(const float4* _
         return;
     }
     // pass 1: mask of the winner, centroids of its inliers
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
     int c = 0;
     for (int i = t; i < n; i += FIN_THREADS) {
         const float4 p = pts[i];
         if (residual2(m, p) <= thr2) {
             mask[src[i]] = 1;
-            s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; s3 += (double)p.w;
+            s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z; s[3] += (double)p.w;
             ++c;
         }
     }
-    red[0][t] = s0; red[1][t] = s1; red[2][t] = s2; red[3][t] = s3;
     redc[t] = c;
-    tree_sum<4>(red, t);
+    wg::tree_sum<FIN_THREADS>(s, red);
     if (t == 0) {
         int tot = 0;
         for (int i = 0; i < FIN_THREADS; ++i) tot += redc[i];
@@ -216,28 +183,26 @@ __global__ __launch_bounds__(FIN_THREADS) void det_finish_kernel(const float4* _
     __syncthreads();
     const int n_inl = redc[0];
     const double cnt = (double)n_inl;
-    const double csx = red[0][0] / cnt, csy = red[1][0] / cnt, cdx = red[2][0] / cnt, cdy = red[3][0] / cnt;
-    __syncthreads();
+    const double csx = s[0] / cnt, csy = s[1] / cnt, cdx = s[2] / cnt, cdy = s[3] / cnt;
     // pass 2: centred sums
-    double suu = 0.0, sdot = 0.0, scr = 0.0;
+    double u[3] = {0.0, 0.0, 0.0};   // sums of |u|^2, u . w, u x w
     for (int i = t; i < n; i += FIN_THREADS) {
         const float4 p = pts[i];
         if (residual2(m, p) <= thr2) {
             const double ux = (double)p.x - csx, uy = (double)p.y - csy, wx = (double)p.z - cdx, wy = (double)p.w - cdy;
-            suu += ux * ux + uy * uy;
-            sdot += ux * wx + uy * wy;
-            scr += ux * wy - uy * wx;
+            u[0] += ux * ux + uy * uy;
+            u[1] += ux * wx + uy * wy;
+            u[2] += ux * wy - uy * wx;
         }
     }
-    red[0][t] = suu; red[1][t] = sdot; red[2][t] = scr;
-    tree_sum<3>(red, t);
+    wg::tree_sum<FIN_THREADS>(u, red);
     if (t == 0) {
-        const double den = red[0][0];
+        const double den = u[0];
         if (!(den > 0.0)) {   // cannot happen after a non-degenerate sample; never divide by zero
             for (int k = 0; k < 6; ++k) A[k] = 0.0;
             I[0] = 0; I[1] = n; I[2] = -1; I[3] = 0;
         } else {
-            const double a = red[1][0] / den, b = red[2][0] / den;
+            const double a = u[1] / den, b = u[2] / den;
             A[0] = a; A[1] = -b; A[2] = cdx - (a * csx - b * csy);
             A[3] = b; A[4] = a;  A[5] = cdy - (b * csx + a * csy);
             I[0] = 1; I[1] = n; I[2] = hyp; I[3] = n_inl;

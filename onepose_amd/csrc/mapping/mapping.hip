@@ -3,13 +3,14 @@
 //
 // fp64 geometry on fp32 keypoints.  Small latency-bound work, no MFMA:
 //   map_verify_kernel     one workgroup per image pair: epipolar test of every match against the known relative pose,
-//                         ordered compaction of the survivors (a workgroup prefix sum, as det_gather_kernel does)
+//                         ordered compaction of the survivors (wg::excl_scan)
 //   map_tri_kernel<64>    one wave per track of up to 64 observations; <256>: one workgroup per longer track.  The track's
-//                         observations (camera, centre, ray) are staged in LDS; hypotheses are scored one after the other
-//                         by the whole group (per-lane counters, one reduction per hypothesis); the refit's sums are
-//                         fixed-order trees, so a track's result is the same in any batch and in any run
+//                         observations (camera, centre, ray) are staged in LDS; hypotheses (every pair, or pairs from
+//                         sampling::distinct) are scored one after the other by the whole group (per-lane counters, one
+//                         reduction per hypothesis); the refit's sums are fixed-order trees (<256>: wg::tree_sum), so a
+//                         track's result is the same in any batch and in any run
 //   map_threshold_kernel  LDS histogram of the track lengths and the reference's selection rule
-//   map_filter_kernel     track-length and fp32 box test, ordered compaction
+//   map_filter_kernel     track-length and fp32 box test, ordered compaction (wg::excl_scan)
 //   map_adjacency_kernel  n x n closeness bits, 32 per thread; map_sweep_kernel: the reference's greedy sweep, one
 //                         workgroup walking the bit rows in index order
 //   map_gather_kernel     one workgroup per point, one lane per descriptor channel
@@ -22,6 +23,7 @@
 #include "../../../include/mapping/mapping.h"
 #include "../capi_common.h"
 #include "../ransac_sample.h"
+#include "../wg_primitives.h"
 
 #pragma clang fp contract(off)
 
@@ -37,26 +39,6 @@ __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// exclusive position of every set flag among the SCAN_THREADS threads of the workgroup, and their total
-__device__ __forceinline__ int block_scan(int flag, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = flag;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-    for (int w = 0; w < SCAN_THREADS / 64; ++w) {
-        if (w < wave) before += wsum[w];
-        total += wsum[w];
-    }
-    return before + inc - flag;
-}
-
 __global__ __launch_bounds__(SCAN_THREADS) void map_verify_kernel(const float* __restrict__ kpts, const int32_t* __restrict__ kpt_offsets,
                                                                   const double* __restrict__ cams, int V,
                                                                   const int32_t* __restrict__ pair_images,
@@ -106,7 +88,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void map_verify_kernel(const float* _
             keep = denj > 0.0 && deni > 0.0 && (num * num) / denj <= thr2 && (num * num) / deni <= thr2;
         }
         int tot;
-        const int pos = block_scan(keep, wsum, tot);
+        const int pos = wg::excl_scan<SCAN_THREADS>(keep, wsum, tot);
         if (keep) {
             out[((size_t)base + run + pos) * 2] = a;
             out[((size_t)base + run + pos) * 2 + 1] = (int32_t)b;
@@ -124,7 +106,7 @@ struct TriParams {
 };
 
 // sums of a group of NT threads (NT = 64: the wave, shuffles; NT = 256: the workgroup, LDS), the same on every thread.
-// Doubles are summed as the tree  v[t] += v[t + s], s = NT / 2 .. 1  (oracle: tree_sum).
+// Doubles are summed as the tree  v[t] += v[t + s], s = NT / 2 .. 1  (oracle: lane_tree_sum).
 template <int NT>
 struct Group {
     double* red;   // [9][NT] (NT = 256 only)
@@ -134,8 +116,7 @@ struct Group {
 
     __device__ __forceinline__ int sum(int v) const {
         if constexpr (NT == 64) {
-            for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-            return v;
+            return wg::wave_sum(v);
         } else {
             const int t = threadIdx.x;
             __syncthreads();
@@ -164,20 +145,7 @@ struct Group {
                 v[q] = __shfl(x, 0);
             }
         } else {
-            const int t = threadIdx.x;
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < Q; ++q) red[q * NT + t] = v[q];
-            __syncthreads();
-            for (int s = NT / 2; s > 0; s >>= 1) {
-                if (t < s) {
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) red[q * NT + t] += red[q * NT + t + s];
-                }
-                __syncthreads();
-            }
-#pragma unroll
-            for (int q = 0; q < Q; ++q) v[q] = red[q * NT];
+            wg::tree_sum<NT>(v, red);
         }
     }
 };
@@ -301,11 +269,10 @@ __global__ __launch_bounds__(NT) void map_tri_kernel(const int32_t* __restrict__
                 b = a + 1;
             }
         } else {
-            unsigned long long ctr = 0;
-            a = sampling::draw(P.seed, h, ctr++, m);
-            do {
-                b = sampling::draw(P.seed, h, ctr++, m);
-            } while (b == a);
+            int ab[2];
+            sampling::distinct(P.seed, h, m, ab);
+            a = ab[0];
+            b = ab[1];
         }
         double X[3];
         const bool valid = T.midpoint(a, b, X) && T.angle_ok(a, b, X, P.cos_min) && T.inlier(a, X, P.thr2) && T.inlier(b, X, P.thr2);
@@ -452,7 +419,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void map_filter_kernel(const double* 
             }
         }
         int tot;
-        const int pos = block_scan(keep, wsum, tot);
+        const int pos = wg::excl_scan<SCAN_THREADS>(keep, wsum, tot);
         if (keep) {
             kept_ids[run + pos] = i;
             for (int d = 0; d < 3; ++d) kept_xyz[(size_t)(run + pos) * 3 + d] = p[d];

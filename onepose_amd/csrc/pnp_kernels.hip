@@ -1,9 +1,11 @@
 // RANSAC-EPnP pose solver (C ABI: include/pnp.h; reference call site: src/utils/eval_utils.py:18-42).
 //
 // fp64 throughout, like the reference's float64 cv2 call.  Latency-bound small dense algebra, not MFMA work:
-//   hyp_kernel    one thread per hypothesis: hash-sampled minimal set of 5 -> EPnP -> [R | t]
+//   hyp_kernel    one thread per hypothesis: hash-sampled minimal set of 5 (sampling::distinct) -> EPnP -> [R | t]
 //   score_kernel  one wave per hypothesis: squared reprojection error of every correspondence, ballot count
 //   best_kernel   one workgroup: first arg-max of the inlier counts, inlier mask + ordered index list of the best model
+//                 (wg::excl_scan per 1024 correspondences)
+//   gather_matches_kernel  one workgroup: ordered compaction of the valid matches (wg::excl_scan), inlier mask zeroed
 //   refit_kernel  one wave: EPnP over the inliers (point sums by butterfly reductions: every lane ends with the same
 //                 bits, then runs the same dense stage), pose written as [R | t / scale]
 // The EPnP steps follow OpenCV calib3d/epnp.cpp (see oracle/pnp_oracle.py for the restated algorithm and citations).
@@ -15,6 +17,7 @@
 #include "../../include/pnp.h"
 #include "capi_common.h"
 #include "ransac_sample.h"
+#include "wg_primitives.h"
 
 namespace pnp {
 
@@ -22,18 +25,6 @@ struct Cam {
     double fu, fv, uc, vc;
 };
 constexpr int MODEL_POINTS = 5;
-
-// MODEL_POINTS distinct indices in [0, n): successive hash draws, duplicates rejected (oracle: sample_indices)
-__device__ void sample_indices(unsigned long long seed, int hyp, int n, int (&idx)[MODEL_POINTS]) {
-    int got = 0;
-    unsigned long long ctr = 0;
-    while (got < MODEL_POINTS) {
-        const int v = sampling::draw(seed, hyp, ctr++, n);
-        bool dup = false;
-        for (int k = 0; k < got; ++k) dup |= idx[k] == v;
-        if (!dup) idx[got++] = v;
-    }
-}
 
 // ---- small dense algebra ------------------------------------------------------------------------------
 // Everything below is written so that every array index is a compile-time constant after unrolling: the matrices then
@@ -483,7 +474,7 @@ __global__ __launch_bounds__(64) void hyp_kernel(const float* __restrict__ p3, c
         return;
     }
     int idx[MODEL_POINTS];
-    sample_indices(seed, h, n, idx);
+    sampling::distinct(seed, h, n, idx);
     double spw[MODEL_POINTS][3], suv[MODEL_POINTS][2];
     for (int k = 0; k < MODEL_POINTS; ++k) {
         for (int c = 0; c < 3; ++c) spw[k][c] = (double)p3[(size_t)idx[k] * 3 + c] * scale;
@@ -562,21 +553,9 @@ __global__ __launch_bounds__(1024) void best_kernel(const float* __restrict__ p3
         const int i = i0 + tid;
         const int in = ok && i < n && is_inlier(P, p3, p2, i, scale, cam, thr2);
         if (i < n) mask[src ? src[i] : i] = in;
-        const int lane = tid & 63, wave = tid >> 6;
-        int inc = in;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        __syncthreads();
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int base = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wave) base += wsum[w];
-            tot += wsum[w];
-        }
-        if (in) inl_idx[run + base + inc - 1] = i;
+        int tot;
+        const int pos = wg::excl_scan<1024>(in, wsum, tot);
+        if (in) inl_idx[run + pos] = i;
         run += tot;
     }
     if (tid == 0) {
@@ -591,28 +570,17 @@ __global__ __launch_bounds__(1024) void gather_matches_kernel(const float* __res
                                                               float* __restrict__ p3, int* __restrict__ src, int* __restrict__ count,
                                                               int32_t* __restrict__ mask) {
     __shared__ int wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     int run = 0;
     for (int i0 = 0; i0 < n1; i0 += 1024) {
         const int i = i0 + tid;
         const long long m = i < n1 ? matches0[i] : -1;
         const int valid = m > -1;
         if (i < n1) mask[i] = 0;
-        int inc = valid;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        __syncthreads();
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int base = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wave) base += wsum[w];
-            tot += wsum[w];
-        }
+        int tot;
+        const int pos = wg::excl_scan<1024>(valid, wsum, tot);
         if (valid) {
-            const int o = run + base + inc - 1;
+            const int o = run + pos;
             p2[(size_t)o * 2] = kpts2d[(size_t)i * 2];
             p2[(size_t)o * 2 + 1] = kpts2d[(size_t)i * 2 + 1];
             for (int c = 0; c < 3; ++c) p3[(size_t)o * 3 + c] = kpts3d[(size_t)m * 3 + c];

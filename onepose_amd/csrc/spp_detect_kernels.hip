@@ -5,6 +5,7 @@
 // top-k) is integer / comparison work on one fp32 score map and is reproduced bit for bit: given the same score
 // map the keypoint list is identical to the reference's (tests feed the oracle's map through spp_detect).
 #include "spp_common.h"
+#include "wg_primitives.h"
 
 namespace spp {
 
@@ -240,35 +241,12 @@ __global__ __launch_bounds__(64) void compact_kernel(const float* __restrict__ n
 //   1. select_kernel (one workgroup per image): radix select on the fp32 bit patterns (scores are >= 0, so the
 //      unsigned order of the bits is the order of the values) finds the k-th largest score T in three histogram
 //      passes (12 + 12 + 8 bits); the k survivors -- score > T, plus the lowest-index candidates among those equal to
-//      T -- are compacted in candidate (row-major) order;
+//      T -- are compacted in candidate (row-major) order (wg::excl_scan, also the suffix counts of a radix digit);
 //   2. rank_kernel: rank_i = #{j : s_j > s_i or (s_j == s_i and j < i)} among the k survivors, tiled over a fixed grid;
 //      partial ranks are integers, so the atomic accumulation is exact and order-independent;
 //   3. scatter_kernel: survivor i goes to output slot rank_i (descending score, ties by lower pixel index).
 // With n <= k (or k = -1) the row-major list is kept as is.
 // =====================================================================================================
-__device__ __forceinline__ int block_excl_scan(int v, int* wsum, int& total) {
-    // exclusive prefix sum of one int per thread over a 1024-thread workgroup (thread order)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int t = wsum[w];
-        if (w < wave) base += t;
-        tot += t;
-    }
-    total = tot;
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(1024) void select_kernel(const float* __restrict__ cscore, int HW, const int* __restrict__ ncand,
                                                       const int* __restrict__ cand, int max_kp, int* __restrict__ surv,
                                                       unsigned* __restrict__ skey, int* __restrict__ rank) {
@@ -300,7 +278,7 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* __restrict__ 
             sum += loc[q];
         }
         int total;
-        int above = block_excl_scan(sum, wsum, total);   // keys in bins above this thread's range
+        int above = wg::excl_scan<1024>(sum, wsum, total);   // keys in bins above this thread's range
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int bin = rt * 4 + (3 - q);
@@ -336,7 +314,7 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* __restrict__ 
         const unsigned k = i < n ? key[i] : 0u;
         const int gt = i < n && k > T, tie = i < n && k == T;
         int tot;
-        const int pre = block_excl_scan(gt | (tie << 16), wsum, tot);
+        const int pre = wg::excl_scan<1024>(gt | (tie << 16), wsum, tot);
         const int g = gt_before + (pre & 0xFFFF), t = ties_before + (pre >> 16);
         if (gt || (tie && t < quota)) {
             const int opos = g + min(t, quota);

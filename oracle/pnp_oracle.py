@@ -24,34 +24,19 @@ formulations), not against cv2 outputs:
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
+
+from . import ransac_common
 
 F64 = np.float64
 PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
 MODEL_POINTS = 5          # solvePnPRansac: minimal set for SOLVEPNP_EPNP
 
 
-# ---- sampling ------------------------------------------------------------------------------------------
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-    z = x
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
-    return z ^ (z >> 31)
-
-
-def sample_indices(seed, hyp, n):
-    """MODEL_POINTS distinct indices in [0, n) for hypothesis `hyp`: successive hash draws, duplicates rejected
-    (the same integer arithmetic runs on the GPU)."""
-    out = []
-    ctr = 0
-    while len(out) < MODEL_POINTS:
-        r = _splitmix64((seed << 40) ^ (hyp << 8) ^ ctr)
-        ctr += 1
-        idx = int((r >> 11) % n)
-        if idx not in out:
-            out.append(idx)
-    return out
+# sample_indices(seed, hyp, n): the minimal set of hypothesis `hyp` (the same integer arithmetic runs on the GPU)
+sample_indices = functools.partial(ransac_common.sample_indices, k=MODEL_POINTS)
 
 
 # ---- EPnP -----------------------------------------------------------------------------------------------

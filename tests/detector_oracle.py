@@ -10,33 +10,16 @@ import functools
 
 import numpy as np
 
+from oracle import ransac_common
+from oracle.ransac_common import lane_tree_sum
+
 F64 = np.float64
 MIN_MATCHES = 6            # local_feature_2D_detector.py:93
 REPROJ_THRESHOLD = 6.0     # :105
 ITERATIONS = 2000          # OpenCV's default maxIters of estimateAffinePartial2D
 REFIT_LANES = 256          # the refit's reduction order: lane t sums the inliers t, t + 256, ..., then a binary tree over lanes
-_M64 = (1 << 64) - 1
-
-
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    z = x
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
-
-
-def sample_indices(seed, hyp, n):
-    """Two distinct indices in [0, n) for hypothesis `hyp`: successive hash draws, duplicates rejected (the construction of
-    the pose solver's sampler, for minimal sets of 2)."""
-    out, ctr = [], 0
-    while len(out) < 2:
-        r = _splitmix64(((seed << 40) & _M64) ^ (hyp << 8) ^ ctr)
-        ctr += 1
-        idx = int((r >> 11) % n)
-        if idx not in out:
-            out.append(idx)
-    return out
+# sample_indices(seed, hyp, n): the two matches of hypothesis `hyp` (the pose solver's sampler, for minimal sets of 2)
+sample_indices = functools.partial(ransac_common.sample_indices, k=2)
 
 
 @functools.lru_cache(maxsize=64)
@@ -75,23 +58,6 @@ def residual2(a, b, tx, ty, src, dst, dt=F64):
     return ex * ex + ey * ey
 
 
-def _lane_tree_sum(vals, dt=F64):
-    """Sum in the fixed order of the kernel: lane t adds vals[t], vals[t + 256], ... in turn, then a binary tree."""
-    n = len(vals)
-    rows = -(-max(n, 1) // REFIT_LANES)
-    buf = np.zeros(rows * REFIT_LANES, dtype=dt)
-    buf[:n] = vals
-    buf = buf.reshape(rows, REFIT_LANES)
-    acc = np.zeros(REFIT_LANES, dtype=dt)
-    for r in range(rows):
-        acc = acc + buf[r]
-    s = REFIT_LANES // 2
-    while s > 0:
-        acc = acc[:s] + acc[s:2 * s]
-        s //= 2
-    return acc[0]
-
-
 def refit(src, dst, mask, dt=F64):
     """Closed-form least squares of x' = [[a,-b],[b,a]] x + t over the inliers (centroids, two dot-product sums): the fixed
     point of the Levenberg-Marquardt refinement OpenCV runs.  -> 2x3 [[a, -b, tx], [b, a, ty]]."""
@@ -99,14 +65,14 @@ def refit(src, dst, mask, dt=F64):
     m = mask.astype(bool)
     z = dt(0)
     cnt = dt(int(m.sum()))
-    csx = _lane_tree_sum(np.where(m, s[:, 0], z), dt) / cnt
-    csy = _lane_tree_sum(np.where(m, s[:, 1], z), dt) / cnt
-    cdx = _lane_tree_sum(np.where(m, d[:, 0], z), dt) / cnt
-    cdy = _lane_tree_sum(np.where(m, d[:, 1], z), dt) / cnt
+    csx = lane_tree_sum(np.where(m, s[:, 0], z), REFIT_LANES) / cnt
+    csy = lane_tree_sum(np.where(m, s[:, 1], z), REFIT_LANES) / cnt
+    cdx = lane_tree_sum(np.where(m, d[:, 0], z), REFIT_LANES) / cnt
+    cdy = lane_tree_sum(np.where(m, d[:, 1], z), REFIT_LANES) / cnt
     ux, uy, wx, wy = s[:, 0] - csx, s[:, 1] - csy, d[:, 0] - cdx, d[:, 1] - cdy
-    suu = _lane_tree_sum(np.where(m, ux * ux + uy * uy, z), dt)
-    sdot = _lane_tree_sum(np.where(m, ux * wx + uy * wy, z), dt)
-    scr = _lane_tree_sum(np.where(m, ux * wy - uy * wx, z), dt)
+    suu = lane_tree_sum(np.where(m, ux * ux + uy * uy, z), REFIT_LANES)
+    sdot = lane_tree_sum(np.where(m, ux * wx + uy * wy, z), REFIT_LANES)
+    scr = lane_tree_sum(np.where(m, ux * wy - uy * wx, z), REFIT_LANES)
     a, b = sdot / suu, scr / suu
     return np.array([[a, -b, cdx - (a * csx - b * csy)], [b, a, cdy - (b * csx + a * csy)]], dtype=dt)
 

@@ -12,7 +12,7 @@ import math
 
 import numpy as np
 
-from detector_oracle import sample_indices
+from oracle.ransac_common import lane_tree_sum, sample_indices
 
 F64 = np.float64
 MAX_EPIPOLAR_ERROR = 4.0
@@ -136,24 +136,8 @@ def hypotheses(m, max_hypotheses=MAX_HYPOTHESES, seed=0):
     if m * (m - 1) // 2 <= max_hypotheses:
         a, b = np.triu_indices(m, 1)
         return a.astype(np.int64), b.astype(np.int64)
-    ab = np.array([sample_indices(seed, h, m) for h in range(max_hypotheses)], np.int64)
+    ab = np.array([sample_indices(seed, h, m, 2) for h in range(max_hypotheses)], np.int64)
     return ab[:, 0], ab[:, 1]
-
-
-def tree_sum(vals, lanes):
-    """vals [m, Q] summed as the kernel does: lane t adds the rows t, t + lanes, ... in turn, then v[t] += v[t + s] for
-    s = lanes / 2 .. 1."""
-    vals = np.asarray(vals)
-    m, q = vals.shape
-    part = np.zeros((lanes, q), vals.dtype)
-    for c0 in range(0, m, lanes):
-        chunk = vals[c0:c0 + lanes]
-        part[:len(chunk)] = part[:len(chunk)] + chunk
-    s = lanes // 2
-    while s > 0:
-        part[:s] = part[:s] + part[s:2 * s]
-        s //= 2
-    return part[0]
 
 
 def solve3(S, b):
@@ -180,7 +164,7 @@ def refit(cam, xy, inl, X0, refine_iterations=REFINE_ITERATIONS, dtype=F64):
     rows = np.stack([one - d[:, 0] * d[:, 0] / n2, -(d[:, 0] * d[:, 1] / n2), -(d[:, 0] * d[:, 2] / n2), one - d[:, 1] * d[:, 1] / n2,
                      -(d[:, 1] * d[:, 2] / n2), one - d[:, 2] * d[:, 2] / n2, C[:, 0] - d[:, 0] * qq, C[:, 1] - d[:, 1] * qq,
                      C[:, 2] - d[:, 2] * qq], axis=1)
-    s = tree_sum(np.where(sel, rows, dtype(0.0)), lanes)
+    s = lane_tree_sum(np.where(sel, rows, dtype(0.0)), lanes)
     X = np.asarray(X0, dtype).copy()
     lin = solve3(s[:6], s[6:])
     if lin is not None:
@@ -199,7 +183,7 @@ def refit(cam, xy, inl, X0, refine_iterations=REFINE_ITERATIONS, dtype=F64):
             rows = np.stack([J0[0] * J0[0] + J1[0] * J1[0], J0[0] * J0[1] + J1[0] * J1[1], J0[0] * J0[2] + J1[0] * J1[2],
                              J0[1] * J0[1] + J1[1] * J1[1], J0[1] * J0[2] + J1[1] * J1[2], J0[2] * J0[2] + J1[2] * J1[2],
                              J0[0] * rx + J1[0] * ry, J0[1] * rx + J1[1] * ry, J0[2] * rx + J1[2] * ry], axis=1)
-        s = tree_sum(np.where(sel, rows, dtype(0.0)), lanes)
+        s = lane_tree_sum(np.where(sel, rows, dtype(0.0)), lanes)
         dx = solve3(s[:6], s[6:])
         if dx is None:
             break

@@ -94,6 +94,46 @@ def test_hip_ransac_vs_oracle(n, outl, noise, seed):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [63, 64, 65, 1023, 1024, 1025, 2049])
+def test_hip_ransac_scan_pass_edges(n):
+    """The ordered compactions of best_kernel and gather_matches_kernel at the edges of a wave (64) and of a 1024-thread pass,
+    the carry between passes included (2049: three passes).  Noise-free problems: the oracle alone recovers the planted mask
+    (asserted first, on the CPU: a condition on the inputs), and the solver must then return exactly that mask."""
+    import torch
+    from onepose_amd import pnp
+    p = synthetic.make_pnp_problem(n, 0.3, 0.0, n)
+    planted = p["inlier_mask"]
+    ok, _, _, inl = po.solve_pnp_ransac(p["pts_3d"].astype(np.float64) * 1000, p["pts_2d"], p["K"], 5.0, 256, 5)
+    om = np.zeros(n, bool)
+    om[inl] = True
+    assert ok
+    np.testing.assert_array_equal(om, planted)
+    K = p["K"]
+    pose_b, mask_b, info_b = pnp.ransac_pnp_device(K, torch.from_numpy(p["pts_2d"]).cuda(), torch.from_numpy(p["pts_3d"]).cuda(),
+                                                   scale=1000, iterations=256, seed=5)
+    assert int(info_b[0]) == 1
+    np.testing.assert_array_equal(mask_b.cpu().numpy().astype(bool), planted)
+    assert int(info_b[1]) == int(planted.sum())                  # length of the ordered inlier list
+    # the same correspondences among n + 37 query keypoints, the unmatched ones spread over the whole range
+    rs = np.random.RandomState(n)
+    n1, n3 = n + 37, n + 91
+    kp2 = rs.uniform(0, 512, (n1, 2)).astype(np.float32)
+    kp3 = rs.uniform(-0.1, 0.1, (n3, 3)).astype(np.float32)
+    matches = -np.ones(n1, np.int64)
+    q = np.sort(rs.choice(n1, n, replace=False))
+    d = rs.choice(n3, n, replace=False)
+    kp2[q], kp3[d], matches[q] = p["pts_2d"], p["pts_3d"], d
+    if n1 > 1024:    # valid entries on both sides of the pass boundary, at positions that differ from their indices
+        assert (q < 1024).any() and (q >= 1024).any() and (matches[:1024] < 0).any()
+    pose_a, mask_a, info_a = pnp.ransac_pnp_from_matches(K, torch.from_numpy(kp2).cuda(), torch.from_numpy(kp3).cuda(),
+                                                          torch.from_numpy(matches).cuda(), scale=1000, iterations=256, seed=5)
+    assert torch.equal(info_a, info_b) and torch.equal(pose_a, pose_b)
+    full = np.zeros(n1, np.int32)
+    full[q] = mask_b.cpu().numpy()
+    np.testing.assert_array_equal(mask_a.cpu().numpy(), full)
+
+
+@pytest.mark.gpu
 def test_hip_epnp_vs_oracle_and_drop_in_signature():
     import torch
     from onepose_amd import pnp
