@@ -35,6 +35,7 @@ typedef struct ihipStream_t* sg_stream_t; /* hipStream_t */
 #define SG_MAX_LAYERS 64
 #define SG_LAYER_SELF 0
 #define SG_LAYER_CROSS 1
+#define SG_MAX_ITEMS 64 /* items of one ragged batch */
 /* float tensors of the reference state_dict (num_batches_tracked skipped): bin_score, 26 of kenc,
  * 16 per GNN layer, 2 of final_proj */
 #define SG_NUM_RAW(n_layers) (29 + 16 * (n_layers))
@@ -91,6 +92,41 @@ int sg_sinkhorn(const float* scores, const float* bin_score, int b, int n0, int 
  * columns (first index wins on exact ties), mutual check, exp, threshold. */
 int sg_match_tail(const float* z, int b, int n0, int n1, float match_threshold, int64_t* matches0, int64_t* matches1,
                   float* mscores0, float* mscores1, void* workspace, size_t workspace_bytes, sg_stream_t stream);
+
+/* ---- Ragged batch (sg_version() >= 2): b pairs, each with its own n0[i], n1[i] and image sizes, in one chain of launches.
+ *
+ * Inputs are padded to the capacities cap0 / cap1: keypoints [b][cap][2], scores [b][cap], descriptors [b][256][cap].
+ * n0, n1 ([b]) and hw0, hw1 ([b][2], (h, w) per item) are HOST int32 arrays, like layer_kinds; they travel to the kernels by
+ * value, so the library still allocates nothing, copies nothing from host memory and never synchronises.
+ *   - 1 <= b <= SG_MAX_ITEMS, and every item has 1 <= n0[i] <= cap0 and 1 <= n1[i] <= cap1 (an item with an empty side
+ *     is the caller's to answer, as for sg_forward).
+ *   - Nothing past an item's counts is read: padded input entries and stale workspace contents may hold anything.
+ *   - Outputs matches0 / mscores0 [b][cap0], matches1 / mscores1 [b][cap1]; entries past an item's count are -1 / 0.f.
+ *   - In z_out ([b][cap0+1][cap1+1]) item i occupies rows 0..n0[i] and columns 0..n1[i] of its slot at row stride cap1 + 1
+ *     (the dustbin row is row n0[i], the dustbin column is column n1[i]); in a scores input ([b][cap0][cap1]) rows
+ *     0..n0[i]-1 and columns 0..n1[i]-1 at row stride cap1.  The rest of a slot is unspecified.
+ *   - Every item's outputs are bitwise those of the same pair run alone through the uniform entry points: the order of every
+ *     reduction depends on the item's own counts, never on the capacities or on the other items.
+ *   - All argument validation happens before the first HIP call: a bad argument returns -1 (a short workspace -2) with a
+ *     message, also on a machine without a GPU.
+ * sg_ragged_workspace_bytes returns 0 for a shape it refuses. */
+size_t sg_ragged_workspace_bytes(int b, int cap0, int cap1);
+
+int sg_forward_ragged(const float* packed, int n_layers, const int32_t* layer_kinds, int sinkhorn_iters, float match_threshold,
+                      const float* kpts0, const float* scores0, const float* desc0,
+                      const float* kpts1, const float* scores1, const float* desc1,
+                      int b, int cap0, int cap1, const int32_t* n0, const int32_t* n1, const int32_t* hw0, const int32_t* hw1,
+                      int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* z_out,
+                      void* workspace, size_t workspace_bytes, sg_stream_t stream);
+
+/* Ragged stages, for tests: sg_attention (q [b][256][capN], kv [b][512][capM], n / m HOST [b]), sg_sinkhorn and sg_match_tail. */
+int sg_attention_ragged(const float* q, const float* kv, int b, int capN, int capM, const int32_t* n, const int32_t* m,
+                        float* out, sg_stream_t stream);
+int sg_sinkhorn_ragged(const float* scores, const float* bin_score, int b, int cap0, int cap1, const int32_t* n0,
+                       const int32_t* n1, int iters, float* z_out, void* workspace, size_t workspace_bytes, sg_stream_t stream);
+int sg_match_tail_ragged(const float* z, int b, int cap0, int cap1, const int32_t* n0, const int32_t* n1, float match_threshold,
+                         int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                         void* workspace, size_t workspace_bytes, sg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ from ._binding import bind
 from .build_ext import SG_LIB_PATH as LIB_PATH
 
 LAYER_SELF, LAYER_CROSS = 0, 1
+MAX_ITEMS = 64          # SG_MAX_ITEMS: items of one ragged batch
 
 
 def num_raw(n_layers):
@@ -19,6 +20,7 @@ def num_raw(n_layers):
 
 
 _P = c_void_p
+_I = POINTER(c_int32)   # a HOST int32 array
 # name -> (restype, argtypes); every symbol include/superglue/superglue.h declares
 SYMBOLS = {
     "sg_version": (c_int, []),
@@ -34,6 +36,12 @@ SYMBOLS = {
     "sg_attention": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "sg_sinkhorn": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "sg_match_tail": (c_int, [_P, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sg_ragged_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sg_forward_ragged": (c_int, [_P, c_int, POINTER(c_int32), c_int, c_float, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _I, _I, _I,
+                                  _I, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sg_attention_ragged": (c_int, [_P, _P, c_int, c_int, c_int, _I, _I, _P, _P]),
+    "sg_sinkhorn_ragged": (c_int, [_P, _P, c_int, c_int, c_int, _I, _I, c_int, _P, _P, c_size_t, _P]),
+    "sg_match_tail_ragged": (c_int, [_P, c_int, c_int, c_int, _I, _I, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

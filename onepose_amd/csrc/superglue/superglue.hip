@@ -68,6 +68,22 @@ __global__ void sg_copy_perm_kernel(float* dst, const float* src, int rows, int 
     dst[i] = src[size_t(sr) * cols + sc];
 }
 
+// ---- per-item counts ----
+// A batch is b items; item i matches n[0][i] points of side 0 against n[1][i] points of side 1.  The table travels by value in
+// the kernel arguments (the library copies nothing from host memory), so every lookup is a scalar load at a block-uniform
+// index.  A uniform batch (sg_forward: one n0, one n1, any b) is the table with `uniform` set and entry 0 filled.  Buffers
+// are laid out by the capacities (cap0, cap1); a kernel bounds its loops, masks and stores by the item's own counts, so the
+// order of every reduction depends on the item alone and nothing past an item's counts is ever read.
+struct Items {
+    int n[2][SG_MAX_ITEMS];
+    int uniform;
+    __host__ __device__ int slot(int bi) const { return uniform ? 0 : bi; }
+    __host__ __device__ int count(int s, int bi) const { return n[s][slot(bi)]; }
+};
+struct Marginals {   // log_optimal_transport's (:157-165), per item, computed on the host
+    float norm[SG_MAX_ITEMS], mu_last[SG_MAX_ITEMS], nu_last[SG_MAX_ITEMS];
+};
+
 // ---- fp32 MFMA GEMM: C[m][n] = epilogue( sum_k A[m][k] B[k][n] ), 64x64 tiles, 4 waves of 32x32, K slabs of 32 ----
 struct GemmJob {
     const float* A; long sA;          // row-major [M][K] (lda) or, with a_km, [K][M] (lda); batch stride sA
@@ -78,23 +94,26 @@ struct GemmJob {
     float* C; long sC; int ldc;
     float* Ct; long sCt; int ldct;    // optional transposed copy: Ct[n][m]
     const float* R; long sR;          // optional residual (ld = ldc): C = R + epilogue
-    int M, N;
+    int M, N;                         // capacities: N is the leading dimension of B / B2
+    int msel, nsel;                   // rows / columns of an item: count(msel) (M itself if msel < 0), count(nsel)
 };
 struct GemmArgs {
     GemmJob job[4];
     int njobs, b, K, ksplit, lda, a_km, relu;
     float scale;                      // applied to the accumulator first (1 = none)
+    Items items;
 };
 
 __global__ __launch_bounds__(256) void sg_gemm_kernel(GemmArgs p) {
     const int jz = blockIdx.z / p.b, bi = blockIdx.z % p.b;
     const GemmJob& J = p.job[jz];
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    if (m0 >= J.M || n0 >= J.N) return;
+    const int M = J.msel < 0 ? J.M : p.items.count(J.msel, bi), N = p.items.count(J.nsel, bi);
+    if (m0 >= M || n0 >= N) return;
     const float* A = J.A + bi * J.sA;
     const float* B = J.B + bi * J.sB;
     const float* B2 = J.B2 ? J.B2 + bi * J.sB2 : nullptr;
-    const int M = J.M, N = J.N, K = p.K, lda = p.lda;
+    const int K = p.K, lda = p.lda, ldb = J.N;
 
     __shared__ float As[32][64 + 4];
     __shared__ float Bs[32][64 + 4];
@@ -119,11 +138,11 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(GemmArgs p) {
             }
         }
         const bool second = k0 >= p.ksplit;
-        const float* Bp = second ? B2 + size_t(k0 - p.ksplit) * N : B + size_t(k0) * N;
+        const float* Bp = second ? B2 + size_t(k0 - p.ksplit) * ldb : B + size_t(k0) * ldb;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int kk = (tid >> 6) + 4 * i, n = tid & 63;
-            rb[i] = (n0 + n < N) ? Bp[size_t(kk) * N + n0 + n] : 0.f;
+            rb[i] = (n0 + n < N) ? Bp[size_t(kk) * ldb + n0 + n] : 0.f;
         }
     };
     auto store = [&]() {
@@ -169,7 +188,7 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(GemmArgs p) {
         float v = acc[r];
         if (p.scale != 1.f) v *= p.scale;
         if (J.bias) v += J.bias[m];
-        if (J.bn) v = (v - J.bn[m]) / sqrtf(J.bn[M + m] + BN_EPS) * J.bn[2 * M + m] + J.bn[3 * M + m];
+        if (J.bn) v = (v - J.bn[m]) / sqrtf(J.bn[J.M + m] + BN_EPS) * J.bn[2 * J.M + m] + J.bn[3 * J.M + m];
         if (p.relu) v = fmaxf(v, 0.f);
         if (R) v = R[size_t(m) * J.ldc + n] + v;
         C[size_t(m) * J.ldc + n] = v;
@@ -184,30 +203,33 @@ struct AttnSide {
     const float* q; long sq;     // [256][N] head-contiguous
     const float* kv; long skv;   // [512][M]: k rows 0..255, v rows 256..511, head-contiguous
     float* out; long so;         // [256][N]
-    int N, M;
+    int N, M;                    // capacities (leading dimensions); N == 0: a side without blocks
+    int nsel, msel;              // queries / sources of an item: count(nsel), count(msel)
 };
 struct AttnArgs {
     AttnSide side[2];
     int b;
+    Items items;
 };
 
 __global__ __launch_bounds__(256) void sg_attn_kernel(AttnArgs p) {
     const int sd = blockIdx.z / p.b, bi = blockIdx.z % p.b, hd = blockIdx.y;
     const AttnSide& S = p.side[sd];
-    const int N = S.N, M = S.M, q0 = blockIdx.x * 128;
+    const int ldn = S.N, ldm = S.M, q0 = blockIdx.x * 128;
+    const int N = ldn ? p.items.count(S.nsel, bi) : 0, M = p.items.count(S.msel, bi);
     if (q0 >= N) return;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, half = l >> 5, c = l & 31;
     const int myq = q0 + w * 32 + c;
-    const float* Q = S.q + bi * S.sq + size_t(hd) * 64 * N;
-    const float* Kp = S.kv + bi * S.skv + size_t(hd) * 64 * M;
-    const float* Vp = Kp + size_t(D) * M;
+    const float* Q = S.q + bi * S.sq + size_t(hd) * 64 * ldn;
+    const float* Kp = S.kv + bi * S.skv + size_t(hd) * 64 * ldm;
+    const float* Vp = Kp + size_t(D) * ldm;
 
     __shared__ float Ks[64][64];
     __shared__ float Vt[64][65];
 
     float qr[32];
 #pragma unroll
-    for (int s = 0; s < 32; ++s) qr[s] = myq < N ? Q[size_t(2 * s + half) * N + myq] * 0.125f : 0.f;   // 1/sqrt(64): exact
+    for (int s = 0; s < 32; ++s) qr[s] = myq < N ? Q[size_t(2 * s + half) * ldn + myq] * 0.125f : 0.f;   // 1/sqrt(64): exact
 
     f32x16 o0, o1;
 #pragma unroll
@@ -220,8 +242,8 @@ __global__ __launch_bounds__(256) void sg_attn_kernel(AttnArgs p) {
         for (int i = 0; i < 16; ++i) {
             const int src = tid & 63, d = (tid >> 6) + 4 * i;
             const bool ok = j0 + src < M;
-            Ks[d][src] = ok ? Kp[size_t(d) * M + j0 + src] : 0.f;
-            Vt[src][d] = ok ? Vp[size_t(d) * M + j0 + src] : 0.f;
+            Ks[d][src] = ok ? Kp[size_t(d) * ldm + j0 + src] : 0.f;
+            Vt[src][d] = ok ? Vp[size_t(d) * ldm + j0 + src] : 0.f;
         }
         __syncthreads();
         f32x16 s0, s1;
@@ -269,18 +291,20 @@ __global__ __launch_bounds__(256) void sg_attn_kernel(AttnArgs p) {
     }
     if (myq >= N) return;
     const float inv = 1.f / lrun;
-    float* O = S.out + bi * S.so + size_t(hd) * 64 * N;
+    float* O = S.out + bi * S.so + size_t(hd) * 64 * ldn;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        O[size_t(mfma_row(r, half)) * N + myq] = o0[r] * inv;
-        O[size_t(32 + mfma_row(r, half)) * N + myq] = o1[r] * inv;
+        O[size_t(mfma_row(r, half)) * ldn + myq] = o0[r] * inv;
+        O[size_t(32 + mfma_row(r, half)) * ldn + myq] = o1[r] * inv;
     }
 }
 
 // ---- keypoint encoder, layers 0..2 (3 -> 32 -> 64 -> 128, BatchNorm + ReLU) per point; layers 3, 4 run as GEMMs ----
 struct KencSide {
-    const float* kpts; const float* scores; float* h3;   // h3: [b][128][N]
+    const float* kpts; const float* scores; float* h3;   // [b][N][2], [b][N], h3: [b][128][N]; N: the side's capacity
     int N;
+};
+struct KencNorm {
     float cx, cy, sc;                                     // normalisation: (k - c) / sc
 };
 struct KencArgs {
@@ -288,6 +312,8 @@ struct KencArgs {
     const float* w;   // packed weights
     size_t w0, b0, bn0, w1, b1, bn1, w2, b2, bn2;
     int b;
+    Items items;
+    KencNorm norm[2][SG_MAX_ITEMS];                       // per side and item slot
 };
 
 __device__ __forceinline__ float bn_relu(float v, const float* bn, int C, int o) {
@@ -299,9 +325,10 @@ __global__ __launch_bounds__(256) void sg_kenc_kernel(KencArgs p) {
     const int sd = blockIdx.z / p.b, bi = blockIdx.z % p.b;
     const KencSide& S = p.side[sd];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.N) return;
+    if (i >= p.items.count(sd, bi)) return;
+    const KencNorm& nm = p.norm[sd][p.items.slot(bi)];
     const float* kp = S.kpts + (size_t(bi) * S.N + i) * 2;
-    const float in[3] = {(kp[0] - S.cx) / S.sc, (kp[1] - S.cy) / S.sc, S.scores[size_t(bi) * S.N + i]};
+    const float in[3] = {(kp[0] - nm.cx) / nm.sc, (kp[1] - nm.cy) / nm.sc, S.scores[size_t(bi) * S.N + i]};
     const float* W0 = p.w + p.w0; const float* B0 = p.w + p.b0; const float* N0 = p.w + p.bn0;
     const float* W1 = p.w + p.w1; const float* B1 = p.w + p.b1; const float* N1 = p.w + p.bn1;
     const float* W2 = p.w + p.w2; const float* B2 = p.w + p.b2; const float* N2 = p.w + p.bn2;
@@ -330,34 +357,36 @@ __global__ __launch_bounds__(256) void sg_kenc_kernel(KencArgs p) {
 }
 
 // ---- log-space Sinkhorn ----
-// Coupling Z [b][n0+1][n1+1] and its transpose Zt [b][n1+1][n0+1] (bitwise the same values), so both the row update (u) and
-// the column update (v) are contiguous row logsumexps: one wave per row, a fixed-order online (max, sum) per lane and a
-// fixed butterfly across lanes.  Two launches per iteration.
+// Coupling Z [b][cap0+1][cap1+1] and its transpose Zt [b][cap1+1][cap0+1] (bitwise the same values); item i occupies rows
+// 0..n0_i and columns 0..n1_i of its slot.  Both the row update (u) and the column update (v) are contiguous row
+// logsumexps: one wave per row, a fixed-order online (max, sum) per lane and a fixed butterfly across lanes.  Two launches
+// per iteration.
 
-// copy == 1: Z / Zt interior from scores [b][n0][n1] and the dustbins; copy == 0: dustbins only (the score GEMM wrote the
+// copy == 1: Z / Zt interior from scores [b][cap0][cap1] and the dustbins; copy == 0: dustbins only (the score GEMM wrote the
 // interior).  Zeroes u and v either way (iters == 0 leaves them at zero).
-__global__ void sg_sk_build_kernel(const float* scores, const float* bin, float* Z, float* Zt, float* u, float* v, int n0, int n1,
-                                   int copy) {
-    const int bi = blockIdx.y;
-    const size_t zsz = size_t(n0 + 1) * (n1 + 1);
+__global__ void sg_sk_build_kernel(const float* scores, const float* bin, float* Z, float* Zt, float* u, float* v, int cap0, int cap1,
+                                   int copy, Items T) {
+    const int bi = blockIdx.y, n0 = T.count(0, bi), n1 = T.count(1, bi);
+    const size_t zsz = size_t(cap0 + 1) * (cap1 + 1);
     float* z = Z + bi * zsz;
     float* zt = Zt + bi * zsz;
     const float alpha = bin[0];
     const long i = long(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i <= n0) u[size_t(bi) * (n0 + 1) + i] = 0.f;
-    if (i <= n1) v[size_t(bi) * (n1 + 1) + i] = 0.f;
+    if (i <= n0) u[size_t(bi) * (cap0 + 1) + i] = 0.f;
+    if (i <= n1) v[size_t(bi) * (cap1 + 1) + i] = 0.f;
+    int r, cc;
+    float val = alpha;
     if (copy) {
         if (i >= long(zsz)) return;
-        const int r = int(i / (n1 + 1)), cc = int(i % (n1 + 1));
-        const float val = (r < n0 && cc < n1) ? scores[size_t(bi) * n0 * n1 + size_t(r) * n1 + cc] : alpha;
-        z[i] = val;
-        zt[size_t(cc) * (n0 + 1) + r] = val;
+        r = int(i / (cap1 + 1)); cc = int(i % (cap1 + 1));
+        if (r > n0 || cc > n1) return;
+        if (r < n0 && cc < n1) val = scores[size_t(bi) * cap0 * cap1 + size_t(r) * cap1 + cc];
     } else {
         if (i > n0 + n1) return;
-        const int r = i < n0 ? int(i) : n0, cc = i < n0 ? n1 : int(i - n0);
-        z[size_t(r) * (n1 + 1) + cc] = alpha;
-        zt[size_t(cc) * (n0 + 1) + r] = alpha;
+        r = i < n0 ? int(i) : n0; cc = i < n0 ? n1 : int(i - n0);
     }
+    z[size_t(r) * (cap1 + 1) + cc] = val;
+    zt[size_t(cc) * (cap0 + 1) + r] = val;
 }
 
 __device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
@@ -367,13 +396,16 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os
     m = mn;
 }
 
-// out[row] = (row < rows - 1 ? lm : lm_last) - logsumexp_j(Zm[row][j] + in[j])
-__global__ __launch_bounds__(256) void sg_sk_rows_kernel(const float* Zm, const float* in, float* out, int rows, int cols, float lm,
-                                                         float lm_last) {
+// out[row] = (row < rows - 1 ? norm : last) - logsumexp_j(Zm[row][j] + in[j]) over the item's rows x cols of a slot of
+// caprows x capcols; side 0: Zm = Z (rows n0 + 1, last = mu_last), side 1: Zm = Zt (rows n1 + 1, last = nu_last)
+__global__ __launch_bounds__(256) void sg_sk_rows_kernel(const float* Zm, const float* in, float* out, int side, int caprows,
+                                                         int capcols, Items T, Marginals mg) {
     const int bi = blockIdx.y, row = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    const int rows = T.count(side, bi) + 1, cols = T.count(1 - side, bi) + 1;
     if (row >= rows) return;
-    const float* z = Zm + bi * size_t(rows) * cols + size_t(row) * cols;
-    const float* vi = in + size_t(bi) * cols;
+    const float lm = mg.norm[T.slot(bi)], lm_last = side ? mg.nu_last[T.slot(bi)] : mg.mu_last[T.slot(bi)];
+    const float* z = Zm + bi * size_t(caprows) * capcols + size_t(row) * capcols;
+    const float* vi = in + size_t(bi) * capcols;
     float m = -INFINITY, s = 0.f;
     for (int j = l; j < cols; j += 64) {
         const float x = z[j] + vi[j];
@@ -385,18 +417,20 @@ __global__ __launch_bounds__(256) void sg_sk_rows_kernel(const float* Zm, const 
         const float om = __shfl_xor(m, off), os = __shfl_xor(s, off);
         lse_merge(m, s, om, os);
     }
-    if (l == 0) out[size_t(bi) * rows + row] = (row < rows - 1 ? lm : lm_last) - (m + logf(s));
+    if (l == 0) out[size_t(bi) * caprows + row] = (row < rows - 1 ? lm : lm_last) - (m + logf(s));
 }
 
 // Zo = Z + u + v - norm (reference op order)
-__global__ void sg_sk_final_kernel(const float* Z, const float* u, const float* v, float* Zo, int n0, int n1, float norm) {
+__global__ void sg_sk_final_kernel(const float* Z, const float* u, const float* v, float* Zo, int cap0, int cap1, Items T, Marginals mg) {
     const int bi = blockIdx.y;
-    const size_t zsz = size_t(n0 + 1) * (n1 + 1);
+    const size_t zsz = size_t(cap0 + 1) * (cap1 + 1);
     const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= zsz) return;
-    const int r = int(i / (n1 + 1)), cc = int(i % (n1 + 1));
-    const float z = Z[bi * zsz + i] + u[size_t(bi) * (n0 + 1) + r];
-    Zo[bi * zsz + i] = (z + v[size_t(bi) * (n1 + 1) + cc]) - norm;
+    const int r = int(i / (cap1 + 1)), cc = int(i % (cap1 + 1));
+    if (r > T.count(0, bi) || cc > T.count(1, bi)) return;
+    const float norm = mg.norm[T.slot(bi)];
+    const float z = Z[bi * zsz + i] + u[size_t(bi) * (cap0 + 1) + r];
+    Zo[bi * zsz + i] = (z + v[size_t(bi) * (cap1 + 1) + cc]) - norm;
 }
 
 // ---- match tail ----
@@ -405,10 +439,11 @@ __device__ __forceinline__ void argmax_merge(float& best, int& idx, float ob, in
 }
 
 // max / argmax of z[i][0..n1) for i < n0: one wave per row, first index wins on exact ties
-__global__ __launch_bounds__(256) void sg_row_argmax_kernel(const float* Z, int n0, int n1, float* mx, int* ix) {
+__global__ __launch_bounds__(256) void sg_row_argmax_kernel(const float* Z, int cap0, int cap1, Items T, float* mx, int* ix) {
     const int bi = blockIdx.y, row = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    const int n0 = T.count(0, bi), n1 = T.count(1, bi);
     if (row >= n0) return;
-    const float* z = Z + bi * size_t(n0 + 1) * (n1 + 1) + size_t(row) * (n1 + 1);
+    const float* z = Z + bi * size_t(cap0 + 1) * (cap1 + 1) + size_t(row) * (cap1 + 1);
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int j = l; j < n1; j += 64) {
@@ -421,22 +456,24 @@ __global__ __launch_bounds__(256) void sg_row_argmax_kernel(const float* Z, int 
         const int oi = __shfl_xor(idx, off);
         argmax_merge(best, idx, ob, oi);
     }
-    if (l == 0) { mx[size_t(bi) * n0 + row] = best; ix[size_t(bi) * n0 + row] = idx; }
+    if (l == 0) { mx[size_t(bi) * cap0 + row] = best; ix[size_t(bi) * cap0 + row] = idx; }
 }
 
-// column partials over chunks of 256 rows: thread (column, quarter of 64 rows), quarters merged in row order
-__global__ __launch_bounds__(256) void sg_col_partial_kernel(const float* Z, int n0, int n1, float* pv, int* pi) {
+// column partials over chunks of 256 rows: thread (column, quarter of 64 rows), quarters merged in row order; a chunk past
+// the item's rows has no block
+__global__ __launch_bounds__(256) void sg_col_partial_kernel(const float* Z, int cap0, int cap1, Items T, float* pv, int* pi) {
     const int bi = blockIdx.z, chunk = blockIdx.y, col = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-    const int nchunk = gridDim.y;
+    const int nchunk = gridDim.y, n0 = T.count(0, bi), n1 = T.count(1, bi);
+    if (chunk * 256 >= n0) return;
     __shared__ float sv[4][64];
     __shared__ int si[4][64];
     float best = -INFINITY;
     int idx = 0x7fffffff;
     if (col < n1) {
-        const float* z = Z + bi * size_t(n0 + 1) * (n1 + 1) + col;
+        const float* z = Z + bi * size_t(cap0 + 1) * (cap1 + 1) + col;
         const int r0 = chunk * 256 + q * 64, r1 = min(r0 + 64, n0);
         for (int r = r0; r < r1; ++r) {
-            const float x = z[size_t(r) * (n1 + 1)];
+            const float x = z[size_t(r) * (cap1 + 1)];
             if (x > best || idx == 0x7fffffff) { best = x; idx = r; }
         }
     }
@@ -445,56 +482,69 @@ __global__ __launch_bounds__(256) void sg_col_partial_kernel(const float* Z, int
     __syncthreads();
     if (q == 0 && col < n1) {
         for (int k = 1; k < 4; ++k) argmax_merge(best, idx, sv[k][threadIdx.x], si[k][threadIdx.x]);
-        pv[(size_t(bi) * nchunk + chunk) * n1 + col] = best;
-        pi[(size_t(bi) * nchunk + chunk) * n1 + col] = idx;
+        pv[(size_t(bi) * nchunk + chunk) * cap1 + col] = best;
+        pi[(size_t(bi) * nchunk + chunk) * cap1 + col] = idx;
     }
 }
 
-__global__ void sg_col_final_kernel(const float* pv, const int* pi, int nchunk, int n1, float* mx, int* ix) {
+// merges the item's own chunks in order; `nchunk` (of cap0) is the layout of pv / pi
+__global__ void sg_col_final_kernel(const float* pv, const int* pi, int nchunk, int cap1, Items T, float* mx, int* ix) {
     const int bi = blockIdx.y, col = blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= n1) return;
+    if (col >= T.count(1, bi)) return;
+    const int mine = (T.count(0, bi) + 255) / 256;
     float best = -INFINITY;
     int idx = 0x7fffffff;
-    for (int k = 0; k < nchunk; ++k)
-        argmax_merge(best, idx, pv[(size_t(bi) * nchunk + k) * n1 + col], pi[(size_t(bi) * nchunk + k) * n1 + col]);
-    mx[size_t(bi) * n1 + col] = best;
-    ix[size_t(bi) * n1 + col] = idx;
+    for (int k = 0; k < mine; ++k)
+        argmax_merge(best, idx, pv[(size_t(bi) * nchunk + k) * cap1 + col], pi[(size_t(bi) * nchunk + k) * cap1 + col]);
+    mx[size_t(bi) * cap1 + col] = best;
+    ix[size_t(bi) * cap1 + col] = idx;
 }
 
 __device__ __forceinline__ float mscore0(const float* mx0, const int* ix0, const int* ix1, int i) {
     return ix1[ix0[i]] == i ? expf(mx0[i]) : 0.f;
 }
 
-// mutual check, exp, threshold (reference :257-268), one thread per point of either side
-__global__ void sg_tail_kernel(const float* mx0, const int* ix0, const float* mx1, const int* ix1, int n0, int n1, float th,
-                               int64_t* m0, int64_t* m1, float* s0, float* s1) {
+// mutual check, exp, threshold (reference :257-268), one thread per point of either side; -1 / 0 past an item's counts
+__global__ void sg_tail_kernel(const float* mx0, const int* ix0, const int* ix1, int cap0, int cap1, Items T, float th, int64_t* m0,
+                               int64_t* m1, float* s0, float* s1) {
     const int bi = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n0 + n1) return;
-    const float* x0 = mx0 + size_t(bi) * n0;
-    const int* i0 = ix0 + size_t(bi) * n0;
-    const int* i1 = ix1 + size_t(bi) * n1;
-    if (k < n0) {
-        const bool mutual = i1[i0[k]] == k;
-        const float ms = mutual ? expf(x0[k]) : 0.f;
-        const bool valid = mutual && ms > th;
-        m0[size_t(bi) * n0 + k] = valid ? i0[k] : -1;
-        s0[size_t(bi) * n0 + k] = ms;
+    if (k >= cap0 + cap1) return;
+    const int n0 = T.count(0, bi), n1 = T.count(1, bi);
+    const float* x0 = mx0 + size_t(bi) * cap0;
+    const int* i0 = ix0 + size_t(bi) * cap0;
+    const int* i1 = ix1 + size_t(bi) * cap1;
+    if (k < cap0) {
+        int64_t m = -1;
+        float ms = 0.f;
+        if (k < n0) {
+            const bool mutual = i1[i0[k]] == k;
+            ms = mutual ? expf(x0[k]) : 0.f;
+            if (mutual && ms > th) m = i0[k];
+        }
+        m0[size_t(bi) * cap0 + k] = m;
+        s0[size_t(bi) * cap0 + k] = ms;
     } else {
-        const int j = k - n0, i = i1[j];
-        const bool mutual = i0[i] == j;
-        const float ms0 = mscore0(x0, i0, i1, i);
-        const bool valid0 = (i1[i0[i]] == i) && ms0 > th;
-        m1[size_t(bi) * n1 + j] = (mutual && valid0) ? i : -1;
-        s1[size_t(bi) * n1 + j] = mutual ? ms0 : 0.f;
+        const int j = k - cap0;
+        int64_t m = -1;
+        float ms = 0.f;
+        if (j < n1) {
+            const int i = i1[j];
+            const bool mutual = i0[i] == j;
+            const float ms0 = mscore0(x0, i0, i1, i);
+            const bool valid0 = (i1[i0[i]] == i) && ms0 > th;
+            if (mutual && valid0) m = i;
+            ms = mutual ? ms0 : 0.f;
+        }
+        m1[size_t(bi) * cap1 + j] = m;
+        s1[size_t(bi) * cap1 + j] = ms;
     }
-    (void)mx1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------------------------
 struct Layout {
-    int b, n0, n1, nm;
+    int b, n0, n1, nm;       // n0 / n1: the capacities of the two sides (the counts themselves for a uniform batch)
     size_t side_floats[7];   // per-side channel counts of the activation buffers below
     size_t xa, xb, q, kv, msg, mrg, hb, z, zt, u, v, mx0, ix0, mx1, ix1, pv, pi, total;
     int nchunk;
@@ -524,12 +574,24 @@ struct Ctx {
     char* ws;
     hipStream_t st;
     const float* w;
+    Items items;
     // side s of a per-side activation buffer with `ch` channels
     float* buf(size_t off, int ch, int s) const { return reinterpret_cast<float*>(ws + off) + size_t(s) * ch * L.b * L.nm; }
-    int n(int s) const { return s ? L.n1 : L.n0; }
+    int n(int s) const { return s ? L.n1 : L.n0; }   // capacity of side s: leading dimension and grid extent
+    int slots() const { return items.uniform ? 1 : L.b; }
     float* f(size_t off) const { return reinterpret_cast<float*>(ws + off); }
     int* i(size_t off) const { return reinterpret_cast<int*>(ws + off); }
 };
+
+Items uniform_items(int n0, int n1) {
+    Items t{};
+    t.uniform = 1; t.n[0][0] = n0; t.n[1][0] = n1;
+    return t;
+}
+
+Ctx make_ctx(int b, int cap0, int cap1, const Items& items, void* ws, sg_stream_t stream, const float* packed) {
+    return Ctx{make_layout(b, cap0, cap1), static_cast<char*>(ws), reinterpret_cast<hipStream_t>(stream), packed, items};
+}
 
 int launch_status(const char* what) { return check_launch(-3, what, ": launch failed: "); }
 
@@ -542,9 +604,24 @@ int check_common(int b, int n0, int n1, void* ws, size_t ws_bytes) {
     return 0;
 }
 
-GemmJob job(const float* A, const float* bias, const float* bn, const float* B, long sB, float* C, long sC, int M, int N) {
+// the table of a ragged batch from its host arrays; everything is checked here, before any HIP call
+int check_ragged(int b, int cap0, int cap1, const int32_t* n0, const int32_t* n1, Items* items) {
+    if (b < 1 || b > SG_MAX_ITEMS) return fail(-1, "b must be in [1, %d] (got %d)", SG_MAX_ITEMS, b);
+    if (cap0 < 1 || cap1 < 1) return fail(-1, "cap0, cap1 must be >= 1 (got %d, %d)", cap0, cap1);
+    if (!n0 || !n1) return fail(-1, "n0 / n1 (host arrays) are null");
+    *items = Items{};
+    for (int i = 0; i < b; ++i) {
+        if (n0[i] < 1 || n0[i] > cap0) return fail(-1, "item %d: n0 = %d is outside [1, cap0 = %d]", i, n0[i], cap0);
+        if (n1[i] < 1 || n1[i] > cap1) return fail(-1, "item %d: n1 = %d is outside [1, cap1 = %d]", i, n1[i], cap1);
+        items->n[0][i] = n0[i]; items->n[1][i] = n1[i];
+    }
+    return 0;
+}
+
+GemmJob job(const float* A, const float* bias, const float* bn, const float* B, long sB, float* C, long sC, int M, int N, int nsel) {
     GemmJob j{};
     j.A = A; j.bias = bias; j.bn = bn; j.B = B; j.sB = sB; j.C = C; j.sC = sC; j.ldc = N; j.M = M; j.N = N;
+    j.msel = -1; j.nsel = nsel;
     return j;
 }
 
@@ -552,6 +629,7 @@ int gemm(const Ctx& c, GemmArgs& a, const char* what) {
     int maxm = 0, maxn = 0;
     for (int k = 0; k < a.njobs; ++k) { maxm = std::max(maxm, a.job[k].M); maxn = std::max(maxn, a.job[k].N); }
     a.b = c.L.b;
+    a.items = c.items;
     if (a.scale == 0.f) a.scale = 1.f;
     if (a.ksplit == 0) a.ksplit = a.K;
     dim3 grid((maxn + 63) / 64, (maxm + 63) / 64, a.njobs * c.L.b);
@@ -561,17 +639,21 @@ int gemm(const Ctx& c, GemmArgs& a, const char* what) {
 
 float norm_scale(int h, int w) { return float(std::max(h, w)) * 0.7f; }
 
-int run_kenc(const Ctx& c, const float* const kp[2], const float* const sc[2], const float* const desc[2], const int hw[2][2],
+// hw[s]: HOST (h, w) of side s per item slot
+int run_kenc(const Ctx& c, const float* const kp[2], const float* const sc[2], const float* const desc[2], const int32_t* const hw[2],
              float* const out[2]) {
     const KencOff o = kenc_offsets();
     KencArgs ka{};
-    ka.w = c.w; ka.b = c.L.b;
+    ka.w = c.w; ka.b = c.L.b; ka.items = c.items;
     ka.w0 = o.w[0]; ka.b0 = o.b[0]; ka.bn0 = o.bn[0];
     ka.w1 = o.w[1]; ka.b1 = o.b[1]; ka.bn1 = o.bn[1];
     ka.w2 = o.w[2]; ka.b2 = o.b[2]; ka.bn2 = o.bn[2];
     for (int s = 0; s < 2; ++s) {
-        const int h = hw[s][0], w = hw[s][1];
-        ka.side[s] = KencSide{kp[s], sc[s], c.buf(c.L.mrg, CH_MRG, s), c.n(s), float(w) / 2.f, float(h) / 2.f, norm_scale(h, w)};
+        ka.side[s] = KencSide{kp[s], sc[s], c.buf(c.L.mrg, CH_MRG, s), c.n(s)};
+        for (int i = 0; i < c.slots(); ++i) {
+            const int h = hw[s][2 * i], w = hw[s][2 * i + 1];
+            ka.norm[s][i] = KencNorm{float(w) / 2.f, float(h) / 2.f, norm_scale(h, w)};
+        }
     }
     dim3 grid((c.L.nm + 255) / 256, 1, 2 * c.L.b);
     hipLaunchKernelGGL(sg_kenc_kernel, grid, dim3(256), 0, c.st, ka);
@@ -581,20 +663,20 @@ int run_kenc(const Ctx& c, const float* const kp[2], const float* const sc[2], c
     g3.njobs = 2; g3.K = 128; g3.lda = 128; g3.relu = 1;
     for (int s = 0; s < 2; ++s)
         g3.job[s] = job(c.w + o.w[3], c.w + o.b[3], c.w + o.bn[3], c.buf(c.L.mrg, CH_MRG, s), 128L * c.n(s),
-                        c.buf(c.L.msg, CH_MSG, s), 256L * c.n(s), 256, c.n(s));
+                        c.buf(c.L.msg, CH_MSG, s), 256L * c.n(s), 256, c.n(s), s);
     if (int rc = gemm(c, g3, "kenc layer 3")) return rc;
     // layer 4: 256 -> 256, + descriptors
     GemmArgs g4{};
     g4.njobs = 2; g4.K = 256; g4.lda = 256;
     for (int s = 0; s < 2; ++s) {
         g4.job[s] = job(c.w + o.w[4], c.w + o.b[4], nullptr, c.buf(c.L.msg, CH_MSG, s), 256L * c.n(s), out[s], 256L * c.n(s), 256,
-                        c.n(s));
+                        c.n(s), s);
         g4.job[s].R = desc[s]; g4.job[s].sR = 256L * c.n(s);
     }
     return gemm(c, g4, "kenc layer 4");
 }
 
-// one launch for both sides: grid (query blocks of the larger side, heads, 2 * b); blocks past a side's N return at once
+// one launch for both sides: grid (query blocks of the larger side, heads, 2 * b); blocks past an item's N return at once
 int launch_attention(const AttnArgs& aa, int nmax, hipStream_t st) {
     hipLaunchKernelGGL(sg_attn_kernel, dim3((nmax + 127) / 128, SG_HEADS, 2 * aa.b), dim3(256), 0, st, aa);
     return launch_status("attention");
@@ -607,30 +689,30 @@ int run_layer(const Ctx& c, int layer, int kind, const float* const in[2], float
     gp.njobs = 4; gp.K = 256; gp.lda = 256;
     for (int s = 0; s < 2; ++s) {
         const int src = kind == SG_LAYER_CROSS ? 1 - s : s;
-        gp.job[2 * s] = job(W + L_WQKV, W + L_BQKV, nullptr, in[s], 256L * c.n(s), c.buf(c.L.q, CH_Q, s), 256L * c.n(s), 256, c.n(s));
+        gp.job[2 * s] = job(W + L_WQKV, W + L_BQKV, nullptr, in[s], 256L * c.n(s), c.buf(c.L.q, CH_Q, s), 256L * c.n(s), 256, c.n(s), s);
         gp.job[2 * s + 1] = job(W + L_WQKV + 256 * 256, W + L_BQKV + 256, nullptr, in[src], 256L * c.n(src), c.buf(c.L.kv, CH_KV, s),
-                                512L * c.n(src), 512, c.n(src));
+                                512L * c.n(src), 512, c.n(src), src);
     }
     if (int rc = gemm(c, gp, "q/k/v projection")) return rc;
     AttnArgs aa{};
-    aa.b = c.L.b;
+    aa.b = c.L.b; aa.items = c.items;
     for (int s = 0; s < 2; ++s) {
         const int src = kind == SG_LAYER_CROSS ? 1 - s : s;
         aa.side[s] = AttnSide{c.buf(c.L.q, CH_Q, s), 256L * c.n(s), c.buf(c.L.kv, CH_KV, s), 512L * c.n(src),
-                              c.buf(c.L.msg, CH_MSG, s), 256L * c.n(s), c.n(s), c.n(src)};
+                              c.buf(c.L.msg, CH_MSG, s), 256L * c.n(s), c.n(s), c.n(src), s, src};
     }
     if (int rc = launch_attention(aa, c.L.nm, c.st)) return rc;
     GemmArgs gm{};
     gm.njobs = 2; gm.K = 256; gm.lda = 256;
     for (int s = 0; s < 2; ++s)
         gm.job[s] = job(W + L_WM, W + L_BM, nullptr, c.buf(c.L.msg, CH_MSG, s), 256L * c.n(s), c.buf(c.L.mrg, CH_MRG, s),
-                        256L * c.n(s), 256, c.n(s));
+                        256L * c.n(s), 256, c.n(s), s);
     if (int rc = gemm(c, gm, "merge")) return rc;
     // mlp.0 on cat(x, message): split K over the two operands, BatchNorm + ReLU
     GemmArgs g0{};
     g0.njobs = 2; g0.K = 512; g0.ksplit = 256; g0.lda = 512; g0.relu = 1;
     for (int s = 0; s < 2; ++s) {
-        g0.job[s] = job(W + L_W1, W + L_B1, W + L_BN1, in[s], 256L * c.n(s), c.buf(c.L.hb, CH_HB, s), 512L * c.n(s), 512, c.n(s));
+        g0.job[s] = job(W + L_W1, W + L_B1, W + L_BN1, in[s], 256L * c.n(s), c.buf(c.L.hb, CH_HB, s), 512L * c.n(s), 512, c.n(s), s);
         g0.job[s].B2 = c.buf(c.L.mrg, CH_MRG, s); g0.job[s].sB2 = 256L * c.n(s);
     }
     if (int rc = gemm(c, g0, "mlp.0")) return rc;
@@ -638,7 +720,7 @@ int run_layer(const Ctx& c, int layer, int kind, const float* const in[2], float
     GemmArgs g1{};
     g1.njobs = 2; g1.K = 512; g1.lda = 512;
     for (int s = 0; s < 2; ++s) {
-        g1.job[s] = job(W + L_W2, W + L_B2, nullptr, c.buf(c.L.hb, CH_HB, s), 512L * c.n(s), out[s], 256L * c.n(s), 256, c.n(s));
+        g1.job[s] = job(W + L_W2, W + L_B2, nullptr, c.buf(c.L.hb, CH_HB, s), 512L * c.n(s), out[s], 256L * c.n(s), 256, c.n(s), s);
         g1.job[s].R = in[s]; g1.job[s].sR = 256L * c.n(s);
     }
     return gemm(c, g1, "mlp.3");
@@ -652,30 +734,45 @@ void ot_marginals(int n0, int n1, float* norm, float* mu_last, float* nu_last) {
     *nu_last = logf(ms) + *norm;
 }
 
+Marginals marginals(const Ctx& c) {
+    Marginals mg{};
+    for (int i = 0; i < c.slots(); ++i) ot_marginals(c.items.n[0][i], c.items.n[1][i], &mg.norm[i], &mg.mu_last[i], &mg.nu_last[i]);
+    return mg;
+}
+
+// Z / Zt interior from `scores` [b][cap0][cap1] (copy) or already written by the score GEMM, plus the dustbins; u = v = 0
+int run_sk_build(const Ctx& c, const float* scores, const float* bin, int copy) {
+    const int cap0 = c.L.n0, cap1 = c.L.n1;
+    const size_t cells = copy ? size_t(cap0 + 1) * (cap1 + 1) : size_t(std::max(cap0, cap1)) * 2 + 2;
+    hipLaunchKernelGGL(sg_sk_build_kernel, dim3(unsigned((cells + 255) / 256), c.L.b), dim3(256), 0, c.st, scores, bin, c.f(c.L.z),
+                       c.f(c.L.zt), c.f(c.L.u), c.f(c.L.v), cap0, cap1, copy, c.items);
+    return launch_status(copy ? "sinkhorn build" : "dustbins");
+}
+
 // Z / Zt (with dustbins, u = v = 0) in the workspace -> iterations -> zo
 int run_sinkhorn(const Ctx& c, int iters, float* zo) {
-    const int n0 = c.L.n0, n1 = c.L.n1, b = c.L.b;
-    float norm, mu_last, nu_last;
-    ot_marginals(n0, n1, &norm, &mu_last, &nu_last);
+    const int cap0 = c.L.n0, cap1 = c.L.n1, b = c.L.b;
+    const Marginals mg = marginals(c);
     float *Z = c.f(c.L.z), *Zt = c.f(c.L.zt), *u = c.f(c.L.u), *v = c.f(c.L.v);
     for (int it = 0; it < iters; ++it) {
-        hipLaunchKernelGGL(sg_sk_rows_kernel, dim3((n0 + 1 + 3) / 4, b), dim3(256), 0, c.st, Z, v, u, n0 + 1, n1 + 1, norm, mu_last);
-        hipLaunchKernelGGL(sg_sk_rows_kernel, dim3((n1 + 1 + 3) / 4, b), dim3(256), 0, c.st, Zt, u, v, n1 + 1, n0 + 1, norm, nu_last);
+        hipLaunchKernelGGL(sg_sk_rows_kernel, dim3((cap0 + 1 + 3) / 4, b), dim3(256), 0, c.st, Z, v, u, 0, cap0 + 1, cap1 + 1, c.items, mg);
+        hipLaunchKernelGGL(sg_sk_rows_kernel, dim3((cap1 + 1 + 3) / 4, b), dim3(256), 0, c.st, Zt, u, v, 1, cap1 + 1, cap0 + 1, c.items, mg);
     }
-    const size_t zsz = size_t(n0 + 1) * (n1 + 1);
-    hipLaunchKernelGGL(sg_sk_final_kernel, dim3(unsigned((zsz + 255) / 256), b), dim3(256), 0, c.st, Z, u, v, zo, n0, n1, norm);
+    const size_t zsz = size_t(cap0 + 1) * (cap1 + 1);
+    hipLaunchKernelGGL(sg_sk_final_kernel, dim3(unsigned((zsz + 255) / 256), b), dim3(256), 0, c.st, Z, u, v, zo, cap0, cap1, c.items, mg);
     return launch_status("sinkhorn");
 }
 
 int run_tail(const Ctx& c, const float* z, float th, int64_t* m0, int64_t* m1, float* s0, float* s1) {
-    const int n0 = c.L.n0, n1 = c.L.n1, b = c.L.b;
-    hipLaunchKernelGGL(sg_row_argmax_kernel, dim3((n0 + 3) / 4, b), dim3(256), 0, c.st, z, n0, n1, c.f(c.L.mx0), c.i(c.L.ix0));
-    hipLaunchKernelGGL(sg_col_partial_kernel, dim3((n1 + 63) / 64, c.L.nchunk, b), dim3(256), 0, c.st, z, n0, n1, c.f(c.L.pv),
-                       c.i(c.L.pi));
-    hipLaunchKernelGGL(sg_col_final_kernel, dim3((n1 + 255) / 256, b), dim3(256), 0, c.st, c.f(c.L.pv), c.i(c.L.pi), c.L.nchunk, n1,
-                       c.f(c.L.mx1), c.i(c.L.ix1));
-    hipLaunchKernelGGL(sg_tail_kernel, dim3((n0 + n1 + 255) / 256, b), dim3(256), 0, c.st, c.f(c.L.mx0), c.i(c.L.ix0), c.f(c.L.mx1),
-                       c.i(c.L.ix1), n0, n1, th, m0, m1, s0, s1);
+    const int cap0 = c.L.n0, cap1 = c.L.n1, b = c.L.b;
+    hipLaunchKernelGGL(sg_row_argmax_kernel, dim3((cap0 + 3) / 4, b), dim3(256), 0, c.st, z, cap0, cap1, c.items, c.f(c.L.mx0),
+                       c.i(c.L.ix0));
+    hipLaunchKernelGGL(sg_col_partial_kernel, dim3((cap1 + 63) / 64, c.L.nchunk, b), dim3(256), 0, c.st, z, cap0, cap1, c.items,
+                       c.f(c.L.pv), c.i(c.L.pi));
+    hipLaunchKernelGGL(sg_col_final_kernel, dim3((cap1 + 255) / 256, b), dim3(256), 0, c.st, c.f(c.L.pv), c.i(c.L.pi), c.L.nchunk, cap1,
+                       c.items, c.f(c.L.mx1), c.i(c.L.ix1));
+    hipLaunchKernelGGL(sg_tail_kernel, dim3((cap0 + cap1 + 255) / 256, b), dim3(256), 0, c.st, c.f(c.L.mx0), c.i(c.L.ix0), c.i(c.L.ix1),
+                       cap0, cap1, c.items, th, m0, m1, s0, s1);
     return launch_status("match tail");
 }
 
@@ -687,11 +784,70 @@ int check_layers(int n_layers, const int32_t* kinds) {
     return 0;
 }
 
+int check_sizes(const Ctx& c, const int32_t* const hw[2]) {
+    for (int s = 0; s < 2; ++s) {
+        if (!hw[s]) return fail(-1, "hw%d (host array) is null", s);
+        for (int i = 0; i < c.slots(); ++i)
+            if (hw[s][2 * i] < 1 || hw[s][2 * i + 1] < 1) return fail(-1, "image sizes must be positive");
+    }
+    return 0;
+}
+
+// SuperGlue.forward on a checked context: the uniform and the ragged entry differ in the table alone
+int run_forward(const Ctx& c, int n_layers, const int32_t* layer_kinds, int sinkhorn_iters, float match_threshold,
+                const float* const kp[2], const float* const sc[2], const float* const de[2], const int32_t* const hw[2],
+                int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* z_out) {
+    const int cap0 = c.L.n0, cap1 = c.L.n1;
+    float* xa[2] = {c.buf(c.L.xa, CH_XA, 0), c.buf(c.L.xa, CH_XA, 1)};
+    float* xb[2] = {c.buf(c.L.xb, CH_XB, 0), c.buf(c.L.xb, CH_XB, 1)};
+    if (int rc = run_kenc(c, kp, sc, de, hw, xa)) return rc;
+    float** cur = xa;
+    float** nxt = xb;
+    for (int l = 0; l < n_layers; ++l) {
+        const float* in[2] = {cur[0], cur[1]};
+        if (int rc = run_layer(c, l, layer_kinds[l], in, nxt)) return rc;
+        std::swap(cur, nxt);
+    }
+    // final_proj on both sides
+    const float* F = c.w + final_base(n_layers);
+    GemmArgs gf{};
+    gf.njobs = 2; gf.K = 256; gf.lda = 256;
+    for (int s = 0; s < 2; ++s)
+        gf.job[s] = job(F, F + D * D, nullptr, cur[s], 256L * c.n(s), c.buf(c.L.q, CH_Q, s), 256L * c.n(s), 256, c.n(s), s);
+    if (int rc = gemm(c, gf, "final_proj")) return rc;
+    // scores = mdesc0^T mdesc1 / 16, written into each item's block of the coupling matrix and its transpose
+    GemmArgs gs{};
+    gs.njobs = 1; gs.K = 256; gs.lda = cap0; gs.a_km = 1; gs.scale = 1.f / 16.f;
+    const long zsz = long(cap0 + 1) * (cap1 + 1);
+    gs.job[0] = job(c.buf(c.L.q, CH_Q, 0), nullptr, nullptr, c.buf(c.L.q, CH_Q, 1), 256L * cap1, c.f(c.L.z), zsz, cap0, cap1, 1);
+    gs.job[0].msel = 0;
+    gs.job[0].sA = 256L * cap0;
+    gs.job[0].ldc = cap1 + 1;
+    gs.job[0].Ct = c.f(c.L.zt); gs.job[0].sCt = zsz; gs.job[0].ldct = cap0 + 1;
+    if (int rc = gemm(c, gs, "scores")) return rc;
+    if (int rc = run_sk_build(c, nullptr, c.w + OFF_BIN, 0)) return rc;
+    float* zf = z_out ? z_out : c.f(c.L.z);
+    if (int rc = run_sinkhorn(c, sinkhorn_iters, zf)) return rc;
+    return run_tail(c, zf, match_threshold, matches0, matches1, mscores0, mscores1);
+}
+
+int run_attention(const float* q, const float* kv, int b, int capN, int capM, const Items& items, float* out, sg_stream_t stream) {
+    if (size_t(b) * 2 * D * std::max(capN, capM) > (size_t(1) << 31)) return fail(-1, "problem too large");
+    if (!q || !kv || !out) return fail(-1, "null argument");
+    if (out == q || out == kv) return fail(-1, "out must not alias q or kv");
+    // the forward's launch: side 1 has no query blocks (capacity 0 returns before any load or store)
+    AttnArgs aa{};
+    aa.b = b; aa.items = items;
+    aa.side[0] = AttnSide{q, 256L * capN, kv, 512L * capM, out, 256L * capN, capN, capM, 0, 1};
+    aa.side[1] = AttnSide{q, 256L * capN, kv, 512L * capM, out, 256L * capN, 0, capM, 0, 1};
+    return launch_attention(aa, capN, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" {
 
-int sg_version(void) { return 1; }
+int sg_version(void) { return 2; }
 const char* sg_last_error(void) { return g_err; }
 
 size_t sg_packed_weights_bytes(int n_layers) {
@@ -752,6 +908,11 @@ size_t sg_workspace_bytes(int b, int n0, int n1) {
     return make_layout(b, n0, n1).total;
 }
 
+size_t sg_ragged_workspace_bytes(int b, int cap0, int cap1) {
+    if (b > SG_MAX_ITEMS) return 0;
+    return sg_workspace_bytes(b, cap0, cap1);
+}
+
 int sg_keypoint_encode(const float* packed, int n_layers, const float* kpts0, const float* scores0, const float* desc0,
                        const float* kpts1, const float* scores1, const float* desc1, int b, int n0, int n1, int h0, int w0, int h1,
                        int w1, float* out0, float* out1, void* workspace, size_t workspace_bytes, sg_stream_t stream) {
@@ -759,11 +920,12 @@ int sg_keypoint_encode(const float* packed, int n_layers, const float* kpts0, co
     if (!packed || !kpts0 || !scores0 || !desc0 || !kpts1 || !scores1 || !desc1 || !out0 || !out1) return fail(-1, "null argument");
     if (h0 < 1 || w0 < 1 || h1 < 1 || w1 < 1) return fail(-1, "image sizes must be positive");
     (void)n_layers;
-    Ctx c{make_layout(b, n0, n1), static_cast<char*>(workspace), reinterpret_cast<hipStream_t>(stream), packed};
+    const Ctx c = make_ctx(b, n0, n1, uniform_items(n0, n1), workspace, stream, packed);
     const float* kp[2] = {kpts0, kpts1};
     const float* sc[2] = {scores0, scores1};
     const float* de[2] = {desc0, desc1};
-    const int hw[2][2] = {{h0, w0}, {h1, w1}};
+    const int32_t hw0[2] = {h0, w0}, hw1[2] = {h1, w1};
+    const int32_t* hw[2] = {hw0, hw1};
     float* out[2] = {out0, out1};
     return run_kenc(c, kp, sc, de, hw, out);
 }
@@ -775,7 +937,7 @@ int sg_layer(const float* packed, int n_layers, int layer, int kind, const float
     if (layer < 0 || layer >= n_layers || n_layers > SG_MAX_LAYERS) return fail(-1, "layer %d out of range [0, %d)", layer, n_layers);
     if (kind != SG_LAYER_SELF && kind != SG_LAYER_CROSS) return fail(-1, "kind must be SG_LAYER_SELF or SG_LAYER_CROSS");
     if (out0 == desc0 || out0 == desc1 || out1 == desc0 || out1 == desc1) return fail(-1, "outputs must not alias the inputs");
-    Ctx c{make_layout(b, n0, n1), static_cast<char*>(workspace), reinterpret_cast<hipStream_t>(stream), packed};
+    const Ctx c = make_ctx(b, n0, n1, uniform_items(n0, n1), workspace, stream, packed);
     const float* in[2] = {desc0, desc1};
     float* out[2] = {out0, out1};
     return run_layer(c, layer, kind, in, out);
@@ -783,15 +945,14 @@ int sg_layer(const float* packed, int n_layers, int layer, int kind, const float
 
 int sg_attention(const float* q, const float* kv, int b, int N, int M, float* out, sg_stream_t stream) {
     if (b < 1 || N < 1 || M < 1) return fail(-1, "b, N, M must be >= 1 (got %d, %d, %d)", b, N, M);
-    if (size_t(b) * 2 * D * std::max(N, M) > (size_t(1) << 31)) return fail(-1, "problem too large");
-    if (!q || !kv || !out) return fail(-1, "null argument");
-    if (out == q || out == kv) return fail(-1, "out must not alias q or kv");
-    // the forward's launch: side 1 repeats side 0 with no query blocks (N = 0 returns before any load or store)
-    AttnArgs aa{};
-    aa.b = b;
-    aa.side[0] = AttnSide{q, 256L * N, kv, 512L * M, out, 256L * N, N, M};
-    aa.side[1] = AttnSide{q, 256L * N, kv, 512L * M, out, 256L * N, 0, M};
-    return launch_attention(aa, N, reinterpret_cast<hipStream_t>(stream));
+    return run_attention(q, kv, b, N, M, uniform_items(N, M), out, stream);
+}
+
+int sg_attention_ragged(const float* q, const float* kv, int b, int capN, int capM, const int32_t* n, const int32_t* m, float* out,
+                        sg_stream_t stream) {
+    Items items;
+    if (int rc = check_ragged(b, capN, capM, n, m, &items)) return rc;
+    return run_attention(q, kv, b, capN, capM, items, out, stream);
 }
 
 int sg_sinkhorn(const float* scores, const float* bin_score, int b, int n0, int n1, int iters, float* z_out, void* workspace,
@@ -799,11 +960,20 @@ int sg_sinkhorn(const float* scores, const float* bin_score, int b, int n0, int 
     if (int rc = check_common(b, n0, n1, workspace, workspace_bytes)) return rc;
     if (!scores || !bin_score || !z_out) return fail(-1, "null argument");
     if (iters < 0) return fail(-1, "iters must be >= 0");
-    Ctx c{make_layout(b, n0, n1), static_cast<char*>(workspace), reinterpret_cast<hipStream_t>(stream), nullptr};
-    const size_t zsz = size_t(n0 + 1) * (n1 + 1);
-    hipLaunchKernelGGL(sg_sk_build_kernel, dim3(unsigned((zsz + 255) / 256), b), dim3(256), 0, c.st, scores, bin_score, c.f(c.L.z),
-                       c.f(c.L.zt), c.f(c.L.u), c.f(c.L.v), n0, n1, 1);
-    if (int rc = launch_status("sinkhorn build")) return rc;
+    const Ctx c = make_ctx(b, n0, n1, uniform_items(n0, n1), workspace, stream, nullptr);
+    if (int rc = run_sk_build(c, scores, bin_score, 1)) return rc;
+    return run_sinkhorn(c, iters, z_out);
+}
+
+int sg_sinkhorn_ragged(const float* scores, const float* bin_score, int b, int cap0, int cap1, const int32_t* n0, const int32_t* n1,
+                       int iters, float* z_out, void* workspace, size_t workspace_bytes, sg_stream_t stream) {
+    Items items;
+    if (int rc = check_ragged(b, cap0, cap1, n0, n1, &items)) return rc;
+    if (int rc = check_common(b, cap0, cap1, workspace, workspace_bytes)) return rc;
+    if (!scores || !bin_score || !z_out) return fail(-1, "null argument");
+    if (iters < 0) return fail(-1, "iters must be >= 0");
+    const Ctx c = make_ctx(b, cap0, cap1, items, workspace, stream, nullptr);
+    if (int rc = run_sk_build(c, scores, bin_score, 1)) return rc;
     return run_sinkhorn(c, iters, z_out);
 }
 
@@ -811,7 +981,18 @@ int sg_match_tail(const float* z, int b, int n0, int n1, float match_threshold, 
                   float* mscores0, float* mscores1, void* workspace, size_t workspace_bytes, sg_stream_t stream) {
     if (int rc = check_common(b, n0, n1, workspace, workspace_bytes)) return rc;
     if (!z || !matches0 || !matches1 || !mscores0 || !mscores1) return fail(-1, "null argument");
-    Ctx c{make_layout(b, n0, n1), static_cast<char*>(workspace), reinterpret_cast<hipStream_t>(stream), nullptr};
+    const Ctx c = make_ctx(b, n0, n1, uniform_items(n0, n1), workspace, stream, nullptr);
+    return run_tail(c, z, match_threshold, matches0, matches1, mscores0, mscores1);
+}
+
+int sg_match_tail_ragged(const float* z, int b, int cap0, int cap1, const int32_t* n0, const int32_t* n1, float match_threshold,
+                         int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, void* workspace,
+                         size_t workspace_bytes, sg_stream_t stream) {
+    Items items;
+    if (int rc = check_ragged(b, cap0, cap1, n0, n1, &items)) return rc;
+    if (int rc = check_common(b, cap0, cap1, workspace, workspace_bytes)) return rc;
+    if (!z || !matches0 || !matches1 || !mscores0 || !mscores1) return fail(-1, "null argument");
+    const Ctx c = make_ctx(b, cap0, cap1, items, workspace, stream, nullptr);
     return run_tail(c, z, match_threshold, matches0, matches1, mscores0, mscores1);
 }
 
@@ -825,43 +1006,36 @@ int sg_forward(const float* packed, int n_layers, const int32_t* layer_kinds, in
     if (!packed || !kpts0 || !scores0 || !desc0 || !kpts1 || !scores1 || !desc1 || !matches0 || !matches1 || !mscores0 || !mscores1)
         return fail(-1, "null argument");
     if (h0 < 1 || w0 < 1 || h1 < 1 || w1 < 1) return fail(-1, "image sizes must be positive");
-    Ctx c{make_layout(b, n0, n1), static_cast<char*>(workspace), reinterpret_cast<hipStream_t>(stream), packed};
+    const Ctx c = make_ctx(b, n0, n1, uniform_items(n0, n1), workspace, stream, packed);
     const float* kp[2] = {kpts0, kpts1};
     const float* sc[2] = {scores0, scores1};
     const float* de[2] = {desc0, desc1};
-    const int hw[2][2] = {{h0, w0}, {h1, w1}};
-    float* xa[2] = {c.buf(c.L.xa, CH_XA, 0), c.buf(c.L.xa, CH_XA, 1)};
-    float* xb[2] = {c.buf(c.L.xb, CH_XB, 0), c.buf(c.L.xb, CH_XB, 1)};
-    if (int rc = run_kenc(c, kp, sc, de, hw, xa)) return rc;
-    float** cur = xa;
-    float** nxt = xb;
-    for (int l = 0; l < n_layers; ++l) {
-        const float* in[2] = {cur[0], cur[1]};
-        if (int rc = run_layer(c, l, layer_kinds[l], in, nxt)) return rc;
-        std::swap(cur, nxt);
-    }
-    // final_proj on both sides
-    const float* F = packed + final_base(n_layers);
-    GemmArgs gf{};
-    gf.njobs = 2; gf.K = 256; gf.lda = 256;
-    for (int s = 0; s < 2; ++s)
-        gf.job[s] = job(F, F + D * D, nullptr, cur[s], 256L * c.n(s), c.buf(c.L.q, CH_Q, s), 256L * c.n(s), 256, c.n(s));
-    if (int rc = gemm(c, gf, "final_proj")) return rc;
-    // scores = mdesc0^T mdesc1 / 16, written into the coupling matrix and its transpose
-    GemmArgs gs{};
-    gs.njobs = 1; gs.K = 256; gs.lda = n0; gs.a_km = 1; gs.scale = 1.f / 16.f;
-    const long zsz = long(n0 + 1) * (n1 + 1);
-    gs.job[0] = job(c.buf(c.L.q, CH_Q, 0), nullptr, nullptr, c.buf(c.L.q, CH_Q, 1), 256L * n1, c.f(c.L.z), zsz, n0, n1);
-    gs.job[0].sA = 256L * n0;
-    gs.job[0].ldc = n1 + 1;
-    gs.job[0].Ct = c.f(c.L.zt); gs.job[0].sCt = zsz; gs.job[0].ldct = n0 + 1;
-    if (int rc = gemm(c, gs, "scores")) return rc;
-    hipLaunchKernelGGL(sg_sk_build_kernel, dim3((std::max(n0, n1) * 2 + 2 + 255) / 256, b), dim3(256), 0, c.st, nullptr,
-                       packed + OFF_BIN, c.f(c.L.z), c.f(c.L.zt), c.f(c.L.u), c.f(c.L.v), n0, n1, 0);
-    if (int rc = launch_status("dustbins")) return rc;
-    float* zf = z_out ? z_out : c.f(c.L.z);
-    if (int rc = run_sinkhorn(c, sinkhorn_iters, zf)) return rc;
-    return run_tail(c, zf, match_threshold, matches0, matches1, mscores0, mscores1);
+    const int32_t hw0[2] = {h0, w0}, hw1[2] = {h1, w1};
+    const int32_t* hw[2] = {hw0, hw1};
+    return run_forward(c, n_layers, layer_kinds, sinkhorn_iters, match_threshold, kp, sc, de, hw, matches0, matches1, mscores0,
+                       mscores1, z_out);
+}
+
+int sg_forward_ragged(const float* packed, int n_layers, const int32_t* layer_kinds, int sinkhorn_iters, float match_threshold,
+                      const float* kpts0, const float* scores0, const float* desc0, const float* kpts1, const float* scores1,
+                      const float* desc1, int b, int cap0, int cap1, const int32_t* n0, const int32_t* n1, const int32_t* hw0,
+                      const int32_t* hw1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* z_out,
+                      void* workspace, size_t workspace_bytes, sg_stream_t stream) {
+    Items items;
+    if (int rc = check_ragged(b, cap0, cap1, n0, n1, &items)) return rc;
+    if (int rc = check_common(b, cap0, cap1, workspace, workspace_bytes)) return rc;
+    if (int rc = check_layers(n_layers, layer_kinds)) return rc;
+    if (sinkhorn_iters < 0) return fail(-1, "sinkhorn_iters must be >= 0");
+    if (!packed || !kpts0 || !scores0 || !desc0 || !kpts1 || !scores1 || !desc1 || !matches0 || !matches1 || !mscores0 || !mscores1)
+        return fail(-1, "null argument");
+    const Ctx c = make_ctx(b, cap0, cap1, items, workspace, stream, packed);
+    const int32_t* hw[2] = {hw0, hw1};
+    if (int rc = check_sizes(c, hw)) return rc;
+    const float* kp[2] = {kpts0, kpts1};
+    const float* sc[2] = {scores0, scores1};
+    const float* de[2] = {desc0, desc1};
+    return run_forward(c, n_layers, layer_kinds, sinkhorn_iters, match_threshold, kp, sc, de, hw, matches0, matches1, mscores0,
+                       mscores1, z_out);
 }
 
 }  // extern "C"

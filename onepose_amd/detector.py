@@ -22,7 +22,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _native_det
+from . import _native_det, _native_sg
 from ._binding import NativeError, WorkspaceCache, k_array, stream_handle  # noqa: F401
 from .superglue import SuperGlue
 
@@ -175,7 +175,9 @@ class LocalFeatureObjectDetector:
         return db
 
     def _pack(self):
-        """Padded device buffers of the reference views: kpts0 [V,cap0,2], n0 [V], hw0 [V,2], and the matcher's outputs."""
+        """Padded device buffers of the reference views: kpts0 [V,cap0,2], n0 [V], hw0 [V,2], and the matcher's outputs; for
+        the native matcher's ragged batch also the view-side scores [V,cap0] and descriptors [V,256,cap0] of the views that
+        have keypoints (``live``), built once."""
         views = list(self.db_dict.values())
         dev = views[0]["keypoints"].device
         self.device = dev
@@ -191,6 +193,14 @@ class LocalFeatureObjectDetector:
         self.hw0 = torch.tensor(np.stack([v["size"] for v in views]).astype(np.int32), device=dev)
         self.matches0 = torch.full((V, cap0), -1, device=dev, dtype=torch.int64)
         self.scores0 = torch.zeros(V, cap0, device=dev, dtype=torch.float32)
+        self.live = [i for i, n in enumerate(self.n0_host) if n > 0]
+        self.view_scores = torch.zeros(V, cap0, device=dev, dtype=torch.float32)
+        self.view_desc = torch.zeros(V, views[0]["descriptors"].shape[0], cap0, device=dev, dtype=torch.float32)
+        for i, v in enumerate(views):
+            self.view_scores[i, :self.n0_host[i]] = v["scores"]
+            self.view_desc[i, :, :self.n0_host[i]] = v["descriptors"]
+        self.hw0_host = [(int(v["size"][0]), int(v["size"][1])) for v in views]
+        self.ragged = True             # native matcher: one ragged batch over the views; False keeps the per-view loop
 
     def _workspace(self, dev):
         shape = (self.V, self.cap0, self.iterations)
@@ -217,6 +227,8 @@ class LocalFeatureObjectDetector:
             self.matches0.fill_(-1)
             return
         native = isinstance(self.matcher, SuperGlue)
+        if native and self.ragged and len(self.live) > 1:
+            return self._match_views_ragged(kpts1, scores1, desc1, query_hw)
         if native:
             m1 = torch.empty(1, n1, device=dev, dtype=torch.int64)
             s1 = torch.empty(1, n1, device=dev, dtype=torch.float32)
@@ -240,6 +252,28 @@ class LocalFeatureObjectDetector:
                     raise RuntimeError(NO_CPU.format("the matcher returned host tensors"))
                 self.matches0[i, :n0] = pred["matches0"][0].to(torch.int64)
                 self.scores0[i, :n0] = pred["matching_scores0"][0]
+
+    def _match_views_ragged(self, kpts1, scores1, desc1, query_hw):
+        """The views that have keypoints as ragged batches of the native matcher (bitwise the loop's results): the query side
+        is expanded per frame; with no empty view the outputs land straight in matches0 / scores0."""
+        n1, dev = int(kpts1.shape[0]), kpts1.device
+        engine, step = self.matcher.engine, _native_sg.MAX_ITEMS
+        qhw = (int(query_hw[0]), int(query_hw[1]))
+        for k in range(0, len(self.live), step):
+            live = self.live[k:k + step]
+            b = len(live)
+            whole = b == self.V
+            sel = slice(None) if whole else torch.tensor(live, device=dev)
+            m0 = self.matches0 if whole else torch.empty(b, self.cap0, device=dev, dtype=torch.int64)
+            s0 = self.scores0 if whole else torch.empty(b, self.cap0, device=dev, dtype=torch.float32)
+            m1 = torch.empty(b, n1, device=dev, dtype=torch.int64)
+            s1 = torch.empty(b, n1, device=dev, dtype=torch.float32)
+            engine.forward_ragged(self.kpts0[sel], self.view_scores[sel], self.view_desc[sel], kpts1[None].expand(b, -1, -1),
+                                  scores1[None].expand(b, -1), desc1[None].expand(b, -1, -1), [self.n0_host[i] for i in live],
+                                  [n1] * b, [self.hw0_host[i] for i in live], [qhw] * b, out=(m0, m1, s0, s1))
+            if not whole:
+                self.matches0[sel] = m0
+                self.scores0[sel] = s0
 
     @torch.no_grad()
     def _tail(self, kpts1, query_hw):

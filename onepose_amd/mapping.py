@@ -27,8 +27,9 @@ import sys
 import numpy as np
 import torch
 
-from . import _native_map
+from . import _native_map, _native_sg
 from ._binding import NativeError, stream_handle
+from .superglue import SuperGlue
 
 THRESHOLDS = dict(max_epipolar_error=4.0, min_pair_inliers=15, max_reproj_error=4.0, min_tri_angle=1.5, max_hypotheses=120,
                   refine_iterations=10, max_num_kp3d=2500, dist_threshold=1e-3, seed=0)
@@ -296,15 +297,19 @@ class ObjectMapper:
     """Builds an object's 3D feature database from a posed scan.
 
     ``extractor``: a ``SuperPoint`` (max_keypoints 4096 in the reference), ``matcher``: a ``SuperGlue`` (match threshold 0.7);
-    both may be None when only ``build_from_features`` / ``build_from_matches`` are used.  ``thresholds``: any of THRESHOLDS.
+    both may be None when only ``build_from_features`` / ``build_from_matches`` are used.  ``pair_batch``: image pairs per
+    ragged batch of the native matcher (``SuperGlue.match_pairs``; the matches are bitwise those of one forward per pair);
+    1, or any other matcher, runs one forward per pair.  ``thresholds``: any of THRESHOLDS.
     Every entry point returns the dict ``load_object_database`` returns and, with ``out_dir``, writes the three annotation
     files it reads; ``self.last`` keeps the intermediate results of the latest build (numpy)."""
 
-    def __init__(self, extractor=None, matcher=None, num_leaf=8, leaf_seed=None, device="cuda", **thresholds):
+    def __init__(self, extractor=None, matcher=None, num_leaf=8, leaf_seed=None, device="cuda", pair_batch=16, **thresholds):
         unknown = set(thresholds) - set(THRESHOLDS)
         if unknown:
             raise TypeError(f"unknown thresholds {sorted(unknown)}; known: {sorted(THRESHOLDS)}")
-        self.extractor, self.matcher = extractor, matcher
+        if int(pair_batch) < 1:
+            raise ValueError(f"pair_batch must be >= 1 (got {pair_batch})")
+        self.extractor, self.matcher, self.pair_batch = extractor, matcher, int(pair_batch)
         self.num_leaf, self.leaf_seed, self.device = num_leaf, leaf_seed, torch.device(device)
         self.cfg = dict(THRESHOLDS, **thresholds)
         self.tail = MapTail(device)
@@ -329,14 +334,25 @@ class ObjectMapper:
         if self.matcher is None:
             raise RuntimeError("ObjectMapper.build_from_features needs a matcher")
         to = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.device)  # noqa: E731
-        pair_matches = []
-        for i, j in unique_pairs(pairs):
+
+        def pair_data(i, j):
             f0, f1 = features[i], features[j]
-            data = {"keypoints0": to(f0["keypoints"])[None], "scores0": to(f0["scores"])[None], "descriptors0": to(f0["descriptors"])[None],
+            return {"keypoints0": to(f0["keypoints"])[None], "scores0": to(f0["scores"])[None], "descriptors0": to(f0["descriptors"])[None],
                     "keypoints1": to(f1["keypoints"])[None], "scores1": to(f1["scores"])[None], "descriptors1": to(f1["descriptors"])[None],
                     "image0": torch.empty(1, 1, int(f0["size"][0]), int(f0["size"][1]), device="meta"),
                     "image1": torch.empty(1, 1, int(f1["size"][0]), int(f1["size"][1]), device="meta")}
-            pair_matches.append((i, j, self.matcher(data)["matches0"][0].to(torch.int64)))
+
+        todo = list(unique_pairs(pairs))
+        pair_matches = []
+        if isinstance(self.matcher, SuperGlue) and self.pair_batch > 1:
+            step = min(self.pair_batch, _native_sg.MAX_ITEMS)
+            for k in range(0, len(todo), step):      # one batch of pairs in memory at a time
+                chunk = todo[k:k + step]
+                preds = self.matcher.match_pairs([pair_data(i, j) for i, j in chunk], max_items=step)
+                pair_matches += [(i, j, pred["matches0"][0].to(torch.int64).clone()) for (i, j), pred in zip(chunk, preds)]
+        else:
+            for i, j in todo:
+                pair_matches.append((i, j, self.matcher(pair_data(i, j))["matches0"][0].to(torch.int64)))
         return self.build_from_matches(features, pair_matches, poses, Ks, box3d_corners, out_dir=out_dir)
 
     @torch.no_grad()

@@ -67,6 +67,61 @@ def _check(t, name, dev):
     return t.to(torch.float32).contiguous()
 
 
+IN_KEYS = ("keypoints0", "scores0", "descriptors0", "keypoints1", "scores1", "descriptors1")
+OUT_KEYS = ("matches0", "matches1", "matching_scores0", "matching_scores1")
+
+
+def _point_axis(key):
+    return 2 if key.startswith("descriptors") else 1
+
+
+def pack_ragged(items):
+    """A list of reference-shaped ``data`` dicts with b = 1 (keypoints [1,n,2], scores [1,n], descriptors [1,256,n], image
+    [1,1,H,W] per side) -> one dict for ``SuperGlueEngine.forward_ragged``: the six inputs zero-padded to the largest count
+    of each side (at least 1), plus the host lists ``n0`` / ``n1`` (counts) and ``hw0`` / ``hw1`` ((H, W) per item).
+    Pure tensor bookkeeping: works on CPU tensors, launches nothing."""
+    if not items:
+        raise ValueError("pack_ragged needs at least one item")
+    b = len(items)
+    out = {"n0": [int(d["keypoints0"].shape[1]) for d in items], "n1": [int(d["keypoints1"].shape[1]) for d in items],
+           "hw0": [tuple(int(x) for x in d["image0"].shape[-2:]) for d in items],
+           "hw1": [tuple(int(x) for x in d["image1"].shape[-2:]) for d in items]}
+    ref = items[0]["keypoints0"]
+    for key in IN_KEYS:
+        cap = max(1, max(out["n" + key[-1]]))
+        shape = {"keypoints": (b, cap, 2), "scores": (b, cap), "descriptors": (b, D, cap)}[key[:-1]]
+        padded = ref.new_zeros(shape, dtype=torch.float32)
+        for i, d in enumerate(items):
+            t = d[key]
+            if t.shape[0] != 1:
+                raise ValueError(f"item {i}: {key} must have batch size 1 (got {t.shape[0]})")
+            padded[i].narrow(_point_axis(key) - 1, 0, out["n" + key[-1]][i]).copy_(t[0])
+        out[key] = padded
+    return out
+
+
+def unpack_ragged(padded, n0, n1):
+    """Per-item views of padded tensors, cut to each item's own counts: ``padded`` maps names ending in 0 / 1 (the inputs of
+    ``pack_ragged``, the outputs of ``forward_ragged``) to [b, ...] tensors -> list of b dicts of [1, ...] views."""
+    counts = {"0": n0, "1": n1}
+    return [{key: t[i:i + 1].narrow(_point_axis(key), 0, counts[key[-1]][i]) for key, t in padded.items()}
+            for i in range(len(n0))]
+
+
+def ragged_chunks(items, max_items):
+    """``items`` in order, in lists of at most ``max_items`` (itself at most SG_MAX_ITEMS)."""
+    if not 1 <= max_items <= _native_sg.MAX_ITEMS:
+        raise ValueError(f"max_items must be in [1, {_native_sg.MAX_ITEMS}] (got {max_items})")
+    return [items[k:k + max_items] for k in range(0, len(items), max_items)]
+
+
+def _host_i32(values, b, width, name):
+    flat = [int(x) for row in values for x in (row if width > 1 else (row,))]
+    if len(flat) != b * width:
+        raise ValueError(f"{name} must have {b} entries" + (f" of {width}" if width > 1 else ""))
+    return (ctypes.c_int32 * len(flat))(*flat)
+
+
 class SuperGlueEngine:
     """Raw-tensor entry to the HIP matcher of one module: packed weights once per weight version and device, workspaces
     cached per (shape, device, stream) so one module serves several streams at once.  Outputs may be preallocated
@@ -78,6 +133,7 @@ class SuperGlueEngine:
         self._packed = PackedWeights("onepose_amd.SuperGlue runs only on a ROCm GPU (a parameter is on {}); "
                                      "there is no CPU fallback -- move the module to the GPU")
         self._workspaces = WorkspaceCache(6)
+        self._ragged_workspaces = WorkspaceCache(6)
 
     def _raw(self):
         """(module, name) of every float tensor of the state_dict in its order, read through getattr on every call."""
@@ -97,6 +153,10 @@ class SuperGlueEngine:
     def workspace(self, b, n0, n1, device):
         return self._workspaces.get((b, n0, n1), device, self.lib.sg_workspace_bytes,
                                     lambda: f"sg_workspace_bytes({b}, {n0}, {n1}) refused the shape")
+
+    def ragged_workspace(self, b, cap0, cap1, device):
+        return self._ragged_workspaces.get((b, cap0, cap1), device, self.lib.sg_ragged_workspace_bytes,
+                                           lambda: f"sg_ragged_workspace_bytes({b}, {cap0}, {cap1}) refused the shape")
 
     @staticmethod
     def outputs(b, n0, n1, device):
@@ -126,7 +186,77 @@ class SuperGlueEngine:
             ms1.data_ptr(), z_out.data_ptr() if z_out is not None else None, ws.data_ptr(), ws.numel(), stream_handle(dev)), "sg_forward")
         return m0, m1, ms0, ms1
 
+    @on_device
+    def forward_ragged(self, kpts0, scores0, desc0, kpts1, scores1, desc1, n0, n1, hw0, hw1, out=None, z_out=None):
+        """b pairs in one chain of launches: inputs padded to [b,cap0,2] / [b,cap0] / [b,256,cap0] (and cap1), host lists
+        n0, n1 (1 <= n <= cap) and hw0, hw1 ((H, W) per item).  Returns the four outputs padded to [b,cap0] / [b,cap1], -1 / 0
+        past an item's count; every item is bitwise what ``forward`` gives on that pair alone.  z_out: [b,cap0+1,cap1+1]."""
+        dev = kpts0.device
+        k0, s0, d0 = _check(kpts0, "keypoints0", dev), _check(scores0, "scores0", dev), _check(desc0, "descriptors0", dev)
+        k1, s1, d1 = _check(kpts1, "keypoints1", dev), _check(scores1, "scores1", dev), _check(desc1, "descriptors1", dev)
+        b, cap0, cap1 = k0.shape[0], k0.shape[1], k1.shape[1]
+        if d0.shape != (b, D, cap0) or d1.shape != (b, D, cap1) or s0.shape != (b, cap0) or s1.shape != (b, cap1) or k1.shape[0] != b:
+            raise ValueError("inconsistent shapes: keypoints [b,cap,2], scores [b,cap], descriptors [b,256,cap] with one b")
+        cn0, cn1 = _host_i32(n0, b, 1, "n0"), _host_i32(n1, b, 1, "n1")
+        chw0, chw1 = _host_i32(hw0, b, 2, "hw0"), _host_i32(hw1, b, 2, "hw1")
+        cfg = self.module.config
+        m0, m1, ms0, ms1 = out if out is not None else self.outputs(b, cap0, cap1, dev)
+        for t, cap, name in ((m0, cap0, "matches0"), (m1, cap1, "matches1"), (ms0, cap0, "matching_scores0"), (ms1, cap1, "matching_scores1")):
+            if t.shape != (b, cap) or not t.is_contiguous():
+                raise ValueError(f"out: {name} must be a contiguous [{b}, {cap}] tensor")
+        if z_out is not None and (z_out.shape != (b, cap0 + 1, cap1 + 1) or z_out.dtype != torch.float32 or not z_out.is_contiguous()):
+            raise ValueError("z_out must be a contiguous fp32 [b, cap0+1, cap1+1] tensor")
+        ws = self.ragged_workspace(b, cap0, cap1, dev)
+        kinds = (ctypes.c_int32 * max(1, self.module.n_layers))(*self.module.layer_kinds)
+        _native_sg.check(self.lib.sg_forward_ragged(
+            self.packed_weights(dev).data_ptr(), self.module.n_layers, kinds, int(cfg["sinkhorn_iterations"]),
+            float(cfg["match_threshold"]), k0.data_ptr(), s0.data_ptr(), d0.data_ptr(), k1.data_ptr(), s1.data_ptr(), d1.data_ptr(),
+            b, cap0, cap1, cn0, cn1, chw0, chw1, m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(), ms1.data_ptr(),
+            z_out.data_ptr() if z_out is not None else None, ws.data_ptr(), ws.numel(), stream_handle(dev)), "sg_forward_ragged")
+        return m0, m1, ms0, ms1
+
     # ---- stages (tests) ----
+    @on_device
+    def attention_ragged(self, q, kv, n, m):
+        """``attention`` on q [b,256,capN], kv [b,512,capM] with per-item counts n, m (host lists); columns past n[i] of
+        the result are not written."""
+        dev = q.device
+        qq, kk = _check(q, "q", dev), _check(kv, "kv", dev)
+        if qq.dim() != 3 or kk.dim() != 3 or qq.shape[1] != D or kk.shape[1] != 2 * D or kk.shape[0] != qq.shape[0]:
+            raise ValueError("q must be [b,256,capN] and kv [b,512,capM] with one b")
+        b = qq.shape[0]
+        out = torch.zeros_like(qq)
+        _native_sg.check(self.lib.sg_attention_ragged(qq.data_ptr(), kk.data_ptr(), b, qq.shape[2], kk.shape[2], _host_i32(n, b, 1, "n"),
+                                                      _host_i32(m, b, 1, "m"), out.data_ptr(), stream_handle(dev)), "sg_attention_ragged")
+        return out
+
+    @on_device
+    def sinkhorn_ragged(self, scores, bin_score, n0, n1, iters):
+        """``sinkhorn`` on scores [b,cap0,cap1] with per-item counts -> z [b,cap0+1,cap1+1] (zero outside an item's block)."""
+        dev = scores.device
+        sc = _check(scores, "scores", dev)
+        alpha = _check(torch.as_tensor(bin_score, dtype=torch.float32, device=dev).reshape(1), "bin_score", dev)
+        b, cap0, cap1 = sc.shape
+        ws = self.ragged_workspace(b, cap0, cap1, dev)
+        z = torch.zeros(b, cap0 + 1, cap1 + 1, device=dev, dtype=torch.float32)
+        _native_sg.check(self.lib.sg_sinkhorn_ragged(sc.data_ptr(), alpha.data_ptr(), b, cap0, cap1, _host_i32(n0, b, 1, "n0"),
+                                                     _host_i32(n1, b, 1, "n1"), int(iters), z.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     stream_handle(dev)), "sg_sinkhorn_ragged")
+        return z
+
+    @on_device
+    def match_tail_ragged(self, z, n0, n1, match_threshold):
+        dev = z.device
+        zz = _check(z, "z", dev)
+        b, cap0, cap1 = zz.shape[0], zz.shape[1] - 1, zz.shape[2] - 1
+        ws = self.ragged_workspace(b, cap0, cap1, dev)
+        m0, m1, s0, s1 = self.outputs(b, cap0, cap1, dev)
+        _native_sg.check(self.lib.sg_match_tail_ragged(zz.data_ptr(), b, cap0, cap1, _host_i32(n0, b, 1, "n0"), _host_i32(n1, b, 1, "n1"),
+                                                       float(match_threshold), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(),
+                                                       s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
+                         "sg_match_tail_ragged")
+        return m0, m1, s0, s1
+
     @on_device
     def keypoint_encode(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1):
         dev = kpts0.device
@@ -261,3 +391,34 @@ class SuperGlue(nn.Module):
         m0, m1, s0, s1 = self.engine.forward(kpts0, data["scores0"], data["descriptors0"], kpts1, data["scores1"],
                                              data["descriptors1"], hw0, hw1)
         return {"matches0": m0, "matches1": m1, "matching_scores0": s0, "matching_scores1": s1}
+
+    @torch.no_grad()
+    def match_pairs(self, items, max_items=16):
+        """``forward`` on a list of pairs (``data`` dicts with b = 1, any keypoint counts and image sizes) -> list of the
+        dicts ``forward`` returns, bitwise the same values.  The pairs go through the ragged batch ``max_items`` (at most 64)
+        at a time; a pair with an empty side gets the empty result without entering the library, a chunk of one pair
+        goes through ``forward``."""
+        if self.training:
+            raise RuntimeError("onepose_amd.SuperGlue is inference only (BatchNorm running statistics, no backward): call .eval()")
+        items = list(items)
+        results = [None] * len(items)
+        live = []
+        for i, data in enumerate(items):
+            if data["keypoints0"].shape[0] != 1:
+                raise ValueError(f"item {i}: match_pairs takes pairs with batch size 1")
+            if data["keypoints0"].shape[1] == 0 or data["keypoints1"].shape[1] == 0:
+                results[i] = self.forward(data)
+            elif not data["keypoints0"].is_cuda:
+                raise RuntimeError(f"onepose_amd.SuperGlue runs only on a ROCm GPU (item {i} is on {data['keypoints0'].device}); "
+                                   "there is no CPU fallback")
+            else:
+                live.append(i)
+        for chunk in ragged_chunks(live, max_items):
+            if len(chunk) == 1:
+                results[chunk[0]] = self.forward(items[chunk[0]])
+                continue
+            p = pack_ragged([items[i] for i in chunk])
+            out = self.engine.forward_ragged(*(p[k] for k in IN_KEYS), p["n0"], p["n1"], p["hw0"], p["hw1"])
+            for i, res in zip(chunk, unpack_ragged(dict(zip(OUT_KEYS, out)), p["n0"], p["n1"])):
+                results[i] = res
+        return results

@@ -135,7 +135,9 @@ def main():
         assert np.array_equal(out["bbox"].cpu().numpy(), tail["bbox"]) and np.array_equal(out["info"].cpu().numpy(), tail["info"])
         if tail["bbox"][2] > tail["bbox"][0] and tail["bbox"][3] > tail["bbox"][1]:
             assert crop[0, 0].cpu().numpy().tobytes() == ref_crop.tobytes() and K_crop.cpu().numpy().tobytes() == ref_K.tobytes()
-        t_ext, t_match, t_tail, t_host, t_whole = [], [], [], [], []
+        t_ext, t_match, t_tail, t_host, t_whole, t_loop, t_ragged = [], [], [], [], [], [], []
+        qd = ext_run(det._check_frame(frame))
+        q1 = (qd["keypoints"][0], qd["scores"][0], qd["descriptors"][0].contiguous())
         for _ in range(a.passes):                      # the two routes alternate inside every pass
             e, m, t = [], [], []
             for _ in range(a.steps):
@@ -157,13 +159,24 @@ def main():
                 det.detect_device(frame, K, a.crop)
             torch.cuda.synchronize()
             t_whole.append((time.perf_counter() - t0) / a.steps * 1e3)
+            for flag, acc in ((False, t_loop), (True, t_ragged)):      # the matcher alone: one forward per view / one ragged batch
+                det.ragged = flag
+                det._match_views(*q1, frame.shape[-2:])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    det._match_views(*q1, frame.shape[-2:])
+                torch.cuda.synchronize()
+                acc.append((time.perf_counter() - t0) / a.steps * 1e3)
         info = out["info"].cpu().numpy()
         whole = statistics.median(t_whole)
         rows.append({"frame": f"{h}x{w}", "views": a.views, "query_keypoints": int(k1.shape[0]), "ref_keypoints": det.n0_host,
                      "matches_per_view": info[:, 1].tolist(), "inliers_per_view": info[:, 3].tolist(), "iterations": det.iterations,
                      "detect_device_ms": spread(t_whole), "frames_per_s": round(1e3 / whole, 2),
                      "extractor_ms": spread(t_ext), "matcher_forwards_ms": spread(t_match), "tail_ms": spread(t_tail),
-                     "host_tail_ms": spread(t_host),
+                     "host_tail_ms": spread(t_host), "matcher_loop_ms": spread(t_loop), "matcher_ragged_ms": spread(t_ragged),
+                     "ragged_beats_loop_by_more_than_its_spread": bool(
+                         statistics.median(t_loop) - statistics.median(t_ragged) > max(t_loop) - min(t_loop)),
                      "host_over_native_tail": round(statistics.median(t_host) / statistics.median(t_tail), 1),
                      "tail_share_of_detect": round(statistics.median(t_tail) / whole, 4)})
         print(json.dumps(rows[-1]), file=sys.stderr, flush=True)

@@ -45,6 +45,38 @@ def host_ms(fn):
     return out, round((time.perf_counter() - t0) * 1e3, 2)
 
 
+def matching_stage(feats, pairs, dev, passes):
+    """The matcher of build_from_features on a subset of the scan's pairs: one forward per pair against ragged batches of 16
+    (SuperGlue.match_pairs), ms per pair over the passes; the matches are asserted equal."""
+    import time
+    from onepose_amd import SuperGlue
+    sg = SuperGlue({"GNN_layers": ["self", "cross"] * 9, "sinkhorn_iterations": 100, "match_threshold": 0.7}).eval()
+    sg.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synthetic.make_superglue_passthrough_state_dict(10, 18).items()}, strict=True)
+    sg = sg.to(dev)
+    t = {k: [{n: torch.from_numpy(np.ascontiguousarray(f[n])).to(dev)[None] for n in ("keypoints", "scores", "descriptors")} for f in feats]
+         for k in (0,)}[0]
+    items = [{"keypoints0": t[i]["keypoints"], "scores0": t[i]["scores"], "descriptors0": t[i]["descriptors"], "keypoints1": t[j]["keypoints"],
+              "scores1": t[j]["scores"], "descriptors1": t[j]["descriptors"], "image0": torch.empty(1, 1, 480, 640, device="meta"),
+              "image1": torch.empty(1, 1, 480, 640, device="meta")} for i, j in pairs]
+    loop = lambda: [sg(d)["matches0"] for d in items]                 # noqa: E731
+    batched = lambda: [r["matches0"] for r in sg.match_pairs(items, max_items=16)]     # noqa: E731
+    assert all(torch.equal(x, y) for x, y in zip(loop(), batched()))
+    out = {"pairs": len(items), "keypoints_per_image": [min(int(d["keypoints0"].shape[1]) for d in items), max(int(d["keypoints0"].shape[1]) for d in items)]}
+    for name, fn in (("loop_ms_per_pair", loop), ("pair_batch_16_ms_per_pair", batched)):
+        ts = []
+        for _ in range(passes):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / len(items) * 1e3)
+        ts.sort()
+        out[name] = {"median": round(ts[len(ts) // 2], 3), "min": round(ts[0], 3), "max": round(ts[-1], 3)}
+    out["ragged_beats_loop_by_more_than_its_spread"] = bool(out["loop_ms_per_pair"]["median"] - out["pair_batch_16_ms_per_pair"]["median"]
+                                                            > out["loop_ms_per_pair"]["max"] - out["loop_ms_per_pair"]["min"])
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--views", type=int, default=100)
@@ -53,6 +85,8 @@ def main(argv=None):
     ap.add_argument("--distract", type=int, default=200, help="unmatched keypoints per view")
     ap.add_argument("--neighbours", type=int, default=10)
     ap.add_argument("--passes", type=int, default=7)
+    ap.add_argument("--match-pairs", type=int, default=32, help="image pairs of the scan the matching stage is timed on (0: skip)")
+    ap.add_argument("--match-passes", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "map_bench.json"))
     a = ap.parse_args(argv)
     scene = synthetic.make_map_scene(n_points=a.points, n_views=a.views, hw=(480, 640), seed=0, noise_px=0.3, wrong_frac=0.05,
@@ -108,6 +142,8 @@ def main(argv=None):
     _, y["gather_descriptors_ms"] = host_ms(lambda: mo.gather_descriptors(feats, po, gi, gk))
     res["numpy_yardstick_host"] = y
     res["tail_median_ms_total"] = round(sum(v["median_ms"] for k, v in res["stages"].items()), 3)
+    if a.match_pairs:
+        res["matching"] = matching_stage(feats, [(i, j) for i, j, _ in pm[:a.match_pairs]], dev, a.match_passes)
     line = json.dumps(res)
     print(line)
     with open(a.out, "w") as f:

@@ -4,6 +4,12 @@
 
 Prints one JSON line: per shape pairs/s and ms per pair one at a time and with 4 pairs in flight (StreamRing), algorithmic
 GFLOP per pair, the fraction of the fp32-MFMA peak, the eager restatement's ms per pair, and the time of the Sinkhorn stage alone.
+
+    python tools/superglue_bench.py --ragged [--passes 5] [--steps 3]
+
+The ragged leg instead: b pairs (4, 15, 16) at 512 and 1024 keypoints, with equal counts and with n0, n1 drawn uniformly in
+[0.5, 1] x cap, through SuperGlue.match_pairs (one ragged batch, packing included) beside the same pairs one forward at a time
+and 4 in flight; per leg the median and the min / max over the passes, in ms per pair.  Prints {"ragged": [...]}.
 """
 import argparse
 import json
@@ -50,8 +56,54 @@ def timed(fn, steps, warmup):
     return (time.perf_counter() - t) / steps * 1e3
 
 
+def spread(fn, passes, steps, pairs):
+    """ms per pair: median, min, max over `passes` timings of `steps` calls of fn (fn handles `pairs` pairs)."""
+    t = sorted(timed(fn, steps, 1) / pairs for _ in range(passes))
+    return {"median": round(t[len(t) // 2], 3), "min": round(t[0], 3), "max": round(t[-1], 3)}
+
+
+def ragged_leg(model, dev, ring, passes, steps):
+    rows = []
+    rs = np.random.RandomState(3)
+    for cap in (512, 1024):
+        for b in (4, 15, 16):
+            for draw in ("equal", "ragged"):
+                counts = [(cap, cap)] * b if draw == "equal" else [tuple(int(x) for x in rs.randint(cap // 2, cap + 1, 2)) for _ in range(b)]
+                items = []
+                for k, (n, m) in enumerate(counts):
+                    inp = synthetic.make_superglue_inputs(1, n, m, 512, 512, seed=11 + k)
+                    d = {key: torch.from_numpy(inp[key]).to(dev) for key in ("keypoints0", "keypoints1", "scores0", "scores1",
+                                                                             "descriptors0", "descriptors1")}
+                    d["image0"] = d["image1"] = torch.empty(1, 1, 512, 512, device="meta")
+                    items.append(d)
+
+                def serial():
+                    for d in items:
+                        model(d)
+
+                def four():
+                    for d in items:
+                        with ring.next():
+                            model(d)
+                g = sum(gflop(n, m) for n, m in counts) / b
+                row = {"cap": cap, "b": b, "draw": draw, "mean_n0": round(float(np.mean([c[0] for c in counts])), 1),
+                       "mean_n1": round(float(np.mean([c[1] for c in counts])), 1),
+                       "serial_ms_per_pair": spread(serial, passes, steps, b), "four_in_flight_ms_per_pair": spread(four, passes, steps, b),
+                       "ragged_ms_per_pair": spread(lambda: model.match_pairs(items, max_items=b), passes, steps, b)}
+                row["speedup_vs_serial"] = round(row["serial_ms_per_pair"]["median"] / row["ragged_ms_per_pair"]["median"], 2)
+                row["ragged_beats_serial_by_more_than_its_spread"] = bool(
+                    row["serial_ms_per_pair"]["median"] - row["ragged_ms_per_pair"]["median"]
+                    > row["serial_ms_per_pair"]["max"] - row["serial_ms_per_pair"]["min"])
+                row["frac_fp32_mfma_peak_ragged"] = round(g / row["ragged_ms_per_pair"]["median"] / PEAK_TFLOPS, 4)
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", action="store_true", help="run the ragged-batch leg only")
+    ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default="512x512,1024x1024,2048x2048,4096x4096,1024x2048")
@@ -64,6 +116,10 @@ def main():
     model.to(dev)
     params = {k: torch.from_numpy(np.asarray(v)).to(dev) for k, v in sd.items()}
     ring = StreamRing(dev)
+    if a.ragged:
+        print(json.dumps({"metric": "superglue_ragged_ms_per_pair", "config": "outdoor",
+                          "ragged": ragged_leg(model, dev, ring, a.passes, min(a.steps, 3))}))
+        return
     rows = []
     for shp in a.shapes.split(","):
         n, m = (int(x) for x in shp.split("x"))
