@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_void_p
 
-from ._binding import NativeError, bind  # noqa: F401
+from ._binding import F32, I64, RAW, STREAM, NativeError, bind  # noqa: F401
 from .build_ext import LIB_PATH
 
 NUM_GATS, NUM_ATTN = 4, 8
@@ -41,36 +41,32 @@ class KencWeights(ctypes.Structure):
     _fields_ = [("w", c_void_p * 4), ("b", c_void_p * 4), ("inp_dim", c_int)]
 
 
-# name -> (restype, argtypes); every symbol include/gatsspg.h declares
+_FWD_OUT = [F32, I64, I64, F32, F32, RAW, c_size_t, STREAM]      # conf, matches0 / 1, mscores0 / 1, ws, ws_bytes, stream
+_FWD = [F32, F32, F32, F32, c_int, c_int, c_int, c_int, c_int, c_float, c_float] + _FWD_OUT
+_STATE = [c_int, c_int, c_int, c_int]                             # b, n1, n2, num_leaf
+
+# name -> (restype, parameters); every symbol include/gatsspg.h declares
 SYMBOLS = {
     "gatsspg_version": (c_int, []),
     "gatsspg_last_error": (c_char_p, []),
     "gatsspg_packed_weights_bytes": (c_size_t, []),
-    "gatsspg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "gatsspg_pack_weights": (c_int, [POINTER(RawWeights), c_void_p, c_void_p]),
-    "gatsspg_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
-                                c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "gatsspg_forward_profiled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_size_t, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gatsspg_workspace_bytes": (c_size_t, _STATE),
+    "gatsspg_pack_weights": (c_int, [POINTER(RawWeights), F32, STREAM]),
+    "gatsspg_forward": (c_int, _FWD),
+    "gatsspg_forward_profiled": (c_int, _FWD + [c_int, c_int, c_void_p, c_void_p]),       # ... kernel_id, occurrence, two hipEvent_t
     "gatsspg_db_cache_bytes": (c_size_t, [c_int, c_int]),
-    "gatsspg_prepare_database": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
-                                         c_void_p, c_size_t, c_void_p]),
-    "gatsspg_forward_cached": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
-                                       c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_size_t, c_void_p]),
-    "gatsspg_load_state": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "gatsspg_store_state": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "gatsspg_gats_layer": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
-                                   c_void_p]),
-    "gatsspg_attn_layer": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "gatsspg_final_proj_norm": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "gatsspg_score_dual_softmax_match": (c_int, [c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
-                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gatsspg_prepare_database": (c_int, [F32, F32, F32, c_int, c_int, c_int, c_int, RAW, c_size_t, RAW, c_size_t, STREAM]),
+    "gatsspg_forward_cached": (c_int, [F32, F32, F32, RAW, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_float]
+                               + _FWD_OUT),
+    "gatsspg_load_state": (c_int, [F32, F32] + _STATE + [RAW, c_size_t, STREAM]),
+    "gatsspg_store_state": (c_int, [c_int, F32, F32] + _STATE + [RAW, c_size_t, STREAM]),
+    "gatsspg_gats_layer": (c_int, [F32, c_int, F32] + _STATE + [c_int, RAW, c_size_t, STREAM]),
+    "gatsspg_attn_layer": (c_int, [F32, c_int, c_int] + _STATE + [c_int, RAW, c_size_t, STREAM]),
+    "gatsspg_final_proj_norm": (c_int, [F32] + _STATE + [RAW, c_size_t, STREAM]),
+    "gatsspg_score_dual_softmax_match": (c_int, _STATE + [c_float, c_float] + _FWD_OUT),
     "gatsspg_kenc_scratch_bytes": (c_size_t, [c_int, c_int]),
-    "gatsspg_keypoint_encoder": (c_int, [POINTER(KencWeights), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                         c_size_t, c_void_p]),
+    "gatsspg_keypoint_encoder": (c_int, [POINTER(KencWeights), F32, F32, c_int, c_int, F32, RAW, c_size_t, STREAM]),
 }
 
 _lib = None
-load, check = bind(globals(), "GATsSPG", "gatsspg")
+load, check, call = bind(globals(), "GATsSPG", "gatsspg")

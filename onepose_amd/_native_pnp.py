@@ -1,22 +1,22 @@
 """ctypes binding of libpnp_hip.so (C ABI declared in include/pnp.h).  No fallback: a missing library raises."""
 from __future__ import annotations
 
-from ctypes import POINTER, c_char_p, c_double, c_int, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_int, c_size_t, c_uint64
 
-from ._binding import bind
+from ._binding import F32, F64, I32, I64, RAW, STREAM, bind
 from .build_ext import PNP_LIB_PATH as LIB_PATH
 
-# name -> (restype, argtypes); every symbol include/pnp.h declares
+_K = POINTER(c_double)                                    # K_host: nine HOST doubles
+_OUT = [F64, I32, I32, RAW, c_size_t, STREAM]             # pose, inlier_mask, info, workspace, workspace_bytes, stream
+# name -> (restype, parameters); every symbol include/pnp.h declares
 SYMBOLS = {
     "pnp_version": (c_int, []),
     "pnp_last_error": (c_char_p, []),
     "pnp_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "pnp_ransac_epnp": (c_int, [c_void_p, c_void_p, POINTER(c_double), c_double, c_int, c_double, c_int, c_uint64, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pnp_ransac_epnp_matches": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double), c_double, c_double, c_int, c_uint64,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pnp_epnp": (c_int, [c_void_p, c_void_p, POINTER(c_double), c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnp_ransac_epnp": (c_int, [F32, F32, _K, c_double, c_int, c_double, c_int, c_uint64] + _OUT),
+    "pnp_ransac_epnp_matches": (c_int, [F32, F32, I64, c_int, _K, c_double, c_double, c_int, c_uint64] + _OUT),
+    "pnp_epnp": (c_int, [F32, F32, _K, c_double, c_int, F64, RAW, c_size_t, STREAM]),
 }
 
 _lib = None
-load, check = bind(globals(), "PnP", "pnp")
+load, check, call = bind(globals(), "PnP", "pnp")

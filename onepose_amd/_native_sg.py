@@ -7,7 +7,7 @@ from __future__ import annotations
 
 from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_size_t, c_void_p
 
-from ._binding import bind
+from ._binding import F32, I64, RAW, STREAM, bind
 from .build_ext import SG_LIB_PATH as LIB_PATH
 
 LAYER_SELF, LAYER_CROSS = 0, 1
@@ -19,30 +19,31 @@ def num_raw(n_layers):
     return 29 + 16 * n_layers
 
 
-_P = c_void_p
 _I = POINTER(c_int32)   # a HOST int32 array
-# name -> (restype, argtypes); every symbol include/superglue/superglue.h declares
+_SIDES = [F32, F32, F32, F32, F32, F32]                            # kpts0, scores0, desc0, kpts1, scores1, desc1
+_MATCHES = [I64, I64, F32, F32]                                    # matches0 / 1, mscores0 / 1
+_WS = [RAW, c_size_t, STREAM]                                      # workspace, workspace_bytes, stream
+# name -> (restype, parameters); every symbol include/superglue/superglue.h declares
 SYMBOLS = {
     "sg_version": (c_int, []),
     "sg_last_error": (c_char_p, []),
     "sg_packed_weights_bytes": (c_size_t, [c_int]),
-    "sg_pack_weights": (c_int, [POINTER(c_void_p), c_int, _P, _P]),
+    "sg_pack_weights": (c_int, [POINTER(c_void_p), c_int, F32, STREAM]),
     "sg_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "sg_forward": (c_int, [_P, c_int, POINTER(c_int32), c_int, c_float, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
-                           c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "sg_keypoint_encode": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
-                                   c_size_t, _P]),
-    "sg_layer": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "sg_attention": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
-    "sg_sinkhorn": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
-    "sg_match_tail": (c_int, [_P, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sg_forward": (c_int, [F32, c_int, _I, c_int, c_float] + _SIDES + [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
+                   + _MATCHES + [F32] + _WS),
+    "sg_keypoint_encode": (c_int, [F32, c_int] + _SIDES + [c_int, c_int, c_int, c_int, c_int, c_int, c_int, F32, F32] + _WS),
+    "sg_layer": (c_int, [F32, c_int, c_int, c_int, F32, F32, c_int, c_int, c_int, F32, F32] + _WS),
+    "sg_attention": (c_int, [F32, F32, c_int, c_int, c_int, F32, STREAM]),
+    "sg_sinkhorn": (c_int, [F32, F32, c_int, c_int, c_int, c_int, F32] + _WS),
+    "sg_match_tail": (c_int, [F32, c_int, c_int, c_int, c_float] + _MATCHES + _WS),
     "sg_ragged_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "sg_forward_ragged": (c_int, [_P, c_int, POINTER(c_int32), c_int, c_float, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _I, _I, _I,
-                                  _I, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "sg_attention_ragged": (c_int, [_P, _P, c_int, c_int, c_int, _I, _I, _P, _P]),
-    "sg_sinkhorn_ragged": (c_int, [_P, _P, c_int, c_int, c_int, _I, _I, c_int, _P, _P, c_size_t, _P]),
-    "sg_match_tail_ragged": (c_int, [_P, c_int, c_int, c_int, _I, _I, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sg_forward_ragged": (c_int, [F32, c_int, _I, c_int, c_float] + _SIDES + [c_int, c_int, c_int, _I, _I, _I, _I]
+                          + _MATCHES + [F32] + _WS),
+    "sg_attention_ragged": (c_int, [F32, F32, c_int, c_int, c_int, _I, _I, F32, STREAM]),
+    "sg_sinkhorn_ragged": (c_int, [F32, F32, c_int, c_int, c_int, _I, _I, c_int, F32] + _WS),
+    "sg_match_tail_ragged": (c_int, [F32, c_int, c_int, c_int, _I, _I, c_float] + _MATCHES + _WS),
 }
 
 _lib = None
-load, check = bind(globals(), "SuperGlue", "sg")
+load, check, call = bind(globals(), "SuperGlue", "sg")

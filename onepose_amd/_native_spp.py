@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_void_p
 
-from ._binding import bind
+from ._binding import F32, I32, RAW, STREAM, bind
 from .build_ext import SPP_LIB_PATH as LIB_PATH
 
 NUM_LAYERS = 12
@@ -27,22 +27,22 @@ class RawWeights(ctypes.Structure):
 FLAG_PREC_FP16X4 = 0x800
 PRECISIONS = {"fp32": 0, "fp16x4": FLAG_PREC_FP16X4}   # arithmetic of the GEMM convolutions, a `flags` bit per call
 
-_FWD = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-        c_void_p, c_void_p, c_size_t, c_void_p, c_int]
+_DETECT = [c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, F32, F32, F32, I32]   # b, H, W, nms_radius .. counts
+_WS = [RAW, c_size_t, STREAM]
+_FWD = [F32, F32] + _DETECT + _WS + [c_int]
 
-# name -> (restype, argtypes); every symbol include/superpoint.h declares
+# name -> (restype, parameters); every symbol include/superpoint.h declares
 SYMBOLS = {
     "spp_version": (c_int, []),
     "spp_last_error": (c_char_p, []),
     "spp_packed_weights_bytes": (c_size_t, []),
-    "spp_pack_weights": (c_int, [POINTER(RawWeights), c_void_p, c_void_p]),
+    "spp_pack_weights": (c_int, [POINTER(RawWeights), F32, STREAM]),
     "spp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "spp_dense": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int]),
-    "spp_detect": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p,
-                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "spp_dense": (c_int, [F32, F32, c_int, c_int, c_int, F32, F32] + _WS + [c_int]),
+    "spp_detect": (c_int, [F32, F32] + _DETECT + [F32] + _WS),
     "spp_forward": (c_int, _FWD),
-    "spp_forward_profiled": (c_int, _FWD + [c_int, c_int, c_void_p, c_void_p]),
+    "spp_forward_profiled": (c_int, _FWD + [c_int, c_int, c_void_p, c_void_p]),      # ... kernel_id, occurrence, two hipEvent_t
 }
 
 _lib = None
-load, check = bind(globals(), "SuperPoint", "spp")
+load, check, call = bind(globals(), "SuperPoint", "spp")

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native_det, _native_sg
-from ._binding import NativeError, WorkspaceCache, k_array, stream_handle  # noqa: F401
+from ._binding import NativeError, WorkspaceCache, gpu_tensor, k_array  # noqa: F401
 from .superglue import SuperGlue
 
 REPROJ_THRESHOLD = 6.0     # local_feature_2D_detector.py:105
@@ -211,12 +211,10 @@ class LocalFeatureObjectDetector:
     def _check_frame(self, query_img):
         if not torch.is_tensor(query_img):
             raise TypeError("query_img must be a tensor [1,1,H,W] (or [1,H,W]) in [0, 1]")
-        if not query_img.is_cuda:
-            raise RuntimeError(NO_CPU.format(f"the frame is on {query_img.device}"))
-        img = query_img if query_img.dim() == 4 else query_img[None]
+        img = gpu_tensor(query_img if query_img.dim() == 4 else query_img[None], torch.float32, NO_CPU.format("the frame is on {}"))
         if img.dim() != 4 or img.shape[0] != 1 or img.shape[1] != 1:
             raise ValueError("expected one grayscale frame [1,1,H,W]")
-        return img.to(torch.float32).contiguous()
+        return img
 
     @torch.no_grad()
     def _match_views(self, kpts1, scores1, desc1, query_hw):
@@ -280,19 +278,15 @@ class LocalFeatureObjectDetector:
         """One RANSAC launch over all views and one vote -> dict of device tensors."""
         dev, V, cap0 = self.device, self.V, self.cap0
         ws = self._workspace(dev)
-        k1 = kpts1.to(torch.float32).contiguous()
+        k1 = gpu_tensor(kpts1, torch.float32, NO_CPU.format("the query keypoints are on {}"))
         out = {"affine": torch.empty(V, 2, 3, device=dev, dtype=torch.float64), "mask": torch.empty(V, cap0, device=dev, dtype=torch.int32),
                "info": torch.empty(V, 4, device=dev, dtype=torch.int32), "boxes": torch.empty(V, 4, device=dev, dtype=torch.int32),
                "bbox": torch.empty(4, device=dev, dtype=torch.int32), "best_view": torch.empty(1, device=dev, dtype=torch.int32)}
-        with torch.cuda.device(dev):
-            _native_det.check(self.lib.det_affine_partial_from_matches(
-                self.kpts0.data_ptr(), self.n0.data_ptr(), self.matches0.data_ptr(), k1.data_ptr() if k1.shape[0] else None, V, cap0,
-                int(k1.shape[0]), REPROJ_THRESHOLD, self.iterations, self.seed, out["affine"].data_ptr(), out["mask"].data_ptr(),
-                out["info"].data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "det_affine_partial_from_matches")
-            _native_det.check(self.lib.det_bbox_vote(
-                out["affine"].data_ptr(), out["info"].data_ptr(), self.hw0.data_ptr(), V, int(query_hw[0]), int(query_hw[1]),
-                _native_det.RANK_BY[self.rank_by], out["boxes"].data_ptr(), out["bbox"].data_ptr(), out["best_view"].data_ptr(),
-                stream_handle(dev)), "det_bbox_vote")
+        _native_det.call("det_affine_partial_from_matches", dev, self.kpts0, self.n0, self.matches0, k1 if k1.shape[0] else None, V, cap0,
+                         int(k1.shape[0]), REPROJ_THRESHOLD, self.iterations, self.seed, out["affine"], out["mask"], out["info"], ws,
+                         ws.numel())
+        _native_det.call("det_bbox_vote", dev, out["affine"], out["info"], self.hw0, V, int(query_hw[0]), int(query_hw[1]),
+                         _native_det.RANK_BY[self.rank_by], out["boxes"], out["bbox"], out["best_view"])
         return out
 
     @torch.no_grad()
@@ -305,10 +299,7 @@ class LocalFeatureObjectDetector:
         crop = torch.empty(1, 1, crop_size, crop_size, device=dev, dtype=torch.float32)
         K_crop = torch.empty(3, 3, device=dev, dtype=torch.float64)
         info = torch.empty(4, device=dev, dtype=torch.int32)
-        with torch.cuda.device(dev):
-            _native_det.check(self.lib.det_crop_resize(plane.data_ptr(), H, W, bbox.data_ptr(), _k_array(K), int(crop_size),
-                                                       crop.data_ptr(), K_crop.data_ptr(), info.data_ptr(), stream_handle(dev)),
-                              "det_crop_resize")
+        _native_det.call("det_crop_resize", dev, plane, H, W, bbox, _k_array(K), int(crop_size), crop, K_crop, info)
         return crop, K_crop, info
 
     @torch.no_grad()
@@ -333,9 +324,8 @@ class LocalFeatureObjectDetector:
         """query: dict(keypoints [n,2], scores [n], descriptors [256,n], size (H, W)) on the GPU (numpy is uploaded) ->
         {view id: {"inliers": cv2-style [n_matches, 1] uint8 mask (empty for a failed view), "bbox": [x0, y0, x1, y1]}}."""
         to = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a)).to(self.device)      # noqa: E731
-        kpts1, scores1, desc1 = (to(query[k]).to(torch.float32).contiguous() for k in ("keypoints", "scores", "descriptors"))
-        if not kpts1.is_cuda:
-            raise RuntimeError(NO_CPU.format(f"the query features are on {kpts1.device}"))
+        kpts1, scores1, desc1 = (gpu_tensor(to(query[k]), torch.float32, NO_CPU.format("the query features are on {}"))
+                                 for k in ("keypoints", "scores", "descriptors"))
         self._match_views(kpts1, scores1, desc1, query["size"])
         out = self._tail(kpts1, query["size"])
         self.last = out

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _native
-from ._binding import PackedWeights, WorkspaceCache, on_device, stream_handle
+from ._binding import Engine, gpu_tensor
 
 D = 256
 NUM_HEADS = 4
@@ -99,8 +99,7 @@ class KeypointEncoder(nn.Module):
         if list(self.encoder[0].weight.shape[:1]) != [32] or len(self.encoder) != 10:
             raise NotImplementedError("HIP KeypointEncoder supports the shipped layout [inp,32,64,128,256]")
         lib = _native.load()
-        kpts = _require_gpu(kpts.float().contiguous(), "kpts")
-        scores = _require_gpu(scores.float().contiguous(), "scores")
+        kpts, scores = _gpu(kpts, "kpts"), _gpu(scores, "scores")
         if scores.device != kpts.device:
             raise RuntimeError(f"kpts is on {kpts.device} but scores is on {scores.device}")
         b, n = kpts.shape[0], kpts.shape[1]
@@ -109,18 +108,15 @@ class KeypointEncoder(nn.Module):
         kw = _native.KencWeights()
         keep = []
         for j, idx in enumerate((0, 3, 6, 9)):
-            w = _require_gpu(self.encoder[idx].weight.detach().float().contiguous(), "encoder weight")
-            bb = _require_gpu(self.encoder[idx].bias.detach().float().contiguous(), "encoder bias")
+            w = _gpu(self.encoder[idx].weight.detach(), "encoder weight")
+            bb = _gpu(self.encoder[idx].bias.detach(), "encoder bias")
             keep += [w, bb]
             kw.w[j], kw.b[j] = w.data_ptr(), bb.data_ptr()
         kw.inp_dim = self.inp_dim
-        with torch.cuda.device(kpts.device):   # the C ABI launches on the CURRENT device: make it the tensors' device
-            out = torch.empty(b, D, n, device=kpts.device, dtype=torch.float32)
-            nbytes = lib.gatsspg_kenc_scratch_bytes(b, n)
-            scratch = torch.empty(nbytes, device=kpts.device, dtype=torch.uint8)
-            _native.check(lib.gatsspg_keypoint_encoder(ctypes.byref(kw), kpts.data_ptr(), scores.data_ptr(), b, n,
-                                                       out.data_ptr(), scratch.data_ptr(), nbytes, stream_handle(kpts.device)),
-                          "gatsspg_keypoint_encoder")
+        out = torch.empty(b, D, n, device=kpts.device, dtype=torch.float32)
+        nbytes = lib.gatsspg_kenc_scratch_bytes(b, n)
+        scratch = torch.empty(nbytes, device=kpts.device, dtype=torch.uint8)
+        _native.call("gatsspg_keypoint_encoder", kpts.device, ctypes.byref(kw), kpts, scores, b, n, out, scratch, nbytes)
         return out
 
 
@@ -128,10 +124,8 @@ _NO_CPU = ("onepose_amd.GATsSuperGlue runs only on a ROCm GPU (tensor '{}' is on
            "there is no CPU fallback -- move the module and its inputs to the GPU")
 
 
-def _require_gpu(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(_NO_CPU.format(name, t.device))
-    return t
+def _gpu(t, name):
+    return gpu_tensor(t, torch.float32, _NO_CPU.format(name, "{}"))
 
 
 class Database:
@@ -161,19 +155,18 @@ class Database:
 # --------------------------------------------------------------------------------------------------
 # the engine: packed weights + workspace + stage calls (also used by the per-kernel parity tests)
 # --------------------------------------------------------------------------------------------------
-class GATsSPGEngine:
-    """Owns the device-side packed weights (and their cross-stream ordering: _binding.PackedWeights) and the workspaces
-    (_binding.WorkspaceCache) of one module on one device."""
+class GATsSPGEngine(Engine):
+    """The packed weights, the workspaces (keyed (b, n1, n2, num_leaf), device) and the stage calls of one module."""
 
+    native = _native
+    WORKSPACE_BYTES, LAST_ERROR = "gatsspg_workspace_bytes", "gatsspg_last_error"
+    PARAMETER_REFUSAL = _NO_CPU.format("parameter", "{}")
     # 32 entries cover 8 object databases on 4 streams
     MAX_CACHED_WORKSPACES = 32
     MAX_CACHED_WORKSPACE_BYTES = 32 << 30
 
     def __init__(self, module):
-        self.module = module
-        self.lib = _native.load()
-        self._packed = PackedWeights(_NO_CPU.format("parameter", "{}"))
-        self._workspaces = WorkspaceCache(self.MAX_CACHED_WORKSPACES, self.MAX_CACHED_WORKSPACE_BYTES)
+        super().__init__(module)
         self._slots = None              # (module._parameters dict, name) of every tensor the forward reads, in pack order
 
     @property
@@ -204,9 +197,6 @@ class GATsSPGEngine:
         """Forget the remembered parameter slots (the packed blob is re-validated against the tensors on the next call anyway)."""
         self._slots = None
 
-    def packed_weights(self, device):
-        return self._packed.get(device, self._raw_tensors(), self._pack)
-
     def _pack(self, keep):
         raw = _native.RawWeights()
         it = iter(keep)
@@ -224,13 +214,8 @@ class GATsSPGEngine:
                 ai += 1
         raw.final_w, raw.final_b = next(it).data_ptr(), next(it).data_ptr()
         packed = torch.empty(self.lib.gatsspg_packed_weights_bytes() // 4, device=keep[0].device, dtype=torch.float32)
-        _native.check(self.lib.gatsspg_pack_weights(ctypes.byref(raw), packed.data_ptr(), stream_handle(packed.device)),
-                      "gatsspg_pack_weights")
+        self.call("gatsspg_pack_weights", packed.device, ctypes.byref(raw), packed)
         return packed
-
-    def workspace(self, b, n1, n2, num_leaf, device):
-        return self._workspaces.get((b, n1, n2, num_leaf), device, self.lib.gatsspg_workspace_bytes,
-                                    lambda: "gatsspg_workspace_bytes: " + self.lib.gatsspg_last_error().decode())
 
     def flags(self):
         hp = self.module.hparams
@@ -239,8 +224,13 @@ class GATsSPGEngine:
                 | (_native.FLAG_WITH_LINEAR_TRANSFORM if hp["with_linear_transform"] else 0)
                 | _native.PRECISIONS[self.module.precision])
 
+    def _outputs(self, b, n1, n2, dev):
+        """conf [b,n1,n2], matches0 [b,n1] / matches1 [b,n2] int64, mscores0 / mscores1."""
+        return (torch.empty(b, n1, n2, device=dev, dtype=torch.float32), torch.empty(b, n1, device=dev, dtype=torch.int64),
+                torch.empty(b, n2, device=dev, dtype=torch.int64), torch.empty(b, n1, device=dev, dtype=torch.float32),
+                torch.empty(b, n2, device=dev, dtype=torch.float32))
+
     # ---- whole forward, all b samples ----
-    @on_device
     def forward(self, dq, d3, d2db, scale_factor, match_threshold, database=None):
         b, _, n1 = dq.shape
         n2 = d3.shape[2]
@@ -248,26 +238,16 @@ class GATsSPGEngine:
         dev = dq.device
         packed = self.packed_weights(dev)
         ws = self.workspace(b, n1, n2, num_leaf, dev)
-        conf = torch.empty(b, n1, n2, device=dev, dtype=torch.float32)
-        m0 = torch.empty(b, n1, device=dev, dtype=torch.int64)
-        m1 = torch.empty(b, n2, device=dev, dtype=torch.int64)
-        s0 = torch.empty(b, n1, device=dev, dtype=torch.float32)
-        s1 = torch.empty(b, n2, device=dev, dtype=torch.float32)
+        out = self._outputs(b, n1, n2, dev)
         if database is not None:
             database.check(self, b, n2, num_leaf, dev)
-            _native.check(self.lib.gatsspg_forward_cached(
-                packed.data_ptr(), dq.data_ptr(), database.desc2d_db.data_ptr(), database.cache.data_ptr(),
-                database.cache.numel() * 4, b, n1, n2, num_leaf, self.flags(), float(scale_factor), float(match_threshold),
-                conf.data_ptr(), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(),
-                stream_handle(dev)), "gatsspg_forward_cached")
-            return conf, m0, m1, s0, s1
-        _native.check(self.lib.gatsspg_forward(
-            packed.data_ptr(), dq.data_ptr(), d3.data_ptr(), d2db.data_ptr(), b, n1, n2, num_leaf, self.flags(),
-            float(scale_factor), float(match_threshold), conf.data_ptr(), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(),
-            s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_forward")
-        return conf, m0, m1, s0, s1
+            self.call("gatsspg_forward_cached", dev, packed, dq, database.desc2d_db, database.cache, database.cache.numel() * 4,
+                      b, n1, n2, num_leaf, self.flags(), float(scale_factor), float(match_threshold), *out, ws, ws.numel())
+        else:
+            self.call("gatsspg_forward", dev, packed, dq, d3, d2db, b, n1, n2, num_leaf, self.flags(), float(scale_factor),
+                      float(match_threshold), *out, ws, ws.numel())
+        return out
 
-    @on_device
     def prepare_database(self, d3, d2db):
         """Query-independent part of the first three GNN layers for a resident 3D database (amortised mode)."""
         b, _, n2 = d3.shape
@@ -277,67 +257,43 @@ class GATsSPGEngine:
         nbytes = self.lib.gatsspg_db_cache_bytes(b, n2)
         cache = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
         ws = self.workspace(b, 2, n2, num_leaf, dev)
-        _native.check(self.lib.gatsspg_prepare_database(
-            packed.data_ptr(), d3.data_ptr(), d2db.data_ptr(), b, n2, num_leaf, self.flags(), cache.data_ptr(), nbytes,
-            ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_prepare_database")
+        self.call("gatsspg_prepare_database", dev, packed, d3, d2db, b, n2, num_leaf, self.flags(), cache, nbytes, ws, ws.numel())
         return Database(cache, d3, d2db, b, n2, num_leaf, (self._packed.key, self.flags()))
 
-    # ---- stages (parity tests) ----
-    @on_device
+    # ---- stages (parity tests): ``dims`` = (b, n1, n2, num_leaf, device), what load_state returns ----
     def load_state(self, dq, d3, num_leaf):
-        b, _, n1 = dq.shape
-        n2 = d3.shape[2]
-        ws = self.workspace(b, n1, n2, num_leaf, dq.device)
-        _native.check(self.lib.gatsspg_load_state(dq.data_ptr(), d3.data_ptr(), b, n1, n2, num_leaf, ws.data_ptr(),
-                                                  ws.numel(), stream_handle(dq.device)), "gatsspg_load_state")
-        return (b, n1, n2, num_leaf, dq.device)
+        dims = (dq.shape[0], dq.shape[2], d3.shape[2], num_leaf, dq.device)
+        ws = self.workspace(*dims)
+        self.call("gatsspg_load_state", dq.device, dq, d3, *dims[:4], ws, ws.numel())
+        return dims
 
-    @on_device
     def store_state(self, dims, which=0):
-        b, n1, n2, num_leaf, dev = dims
+        b, n1, n2, _, dev = dims
         ws = self.workspace(*dims)
         o2 = torch.empty(b, D, n1, device=dev, dtype=torch.float32)
         o3 = torch.empty(b, D, n2, device=dev, dtype=torch.float32)
-        _native.check(self.lib.gatsspg_store_state(which, o2.data_ptr(), o3.data_ptr(), b, n1, n2, num_leaf,
-                                                   ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_store_state")
+        self.call("gatsspg_store_state", dev, which, o2, o3, *dims[:4], ws, ws.numel())
         return o2, o3
 
-    @on_device
     def gats_layer(self, dims, layer, d2db, flags=None):
-        b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
-        _native.check(self.lib.gatsspg_gats_layer(self.packed_weights(dev).data_ptr(), layer, d2db.data_ptr(), b, n1, n2,
-                                                  num_leaf, self.flags() if flags is None else flags, ws.data_ptr(),
-                                                  ws.numel(), stream_handle(dev)), "gatsspg_gats_layer")
+        self.call("gatsspg_gats_layer", dims[4], self.packed_weights(dims[4]), layer, d2db, *dims[:4],
+                  self.flags() if flags is None else flags, ws, ws.numel())
 
-    @on_device
     def attn_layer(self, dims, layer, kind):
-        b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
-        _native.check(self.lib.gatsspg_attn_layer(self.packed_weights(dev).data_ptr(), layer, kind, b, n1, n2, num_leaf,
-                                                  self.flags(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_attn_layer")
+        self.call("gatsspg_attn_layer", dims[4], self.packed_weights(dims[4]), layer, kind, *dims[:4], self.flags(), ws, ws.numel())
 
-    @on_device
     def final_proj_norm(self, dims):
-        b, n1, n2, num_leaf, dev = dims
         ws = self.workspace(*dims)
-        _native.check(self.lib.gatsspg_final_proj_norm(self.packed_weights(dev).data_ptr(), b, n1, n2, num_leaf,
-                                                       ws.data_ptr(), ws.numel(), stream_handle(dev)), "gatsspg_final_proj_norm")
+        self.call("gatsspg_final_proj_norm", dims[4], self.packed_weights(dims[4]), *dims[:4], ws, ws.numel())
 
-    @on_device
     def score_match(self, dims, scale_factor, match_threshold):
-        b, n1, n2, num_leaf, dev = dims
+        b, n1, n2, _, dev = dims
         ws = self.workspace(*dims)
-        conf = torch.empty(b, n1, n2, device=dev, dtype=torch.float32)
-        m0 = torch.empty(b, n1, device=dev, dtype=torch.int64)
-        m1 = torch.empty(b, n2, device=dev, dtype=torch.int64)
-        s0 = torch.empty(b, n1, device=dev, dtype=torch.float32)
-        s1 = torch.empty(b, n2, device=dev, dtype=torch.float32)
-        _native.check(self.lib.gatsspg_score_dual_softmax_match(
-            b, n1, n2, num_leaf, float(scale_factor), float(match_threshold), conf.data_ptr(), m0.data_ptr(),
-            m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
-            "gatsspg_score_dual_softmax_match")
-        return conf, m0, m1, s0, s1
+        out = self._outputs(b, n1, n2, dev)
+        self.call("gatsspg_score_dual_softmax_match", dev, *dims[:4], float(scale_factor), float(match_threshold), *out, ws, ws.numel())
+        return out
 
 
 # --------------------------------------------------------------------------------------------------
@@ -407,8 +363,7 @@ class GATsSuperGlue(nn.Module):
         what the first three GNN layers derive from it alone.  ``data`` needs ``descriptors3d_db`` and
         ``descriptors2d_db``; pass the returned handle as ``database=`` to forward()/forward_batched() together
         with the same database tensors.  Results are bit-identical to the plain forward."""
-        d3 = _require_gpu(data["descriptors3d_db"].float().contiguous(), "descriptors3d_db")
-        d2db = _require_gpu(data["descriptors2d_db"].float().contiguous(), "descriptors2d_db")
+        d3, d2db = _gpu(data["descriptors3d_db"], "descriptors3d_db"), _gpu(data["descriptors2d_db"], "descriptors2d_db")
         if d3.shape[2] < 2 or d2db.shape[2] % d3.shape[2] != 0:
             raise ValueError("database needs >= 2 points and a whole number of leaves per point")
         with torch.no_grad():
@@ -422,8 +377,7 @@ class GATsSuperGlue(nn.Module):
         if database is not None:
             data = dict(data, descriptors3d_db=database.desc3d_db, descriptors2d_db=database.desc2d_db)
         _, _, dq, d3, d2db = self._inputs(data)
-        dq, d3, d2db = (_require_gpu(t.contiguous(), n) for t, n in
-                        ((dq, "descriptors2d_query"), (d3, "descriptors3d_db"), (d2db, "descriptors2d_db")))
+        dq, d3, d2db = _gpu(dq, "descriptors2d_query"), _gpu(d3, "descriptors3d_db"), _gpu(d2db, "descriptors2d_db")
         n1, n2 = dq.shape[2], d3.shape[2]
         if n1 == 1 or n2 == 1:  # what nn.InstanceNorm1d raises inside the reference MLP (:126)
             raise ValueError(f"Expected more than 1 spatial element when training, got input size {[dq.shape[0], 512, 1]}")

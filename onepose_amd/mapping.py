@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _native_map, _native_sg
-from ._binding import NativeError, stream_handle
+from ._binding import NativeError
 from .superglue import SuperGlue
 
 THRESHOLDS = dict(max_epipolar_error=4.0, min_pair_inliers=15, max_reproj_error=4.0, min_tri_angle=1.5, max_hypotheses=120,
@@ -145,65 +145,61 @@ class MapTail:
         self.device = torch.device(device)
         self.lib = _native_map.load()
 
-    def _t(self, a, dtype):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.device, dtype=dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(device=self.device, dtype=dtype).contiguous()
-
-    def _call(self, name, *args):
-        with torch.cuda.device(self.device):
-            _native_map.check(getattr(self.lib, name)(*args, stream_handle(self.device)), name)
+    def tensor(self, a, dtype):
+        """``a`` (a tensor or anything array-like: the builder takes numpy) uploaded or moved to this tail's device as a
+        contiguous ``dtype`` tensor."""
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+        return a.to(device=self.device, dtype=dtype).contiguous()
 
     def verify(self, kpts, kpt_offsets, cams, pair_images, match_offsets, matches0, max_epipolar_error=4.0, min_pair_inliers=15):
         """-> (out_matches [sum, 2] int32, counts [P] int32) on the device."""
-        kpts, cams = self._t(kpts, torch.float32), self._t(cams, torch.float64)
-        kpt_offsets, pair_images = self._t(kpt_offsets, torch.int32), self._t(pair_images, torch.int32)
-        match_offsets, matches0 = self._t(match_offsets, torch.int32), self._t(matches0, torch.int64)
+        kpts, cams = self.tensor(kpts, torch.float32), self.tensor(cams, torch.float64)
+        kpt_offsets, pair_images = self.tensor(kpt_offsets, torch.int32), self.tensor(pair_images, torch.int32)
+        match_offsets, matches0 = self.tensor(match_offsets, torch.int32), self.tensor(matches0, torch.int64)
         P, V = pair_images.shape[0], cams.shape[0]
         out = torch.full((max(1, matches0.shape[0]), 2), -1, device=self.device, dtype=torch.int32)
         counts = torch.zeros(P, device=self.device, dtype=torch.int32)
-        self._call("map_verify_matches", kpts.data_ptr(), kpt_offsets.data_ptr(), cams.data_ptr(), V, pair_images.data_ptr(),
-                   match_offsets.data_ptr(), matches0.data_ptr(), P, float(max_epipolar_error), int(min_pair_inliers), out.data_ptr(),
-                   counts.data_ptr())
+        _native_map.call("map_verify_matches", self.device, kpts, kpt_offsets, cams, V, pair_images, match_offsets, matches0, P,
+                         float(max_epipolar_error), int(min_pair_inliers), out, counts)
         return out, counts
 
     def triangulate(self, track_offsets, obs_image, obs_xy, cams, max_track_length, max_reproj_error=4.0, min_tri_angle=1.5,
                     max_hypotheses=120, refine_iterations=10, seed=0):
         """-> (xyz [T,3] float64, inlier_mask [M] int32, info [T,4] int32, lengths [T] int32) on the device."""
-        track_offsets, obs_image = self._t(track_offsets, torch.int32), self._t(obs_image, torch.int32)
-        obs_xy, cams = self._t(obs_xy, torch.float32), self._t(cams, torch.float64)
+        track_offsets, obs_image = self.tensor(track_offsets, torch.int32), self.tensor(obs_image, torch.int32)
+        obs_xy, cams = self.tensor(obs_xy, torch.float32), self.tensor(cams, torch.float64)
         T, M = track_offsets.shape[0] - 1, obs_image.shape[0]
         xyz = torch.full((T, 3), float("nan"), device=self.device, dtype=torch.float64)
         mask = torch.full((max(1, M),), -1, device=self.device, dtype=torch.int32)
         info = torch.full((T, 4), -9, device=self.device, dtype=torch.int32)
         lengths = torch.full((T,), -1, device=self.device, dtype=torch.int32)
-        self._call("map_triangulate_tracks", track_offsets.data_ptr(), obs_image.data_ptr(), obs_xy.data_ptr(), cams.data_ptr(), T,
-                   cams.shape[0], int(max_track_length), float(max_reproj_error), float(min_tri_angle), int(max_hypotheses),
-                   int(refine_iterations), int(seed), xyz.data_ptr(), mask.data_ptr(), info.data_ptr(), lengths.data_ptr())
+        _native_map.call("map_triangulate_tracks", self.device, track_offsets, obs_image, obs_xy, cams, T, cams.shape[0],
+                         int(max_track_length), float(max_reproj_error), float(min_tri_angle), int(max_hypotheses),
+                         int(refine_iterations), int(seed), xyz, mask, info, lengths)
         return xyz, mask[:M], info, lengths
 
     def track_length_threshold(self, lengths, max_num_kp3d):
-        lengths = self._t(lengths, torch.int32)
+        lengths = self.tensor(lengths, torch.int32)
         thr = torch.full((1,), -1, device=self.device, dtype=torch.int32)
-        self._call("map_track_length_threshold", lengths.data_ptr(), lengths.shape[0], int(max_num_kp3d), thr.data_ptr())
+        _native_map.call("map_track_length_threshold", self.device, lengths, lengths.shape[0], int(max_num_kp3d), thr)
         return thr
 
     def filter_points(self, xyz, lengths, threshold, box_corners):
         """-> (kept_ids [n] int32, kept_xyz [n,3] float32) on the device (reads the count: one synchronisation)."""
-        xyz, lengths, threshold = self._t(xyz, torch.float64), self._t(lengths, torch.int32), self._t(threshold, torch.int32)
+        xyz, lengths, threshold = self.tensor(xyz, torch.float64), self.tensor(lengths, torch.int32), self.tensor(threshold, torch.int32)
         T = lengths.shape[0]
         ids = torch.full((T,), -1, device=self.device, dtype=torch.int32)
         out = torch.zeros(T, 3, device=self.device, dtype=torch.float32)
         count = torch.zeros(1, device=self.device, dtype=torch.int32)
         box = (ctypes.c_float * 24)(*np.asarray(box_corners, np.float64).astype(np.float32).reshape(24).tolist())
-        self._call("map_filter_points", xyz.data_ptr(), lengths.data_ptr(), T, threshold.data_ptr(), box, ids.data_ptr(), out.data_ptr(),
-                   count.data_ptr())
+        _native_map.call("map_filter_points", self.device, xyz, lengths, T, threshold, box, ids, out, count)
         n = int(count.item())
         return ids[:n], out[:n]
 
     def merge_points(self, xyz32, dist_threshold=1e-3):
         """-> (merged [n',3] float32, member_offsets [n'+1] int32, members int32) on the device (one synchronisation)."""
-        xyz32 = self._t(xyz32, torch.float32)
+        xyz32 = self.tensor(xyz32, torch.float32)
         n = xyz32.shape[0]
         nbytes = self.lib.map_workspace_bytes(n)
         if nbytes == 0:
@@ -213,8 +209,7 @@ class MapTail:
         offs = torch.zeros(n + 1, device=self.device, dtype=torch.int32)
         members = torch.full((n,), -1, device=self.device, dtype=torch.int32)
         count = torch.zeros(1, device=self.device, dtype=torch.int32)
-        self._call("map_merge_points", xyz32.data_ptr(), n, float(dist_threshold), merged.data_ptr(), offs.data_ptr(), members.data_ptr(),
-                   count.data_ptr(), ws.data_ptr(), nbytes)
+        _native_map.call("map_merge_points", self.device, xyz32, n, float(dist_threshold), merged, offs, members, count, ws, nbytes)
         k = int(count.item())
         offs = offs[:k + 1]
         return merged[:k], offs, members[:int(offs[-1].item())]
@@ -222,22 +217,21 @@ class MapTail:
     def gather(self, descriptors, scores, point_offsets, obs_image, obs_kpt):
         """descriptors: per image a [dim, n_v] float32 device tensor, scores: per image [n_v] ->
         (collect [K,dim] float32, collect_scores [K] float32, idxs [N] int64, mean [N,dim] float64, mean_scores [N] float64)."""
-        descriptors = [self._t(d, torch.float32) for d in descriptors]
-        scores = [self._t(s, torch.float32).reshape(-1) for s in scores]
+        descriptors = [self.tensor(d, torch.float32) for d in descriptors]
+        scores = [self.tensor(s, torch.float32).reshape(-1) for s in scores]
         dim = descriptors[0].shape[0]
         dtab = torch.tensor([d.data_ptr() for d in descriptors], dtype=torch.int64).to(self.device)
         stab = torch.tensor([s.data_ptr() for s in scores], dtype=torch.int64).to(self.device)
         n_kpts = torch.tensor([d.shape[1] for d in descriptors], dtype=torch.int32).to(self.device)
-        point_offsets, obs_image, obs_kpt = (self._t(a, torch.int32) for a in (point_offsets, obs_image, obs_kpt))
+        point_offsets, obs_image, obs_kpt = (self.tensor(a, torch.int32) for a in (point_offsets, obs_image, obs_kpt))
         N, K = point_offsets.shape[0] - 1, obs_image.shape[0]
         cd = torch.full((max(1, K), dim), float("nan"), device=self.device, dtype=torch.float32)
         cs = torch.full((max(1, K),), float("nan"), device=self.device, dtype=torch.float32)
         idxs = torch.full((N,), -1, device=self.device, dtype=torch.int64)
         md = torch.full((N, dim), float("nan"), device=self.device, dtype=torch.float64)
         ms = torch.full((N,), float("nan"), device=self.device, dtype=torch.float64)
-        self._call("map_gather_descriptors", dtab.data_ptr(), stab.data_ptr(), n_kpts.data_ptr(), len(descriptors), point_offsets.data_ptr(),
-                   obs_image.data_ptr(), obs_kpt.data_ptr(), N, dim, cd.data_ptr(), cs.data_ptr(), idxs.data_ptr(), md.data_ptr(),
-                   ms.data_ptr())
+        _native_map.call("map_gather_descriptors", self.device, dtab, stab, n_kpts, len(descriptors), point_offsets, obs_image, obs_kpt,
+                         N, dim, cd, cs, idxs, md, ms)
         torch.cuda.synchronize(self.device)      # the pointer tables and the per-image tensors must outlive the kernel
         return cd[:K], cs[:K], idxs, md, ms
 
@@ -363,14 +357,14 @@ class ObjectMapper:
         V = len(features)
         n_kpts = [int(f["keypoints"].shape[0]) for f in features]
         kpt_offsets = np.concatenate([[0], np.cumsum(n_kpts)]).astype(np.int32)
-        kpts = torch.cat([tail._t(f["keypoints"], torch.float32).reshape(-1, 2) for f in features])
+        kpts = torch.cat([tail.tensor(f["keypoints"], torch.float32).reshape(-1, 2) for f in features])
         cams = make_cams(Ks, poses)
         if len(cams) != V:
             raise ValueError(f"{V} images but {len(cams)} poses")
         if not pair_matches:
             raise ValueError("no image pairs")
         pair_images = np.array([(i, j) for i, j, _ in pair_matches], np.int32)
-        m0 = [tail._t(m, torch.int64).reshape(-1) for _, _, m in pair_matches]
+        m0 = [tail.tensor(m, torch.int64).reshape(-1) for _, _, m in pair_matches]
         for (i, j, _), m in zip(pair_matches, m0):
             if m.shape[0] != n_kpts[i]:
                 raise ValueError(f"pair ({i}, {j}): matches0 has {m.shape[0]} entries, image {i} has {n_kpts[i]} keypoints")

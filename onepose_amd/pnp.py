@@ -12,8 +12,9 @@ import numpy as np
 import torch
 
 from . import _native_pnp
-from ._binding import NativeError, k_array as _k_array, stream_handle  # noqa: F401
+from ._binding import NativeError, gpu_tensor, k_array as _k_array  # noqa: F401
 
+NO_CPU = "onepose_amd.pnp runs only on a ROCm GPU (there is no CPU fallback)"
 REPROJ_ERROR = 5.0        # eval_utils.py:30
 ITERATIONS = 10000        # eval_utils.py:31
 
@@ -22,11 +23,8 @@ ITERATIONS = 10000        # eval_utils.py:31
 def ransac_pnp_device(K, pts_2d, pts_3d, scale=1.0, reproj_error=REPROJ_ERROR, iterations=ITERATIONS, seed=0):
     """pts_2d [n,2], pts_3d [n,3] GPU tensors -> (pose [3,4] float64, inlier_mask [n] int32, info [4] int32:
     ok, inliers, best hypothesis, its count), all on the GPU, nothing synchronised."""
-    if not (pts_2d.is_cuda and pts_3d.is_cuda):
-        raise RuntimeError("onepose_amd.pnp runs only on a ROCm GPU (there is no CPU fallback)")
-    dev = pts_2d.device
-    p2 = pts_2d.to(torch.float32).contiguous()
-    p3 = pts_3d.to(torch.float32).contiguous()
+    p2, p3 = gpu_tensor(pts_2d, torch.float32, NO_CPU), gpu_tensor(pts_3d, torch.float32, NO_CPU)
+    dev = p2.device
     n = p2.shape[0]
     lib = _native_pnp.load()
     nbytes = lib.pnp_workspace_bytes(n, iterations)
@@ -34,10 +32,8 @@ def ransac_pnp_device(K, pts_2d, pts_3d, scale=1.0, reproj_error=REPROJ_ERROR, i
     pose = torch.empty(3, 4, device=dev, dtype=torch.float64)
     mask = torch.zeros(max(n, 1), device=dev, dtype=torch.int32)
     info = torch.zeros(4, device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):   # the C ABI launches on the current device
-        _native_pnp.check(lib.pnp_ransac_epnp(p3.data_ptr(), p2.data_ptr(), _k_array(K), float(scale), n, float(reproj_error),
-                                              int(iterations), int(seed), pose.data_ptr(), mask.data_ptr(), info.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), stream_handle(dev)), "pnp_ransac_epnp")
+    _native_pnp.call("pnp_ransac_epnp", dev, p3, p2, _k_array(K), float(scale), n, float(reproj_error), int(iterations), int(seed),
+                     pose, mask, info, ws, ws.numel())
     return pose, mask[:n], info
 
 
@@ -45,22 +41,17 @@ def ransac_pnp_device(K, pts_2d, pts_3d, scale=1.0, reproj_error=REPROJ_ERROR, i
 def ransac_pnp_from_matches(K, kpts2d, kpts3d, matches0, scale=1.0, reproj_error=REPROJ_ERROR, iterations=ITERATIONS, seed=0):
     """inference.py:148-155 without a host round trip: kpts2d [n1,2] (extractor), kpts3d [N3,3] (database), matches0 [n1]
     int64 (-1 = unmatched), all on the GPU -> (pose [3,4] float64, inlier_mask [n1] int32 per query keypoint, info [4])."""
-    if not (kpts2d.is_cuda and kpts3d.is_cuda and matches0.is_cuda):
-        raise RuntimeError("onepose_amd.pnp runs only on a ROCm GPU (there is no CPU fallback)")
-    dev = kpts2d.device
-    k2 = kpts2d.to(torch.float32).contiguous()
-    k3 = kpts3d.to(torch.float32).contiguous()
-    m0 = matches0.to(torch.int64).contiguous()
+    k2, k3 = gpu_tensor(kpts2d, torch.float32, NO_CPU), gpu_tensor(kpts3d, torch.float32, NO_CPU)
+    m0 = gpu_tensor(matches0, torch.int64, NO_CPU)
+    dev = k2.device
     n1 = k2.shape[0]
     lib = _native_pnp.load()
     ws = torch.empty(lib.pnp_workspace_bytes(n1, iterations), device=dev, dtype=torch.uint8)
     pose = torch.empty(3, 4, device=dev, dtype=torch.float64)
     mask = torch.empty(n1, device=dev, dtype=torch.int32)
     info = torch.empty(4, device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        _native_pnp.check(lib.pnp_ransac_epnp_matches(k2.data_ptr(), k3.data_ptr(), m0.data_ptr(), n1, _k_array(K), float(scale),
-                                                      float(reproj_error), int(iterations), int(seed), pose.data_ptr(), mask.data_ptr(),
-                                                      info.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "pnp_ransac_epnp_matches")
+    _native_pnp.call("pnp_ransac_epnp_matches", dev, k2, k3, m0, n1, _k_array(K), float(scale), float(reproj_error), int(iterations),
+                     int(seed), pose, mask, info, ws, ws.numel())
     return pose, mask, info
 
 
@@ -68,7 +59,7 @@ def ransac_PnP(K, pts_2d, pts_3d, scale=1, iterations=ITERATIONS, seed=0):
     """ solve pnp -- drop-in for eval_utils.ransac_PnP (:18-42); numpy or tensor inputs, numpy outputs."""
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     if dev is None:
-        raise RuntimeError("onepose_amd.pnp runs only on a ROCm GPU (there is no CPU fallback)")
+        raise RuntimeError(NO_CPU)
     to = lambda a: a if isinstance(a, torch.Tensor) and a.is_cuda else torch.as_tensor(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float32)).to(dev)  # noqa: E731
     p2, p3 = to(pts_2d), to(pts_3d)
     if p2.shape[0] < 5:                       # cv2 raises / returns false for fewer than the 5 model points: :40-42
@@ -85,13 +76,9 @@ def ransac_PnP(K, pts_2d, pts_3d, scale=1, iterations=ITERATIONS, seed=0):
 @torch.no_grad()
 def epnp(K, pts_2d, pts_3d, scale=1.0):
     """EPnP over all correspondences (cv2.solvePnP(flags=SOLVEPNP_EPNP)) -> pose [3,4] float64 on the GPU."""
-    p2 = pts_2d.to(torch.float32).contiguous()
-    p3 = pts_3d.to(torch.float32).contiguous()
+    p2, p3 = gpu_tensor(pts_2d, torch.float32, NO_CPU), gpu_tensor(pts_3d, torch.float32, NO_CPU)
     pose = torch.empty(3, 4, device=p2.device, dtype=torch.float64)
-    lib = _native_pnp.load()
-    with torch.cuda.device(p2.device):
-        _native_pnp.check(lib.pnp_epnp(p3.data_ptr(), p2.data_ptr(), _k_array(K), float(scale), p2.shape[0], pose.data_ptr(), None, 0,
-                                       stream_handle(p2.device)), "pnp_epnp")
+    _native_pnp.call("pnp_epnp", p2.device, p3, p2, _k_array(K), float(scale), p2.shape[0], pose, None, 0)
     return pose
 
 

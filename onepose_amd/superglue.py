@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import _native_sg
-from ._binding import PackedWeights, WorkspaceCache, on_device, stream_handle
+from ._binding import Engine, gpu_tensor
 
 D = 256
 HEADS = 4
@@ -59,12 +59,11 @@ class _AttentionalGNN(nn.Module):
         self.names = list(names)
 
 
-def _check(t, name, dev):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if t.device != dev:
-        raise ValueError(f"{name} is on {t.device}, expected {dev}")
-    return t.to(torch.float32).contiguous()
+NO_CPU = "onepose_amd.SuperGlue runs only on a ROCm GPU ({} on {}); there is no CPU fallback"
+
+
+def _gpu(t, name):
+    return gpu_tensor(t, torch.float32, NO_CPU.format(name + " is", "{}"))
 
 
 IN_KEYS = ("keypoints0", "scores0", "descriptors0", "keypoints1", "scores1", "descriptors1")
@@ -122,41 +121,35 @@ def _host_i32(values, b, width, name):
     return (ctypes.c_int32 * len(flat))(*flat)
 
 
-class SuperGlueEngine:
+class SuperGlueEngine(Engine):
     """Raw-tensor entry to the HIP matcher of one module: packed weights once per weight version and device, workspaces
     cached per (shape, device, stream) so one module serves several streams at once.  Outputs may be preallocated
-    (``out=``) by callers that keep frames in flight."""
+    (``out=``) by callers that keep frames in flight.  The uniform and the ragged entry points share their validation and
+    one workspace cache."""
 
-    def __init__(self, module):
-        self.module = module
-        self.lib = _native_sg.load()
-        self._packed = PackedWeights("onepose_amd.SuperGlue runs only on a ROCm GPU (a parameter is on {}); "
-                                     "there is no CPU fallback -- move the module to the GPU")
-        self._workspaces = WorkspaceCache(6)
-        self._ragged_workspaces = WorkspaceCache(6)
+    native = _native_sg
+    WORKSPACE_BYTES, LAST_ERROR = "sg_workspace_bytes", "sg_last_error"
+    PARAMETER_REFUSAL = NO_CPU.format("a parameter is", "{}") + " -- move the module to the GPU"
+    MAX_CACHED_WORKSPACES = 12          # six uniform and six ragged shapes: one key, (b, n0 | cap0, n1 | cap1), and one size
 
-    def _raw(self):
-        """(module, name) of every float tensor of the state_dict in its order, read through getattr on every call."""
-        m = self.module
-        return [getattr(sub, name) for sub, name in m._raw_slots]
-
-    def packed_weights(self, device):
-        return self._packed.get(device, self._raw(), self._pack)
+    def _raw_tensors(self):
+        """Every float tensor of the state_dict in its order, read through getattr on every call."""
+        return [getattr(sub, name) for sub, name in self.module._raw_slots]
 
     def _pack(self, keep):
         n_layers = self.module.n_layers
         ptrs = (ctypes.c_void_p * len(keep))(*[k.data_ptr() for k in keep])
         packed = torch.empty(self.lib.sg_packed_weights_bytes(n_layers) // 4, device=keep[0].device, dtype=torch.float32)
-        _native_sg.check(self.lib.sg_pack_weights(ptrs, n_layers, packed.data_ptr(), stream_handle(packed.device)), "sg_pack_weights")
+        self.call("sg_pack_weights", packed.device, ptrs, n_layers, packed)
         return packed
 
-    def workspace(self, b, n0, n1, device):
-        return self._workspaces.get((b, n0, n1), device, self.lib.sg_workspace_bytes,
-                                    lambda: f"sg_workspace_bytes({b}, {n0}, {n1}) refused the shape")
+    def workspace_refusal(self, shape):
+        return "sg_workspace_bytes({}, {}, {}) refused the shape".format(*shape)
 
     def ragged_workspace(self, b, cap0, cap1, device):
-        return self._ragged_workspaces.get((b, cap0, cap1), device, self.lib.sg_ragged_workspace_bytes,
-                                           lambda: f"sg_ragged_workspace_bytes({b}, {cap0}, {cap1}) refused the shape")
+        """``workspace`` under the ragged limits (b <= 64): the same bytes in the same cache under the same key."""
+        return self._workspaces.get((b, cap0, cap1), device, self.lib.sg_ragged_workspace_bytes,
+                                    lambda: f"sg_ragged_workspace_bytes({b}, {cap0}, {cap1}) refused the shape")
 
     @staticmethod
     def outputs(b, n0, n1, device):
@@ -164,160 +157,136 @@ class SuperGlueEngine:
         return (torch.empty(b, n0, device=device, dtype=torch.int64), torch.empty(b, n1, device=device, dtype=torch.int64),
                 torch.empty(b, n0, device=device, dtype=torch.float32), torch.empty(b, n1, device=device, dtype=torch.float32))
 
-    @on_device
-    def forward(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1, out=None, z_out=None):
-        """kpts [b,n,2], scores [b,n], desc [b,256,n] on one GPU; hw = (H, W) of each image.  Returns the four outputs."""
-        dev = kpts0.device
-        k0, s0, d0 = _check(kpts0, "keypoints0", dev), _check(scores0, "scores0", dev), _check(desc0, "descriptors0", dev)
-        k1, s1, d1 = _check(kpts1, "keypoints1", dev), _check(scores1, "scores1", dev), _check(desc1, "descriptors1", dev)
+    def _validate(self, inputs, out, z_out, n):
+        """The six inputs, ``out=`` and ``z_out`` of ``forward`` (n = "n") and ``forward_ragged`` (n = "cap"): the inputs as fp32
+        contiguous tensors of one GPU and of consistent shapes, the buffers of the right shape and contiguous.  The dtype of
+        the ``out=`` buffers is checked where they enter the library.  -> (the six tensors, b, n0 | cap0, n1 | cap1)."""
+        t = [_gpu(x, key) for x, key in zip(inputs, IN_KEYS)]
+        k0, s0, d0, k1, s1, d1 = t
+        for x, key in zip(t, IN_KEYS):
+            if x.device != k0.device:
+                raise ValueError(f"{key} is on {x.device}, expected {k0.device}")
         b, n0, n1 = k0.shape[0], k0.shape[1], k1.shape[1]
         if d0.shape != (b, D, n0) or d1.shape != (b, D, n1) or s0.shape != (b, n0) or s1.shape != (b, n1) or k1.shape[0] != b:
-            raise ValueError("inconsistent shapes: keypoints [b,n,2], scores [b,n], descriptors [b,256,n] with one b")
-        cfg = self.module.config
-        ws = self.workspace(b, n0, n1, dev)
-        m0, m1, ms0, ms1 = out if out is not None else self.outputs(b, n0, n1, dev)
+            raise ValueError(f"inconsistent shapes: keypoints [b,{n},2], scores [b,{n}], descriptors [b,256,{n}] with one b")
+        for x, cap, name in zip(out or (), (n0, n1, n0, n1), OUT_KEYS):
+            if x.shape != (b, cap) or not x.is_contiguous():
+                raise ValueError(f"out: {name} must be a contiguous [{b}, {cap}] tensor")
         if z_out is not None and (z_out.shape != (b, n0 + 1, n1 + 1) or z_out.dtype != torch.float32 or not z_out.is_contiguous()):
-            raise ValueError("z_out must be a contiguous fp32 [b, n0+1, n1+1] tensor")
-        kinds = (ctypes.c_int32 * max(1, self.module.n_layers))(*self.module.layer_kinds)
-        _native_sg.check(self.lib.sg_forward(
-            self.packed_weights(dev).data_ptr(), self.module.n_layers, kinds, int(cfg["sinkhorn_iterations"]),
-            float(cfg["match_threshold"]), k0.data_ptr(), s0.data_ptr(), d0.data_ptr(), k1.data_ptr(), s1.data_ptr(), d1.data_ptr(),
-            b, n0, n1, int(hw0[0]), int(hw0[1]), int(hw1[0]), int(hw1[1]), m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(),
-            ms1.data_ptr(), z_out.data_ptr() if z_out is not None else None, ws.data_ptr(), ws.numel(), stream_handle(dev)), "sg_forward")
-        return m0, m1, ms0, ms1
+            raise ValueError(f"z_out must be a contiguous fp32 [b, {n}0+1, {n}1+1] tensor")
+        return t, b, n0, n1
 
-    @on_device
+    def _head(self, dev, t, b, n0, n1):
+        """The arguments sg_forward and sg_forward_ragged begin with."""
+        cfg = self.module.config
+        kinds = (ctypes.c_int32 * max(1, self.module.n_layers))(*self.module.layer_kinds)
+        return (self.packed_weights(dev), self.module.n_layers, kinds, int(cfg["sinkhorn_iterations"]), float(cfg["match_threshold"]),
+                *t, b, n0, n1)
+
+    def forward(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1, out=None, z_out=None):
+        """kpts [b,n,2], scores [b,n], desc [b,256,n] on one GPU; hw = (H, W) of each image.  Returns the four outputs."""
+        t, b, n0, n1 = self._validate((kpts0, scores0, desc0, kpts1, scores1, desc1), out, z_out, "n")
+        dev = t[0].device
+        ws = self.workspace(b, n0, n1, dev)
+        out = tuple(out) if out is not None else self.outputs(b, n0, n1, dev)
+        self.call("sg_forward", dev, *self._head(dev, t, b, n0, n1), int(hw0[0]), int(hw0[1]), int(hw1[0]), int(hw1[1]), *out, z_out,
+                  ws, ws.numel())
+        return out
+
     def forward_ragged(self, kpts0, scores0, desc0, kpts1, scores1, desc1, n0, n1, hw0, hw1, out=None, z_out=None):
         """b pairs in one chain of launches: inputs padded to [b,cap0,2] / [b,cap0] / [b,256,cap0] (and cap1), host lists
         n0, n1 (1 <= n <= cap) and hw0, hw1 ((H, W) per item).  Returns the four outputs padded to [b,cap0] / [b,cap1], -1 / 0
         past an item's count; every item is bitwise what ``forward`` gives on that pair alone.  z_out: [b,cap0+1,cap1+1]."""
-        dev = kpts0.device
-        k0, s0, d0 = _check(kpts0, "keypoints0", dev), _check(scores0, "scores0", dev), _check(desc0, "descriptors0", dev)
-        k1, s1, d1 = _check(kpts1, "keypoints1", dev), _check(scores1, "scores1", dev), _check(desc1, "descriptors1", dev)
-        b, cap0, cap1 = k0.shape[0], k0.shape[1], k1.shape[1]
-        if d0.shape != (b, D, cap0) or d1.shape != (b, D, cap1) or s0.shape != (b, cap0) or s1.shape != (b, cap1) or k1.shape[0] != b:
-            raise ValueError("inconsistent shapes: keypoints [b,cap,2], scores [b,cap], descriptors [b,256,cap] with one b")
-        cn0, cn1 = _host_i32(n0, b, 1, "n0"), _host_i32(n1, b, 1, "n1")
-        chw0, chw1 = _host_i32(hw0, b, 2, "hw0"), _host_i32(hw1, b, 2, "hw1")
-        cfg = self.module.config
-        m0, m1, ms0, ms1 = out if out is not None else self.outputs(b, cap0, cap1, dev)
-        for t, cap, name in ((m0, cap0, "matches0"), (m1, cap1, "matches1"), (ms0, cap0, "matching_scores0"), (ms1, cap1, "matching_scores1")):
-            if t.shape != (b, cap) or not t.is_contiguous():
-                raise ValueError(f"out: {name} must be a contiguous [{b}, {cap}] tensor")
-        if z_out is not None and (z_out.shape != (b, cap0 + 1, cap1 + 1) or z_out.dtype != torch.float32 or not z_out.is_contiguous()):
-            raise ValueError("z_out must be a contiguous fp32 [b, cap0+1, cap1+1] tensor")
+        t, b, cap0, cap1 = self._validate((kpts0, scores0, desc0, kpts1, scores1, desc1), out, z_out, "cap")
+        dev = t[0].device
+        sizes = (_host_i32(n0, b, 1, "n0"), _host_i32(n1, b, 1, "n1"), _host_i32(hw0, b, 2, "hw0"), _host_i32(hw1, b, 2, "hw1"))
+        out = tuple(out) if out is not None else self.outputs(b, cap0, cap1, dev)
         ws = self.ragged_workspace(b, cap0, cap1, dev)
-        kinds = (ctypes.c_int32 * max(1, self.module.n_layers))(*self.module.layer_kinds)
-        _native_sg.check(self.lib.sg_forward_ragged(
-            self.packed_weights(dev).data_ptr(), self.module.n_layers, kinds, int(cfg["sinkhorn_iterations"]),
-            float(cfg["match_threshold"]), k0.data_ptr(), s0.data_ptr(), d0.data_ptr(), k1.data_ptr(), s1.data_ptr(), d1.data_ptr(),
-            b, cap0, cap1, cn0, cn1, chw0, chw1, m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(), ms1.data_ptr(),
-            z_out.data_ptr() if z_out is not None else None, ws.data_ptr(), ws.numel(), stream_handle(dev)), "sg_forward_ragged")
-        return m0, m1, ms0, ms1
-
-    # ---- stages (tests) ----
-    @on_device
-    def attention_ragged(self, q, kv, n, m):
-        """``attention`` on q [b,256,capN], kv [b,512,capM] with per-item counts n, m (host lists); columns past n[i] of
-        the result are not written."""
-        dev = q.device
-        qq, kk = _check(q, "q", dev), _check(kv, "kv", dev)
-        if qq.dim() != 3 or kk.dim() != 3 or qq.shape[1] != D or kk.shape[1] != 2 * D or kk.shape[0] != qq.shape[0]:
-            raise ValueError("q must be [b,256,capN] and kv [b,512,capM] with one b")
-        b = qq.shape[0]
-        out = torch.zeros_like(qq)
-        _native_sg.check(self.lib.sg_attention_ragged(qq.data_ptr(), kk.data_ptr(), b, qq.shape[2], kk.shape[2], _host_i32(n, b, 1, "n"),
-                                                      _host_i32(m, b, 1, "m"), out.data_ptr(), stream_handle(dev)), "sg_attention_ragged")
+        self.call("sg_forward_ragged", dev, *self._head(dev, t, b, cap0, cap1), *sizes, *out, z_out, ws, ws.numel())
         return out
 
-    @on_device
-    def sinkhorn_ragged(self, scores, bin_score, n0, n1, iters):
-        """``sinkhorn`` on scores [b,cap0,cap1] with per-item counts -> z [b,cap0+1,cap1+1] (zero outside an item's block)."""
-        dev = scores.device
-        sc = _check(scores, "scores", dev)
-        alpha = _check(torch.as_tensor(bin_score, dtype=torch.float32, device=dev).reshape(1), "bin_score", dev)
-        b, cap0, cap1 = sc.shape
-        ws = self.ragged_workspace(b, cap0, cap1, dev)
-        z = torch.zeros(b, cap0 + 1, cap1 + 1, device=dev, dtype=torch.float32)
-        _native_sg.check(self.lib.sg_sinkhorn_ragged(sc.data_ptr(), alpha.data_ptr(), b, cap0, cap1, _host_i32(n0, b, 1, "n0"),
-                                                     _host_i32(n1, b, 1, "n1"), int(iters), z.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     stream_handle(dev)), "sg_sinkhorn_ragged")
-        return z
-
-    @on_device
-    def match_tail_ragged(self, z, n0, n1, match_threshold):
-        dev = z.device
-        zz = _check(z, "z", dev)
-        b, cap0, cap1 = zz.shape[0], zz.shape[1] - 1, zz.shape[2] - 1
-        ws = self.ragged_workspace(b, cap0, cap1, dev)
-        m0, m1, s0, s1 = self.outputs(b, cap0, cap1, dev)
-        _native_sg.check(self.lib.sg_match_tail_ragged(zz.data_ptr(), b, cap0, cap1, _host_i32(n0, b, 1, "n0"), _host_i32(n1, b, 1, "n1"),
-                                                       float(match_threshold), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(),
-                                                       s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
-                         "sg_match_tail_ragged")
-        return m0, m1, s0, s1
-
-    @on_device
+    # ---- stages (tests): a uniform stage and its ragged variant (per-item counts as host lists) share their validation ----
     def keypoint_encode(self, kpts0, scores0, desc0, kpts1, scores1, desc1, hw0, hw1):
-        dev = kpts0.device
-        t = [_check(x, "input", dev) for x in (kpts0, scores0, desc0, kpts1, scores1, desc1)]
+        t = [_gpu(x, "input") for x in (kpts0, scores0, desc0, kpts1, scores1, desc1)]
+        dev = t[0].device
         b, n0, n1 = t[0].shape[0], t[0].shape[1], t[3].shape[1]
         ws = self.workspace(b, n0, n1, dev)
         o0, o1 = torch.empty_like(t[2]), torch.empty_like(t[5])
-        _native_sg.check(self.lib.sg_keypoint_encode(
-            self.packed_weights(dev).data_ptr(), self.module.n_layers, *[x.data_ptr() for x in t], b, n0, n1, int(hw0[0]),
-            int(hw0[1]), int(hw1[0]), int(hw1[1]), o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
-            "sg_keypoint_encode")
+        self.call("sg_keypoint_encode", dev, self.packed_weights(dev), self.module.n_layers, *t, b, n0, n1, int(hw0[0]), int(hw0[1]),
+                  int(hw1[0]), int(hw1[1]), o0, o1, ws, ws.numel())
         return o0, o1
 
-    @on_device
     def layer(self, index, desc0, desc1):
-        dev = desc0.device
-        d0, d1 = _check(desc0, "desc0", dev), _check(desc1, "desc1", dev)
+        d0, d1 = _gpu(desc0, "desc0"), _gpu(desc1, "desc1")
+        dev = d0.device
         b, n0, n1 = d0.shape[0], d0.shape[2], d1.shape[2]
         ws = self.workspace(b, n0, n1, dev)
         o0, o1 = torch.empty_like(d0), torch.empty_like(d1)
-        _native_sg.check(self.lib.sg_layer(
-            self.packed_weights(dev).data_ptr(), self.module.n_layers, index, self.module.layer_kinds[index], d0.data_ptr(),
-            d1.data_ptr(), b, n0, n1, o0.data_ptr(), o1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)), "sg_layer")
+        self.call("sg_layer", dev, self.packed_weights(dev), self.module.n_layers, index, self.module.layer_kinds[index], d0, d1,
+                  b, n0, n1, o0, o1, ws, ws.numel())
         return o0, o1
 
-    @on_device
+    @staticmethod
+    def _q_kv(q, kv, n, m):
+        qq, kk = _gpu(q, "q"), _gpu(kv, "kv")
+        if qq.dim() != 3 or kk.dim() != 3 or qq.shape[1] != D or kk.shape[1] != 2 * D or kk.shape[0] != qq.shape[0]:
+            raise ValueError(f"q must be [b,256,{n}] and kv [b,512,{m}] with one b")
+        return qq, kk, qq.shape[0]
+
     def attention(self, q, kv):
         """Softmax attention of the layers' kernel on head-contiguous q [b,256,N] and kv [b,512,M] (k rows, then v rows);
         returns [b,256,N]: per head h, out[h*64+d] = sum_m softmax_m(q_h . k_h[:, m] / 8) v[h*64+d, m]."""
-        dev = q.device
-        qq, kk = _check(q, "q", dev), _check(kv, "kv", dev)
-        if qq.dim() != 3 or kk.dim() != 3 or qq.shape[1] != D or kk.shape[1] != 2 * D or kk.shape[0] != qq.shape[0]:
-            raise ValueError("q must be [b,256,N] and kv [b,512,M] with one b")
-        b, n, m = qq.shape[0], qq.shape[2], kk.shape[2]
+        qq, kk, b = self._q_kv(q, kv, "N", "M")
         out = torch.empty_like(qq)
-        _native_sg.check(self.lib.sg_attention(qq.data_ptr(), kk.data_ptr(), b, n, m, out.data_ptr(), stream_handle(dev)), "sg_attention")
+        self.call("sg_attention", qq.device, qq, kk, b, qq.shape[2], kk.shape[2], out)
         return out
 
-    @on_device
+    def attention_ragged(self, q, kv, n, m):
+        """``attention`` on q [b,256,capN], kv [b,512,capM] with per-item counts n, m (host lists); columns past n[i] of
+        the result are not written."""
+        qq, kk, b = self._q_kv(q, kv, "capN", "capM")
+        out = torch.zeros_like(qq)
+        self.call("sg_attention_ragged", qq.device, qq, kk, b, qq.shape[2], kk.shape[2], _host_i32(n, b, 1, "n"),
+                  _host_i32(m, b, 1, "m"), out)
+        return out
+
+    @staticmethod
+    def _scores(scores, bin_score):
+        sc = _gpu(scores, "scores")
+        return sc, torch.as_tensor(bin_score, dtype=torch.float32, device=sc.device).reshape(1), sc.device, sc.shape
+
     def sinkhorn(self, scores, bin_score, iters):
-        dev = scores.device
-        sc = _check(scores, "scores", dev)
-        alpha = _check(torch.as_tensor(bin_score, dtype=torch.float32, device=dev).reshape(1), "bin_score", dev)
-        b, n0, n1 = sc.shape
+        sc, alpha, dev, (b, n0, n1) = self._scores(scores, bin_score)
         ws = self.workspace(b, n0, n1, dev)
         z = torch.empty(b, n0 + 1, n1 + 1, device=dev, dtype=torch.float32)
-        _native_sg.check(self.lib.sg_sinkhorn(sc.data_ptr(), alpha.data_ptr(), b, n0, n1, int(iters), z.data_ptr(), ws.data_ptr(),
-                                              ws.numel(), stream_handle(dev)), "sg_sinkhorn")
+        self.call("sg_sinkhorn", dev, sc, alpha, b, n0, n1, int(iters), z, ws, ws.numel())
         return z
 
-    @on_device
+    def sinkhorn_ragged(self, scores, bin_score, n0, n1, iters):
+        """``sinkhorn`` on scores [b,cap0,cap1] with per-item counts -> z [b,cap0+1,cap1+1] (zero outside an item's block)."""
+        sc, alpha, dev, (b, cap0, cap1) = self._scores(scores, bin_score)
+        ws = self.ragged_workspace(b, cap0, cap1, dev)
+        z = torch.zeros(b, cap0 + 1, cap1 + 1, device=dev, dtype=torch.float32)
+        self.call("sg_sinkhorn_ragged", dev, sc, alpha, b, cap0, cap1, _host_i32(n0, b, 1, "n0"), _host_i32(n1, b, 1, "n1"),
+                  int(iters), z, ws, ws.numel())
+        return z
+
     def match_tail(self, z, match_threshold):
-        dev = z.device
-        zz = _check(z, "z", dev)
+        zz = _gpu(z, "z")
         b, n0, n1 = zz.shape[0], zz.shape[1] - 1, zz.shape[2] - 1
-        ws = self.workspace(b, n0, n1, dev)
-        m0, m1, s0, s1 = self.outputs(b, n0, n1, dev)
-        _native_sg.check(self.lib.sg_match_tail(zz.data_ptr(), b, n0, n1, float(match_threshold), m0.data_ptr(), m1.data_ptr(),
-                                                s0.data_ptr(), s1.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev)),
-                         "sg_match_tail")
-        return m0, m1, s0, s1
+        ws = self.workspace(b, n0, n1, zz.device)
+        out = self.outputs(b, n0, n1, zz.device)
+        self.call("sg_match_tail", zz.device, zz, b, n0, n1, float(match_threshold), *out, ws, ws.numel())
+        return out
+
+    def match_tail_ragged(self, z, n0, n1, match_threshold):
+        zz = _gpu(z, "z")
+        b, cap0, cap1 = zz.shape[0], zz.shape[1] - 1, zz.shape[2] - 1
+        ws = self.ragged_workspace(b, cap0, cap1, zz.device)
+        out = self.outputs(b, cap0, cap1, zz.device)
+        self.call("sg_match_tail_ragged", zz.device, zz, b, cap0, cap1, _host_i32(n0, b, 1, "n0"), _host_i32(n1, b, 1, "n1"),
+                  float(match_threshold), *out, ws, ws.numel())
+        return out
 
 
 class SuperGlue(nn.Module):
@@ -385,8 +354,7 @@ class SuperGlue(nn.Module):
                 "matching_scores1": kpts1.new_zeros(shape1),
             }
         if not kpts0.is_cuda:
-            raise RuntimeError(f"onepose_amd.SuperGlue runs only on a ROCm GPU (the inputs are on {kpts0.device}); "
-                               "there is no CPU fallback")
+            raise RuntimeError(NO_CPU.format("the inputs are", kpts0.device))
         hw0, hw1 = data["image0"].shape[-2:], data["image1"].shape[-2:]
         m0, m1, s0, s1 = self.engine.forward(kpts0, data["scores0"], data["descriptors0"], kpts1, data["scores1"],
                                              data["descriptors1"], hw0, hw1)
@@ -409,8 +377,7 @@ class SuperGlue(nn.Module):
             if data["keypoints0"].shape[1] == 0 or data["keypoints1"].shape[1] == 0:
                 results[i] = self.forward(data)
             elif not data["keypoints0"].is_cuda:
-                raise RuntimeError(f"onepose_amd.SuperGlue runs only on a ROCm GPU (item {i} is on {data['keypoints0'].device}); "
-                                   "there is no CPU fallback")
+                raise RuntimeError(NO_CPU.format(f"item {i} is", data["keypoints0"].device))
             else:
                 live.append(i)
         for chunk in ragged_chunks(live, max_items):

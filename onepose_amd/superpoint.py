@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from . import _native_spp
-from ._binding import PackedWeights, WorkspaceCache, on_device, stream_handle
+from ._binding import Engine, gpu_tensor
 
 LAYERS = (  # (name, out, in, k) -- reference :115-133
     ("conv1a", 64, 1, 3), ("conv1b", 64, 64, 3), ("conv2a", 64, 64, 3), ("conv2b", 64, 64, 3),
@@ -25,50 +25,40 @@ LAYERS = (  # (name, out, in, k) -- reference :115-133
 )
 
 
-class SuperPointEngine:
-    """Owns the packed weights and workspaces of one module on one device; workspaces are cached per (shape, device,
-    stream), so one module can be used from several streams at once."""
+NO_CPU = "onepose_amd.SuperPoint runs only on a ROCm GPU ({} is on {}); there is no CPU fallback"
 
-    def __init__(self, module):
-        self.module = module
-        self.lib = _native_spp.load()
-        self._packed = PackedWeights("onepose_amd.SuperPoint runs only on a ROCm GPU (a parameter is on {}); "
-                                     "there is no CPU fallback -- move the module to the GPU")
-        self._workspaces = WorkspaceCache(6)
 
-    def _params(self):
+class SuperPointEngine(Engine):
+    """The packed weights and the workspaces (keyed (b, H, W), device; per stream, so one module can be used from several
+    streams at once) of one module."""
+
+    native = _native_spp
+    WORKSPACE_BYTES, LAST_ERROR = "spp_workspace_bytes", "spp_last_error"
+    PARAMETER_REFUSAL = NO_CPU.format("a parameter", "{}") + " -- move the module to the GPU"
+
+    def _raw_tensors(self):
         m = self.module
         return [getattr(m, n).weight for n, *_ in LAYERS] + [getattr(m, n).bias for n, *_ in LAYERS]
-
-    def packed_weights(self, device):
-        return self._packed.get(device, self._params(), self._pack)
 
     def _pack(self, keep):
         raw = _native_spp.RawWeights()
         for i in range(_native_spp.NUM_LAYERS):
             raw.weight[i], raw.bias[i] = keep[i].data_ptr(), keep[_native_spp.NUM_LAYERS + i].data_ptr()
         packed = torch.empty(self.lib.spp_packed_weights_bytes() // 4, device=keep[0].device, dtype=torch.float32)
-        _native_spp.check(self.lib.spp_pack_weights(ctypes.byref(raw), packed.data_ptr(), stream_handle(packed.device)),
-                          "spp_pack_weights")
+        self.call("spp_pack_weights", packed.device, ctypes.byref(raw), packed)
         return packed
-
-    def workspace(self, b, h, w, device):
-        return self._workspaces.get((b, h, w), device, self.lib.spp_workspace_bytes,
-                                    lambda: "spp_workspace_bytes: " + self.lib.spp_last_error().decode())
 
     def flags(self):
         return _native_spp.PRECISIONS[self.module.precision]
 
     # ---- stages (tests) ----
-    @on_device
     def dense(self, image):
         b, _, h, w = image.shape
         dev = image.device
         ws = self.workspace(b, h, w, dev)
         score = torch.empty(b, h // 8 * 8, w // 8 * 8, device=dev, dtype=torch.float32)
         dense = torch.empty(b, 256, h // 8, w // 8, device=dev, dtype=torch.float32)
-        _native_spp.check(self.lib.spp_dense(self.packed_weights(dev).data_ptr(), image.data_ptr(), b, h, w, score.data_ptr(),
-                                             dense.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev), self.flags()), "spp_dense")
+        self.call("spp_dense", dev, self.packed_weights(dev), image, b, h, w, score, dense, ws, ws.numel(), self.flags())
         return score, dense
 
     def _outputs(self, b, capacity, dev):
@@ -84,7 +74,6 @@ class SuperPointEngine:
         # -1 = keep everything: NMS survivors are more than `radius` apart (plateaus aside); retried at H*W on overflow
         return mk if mk >= 0 else max(1024, (h * w) // ((cfg["nms_radius"] + 1) ** 2))
 
-    @on_device
     def detect(self, score, dense, cfg, align_corners, capacity=None, return_nms=False):
         b, h, w = score.shape
         dev = score.device
@@ -92,23 +81,18 @@ class SuperPointEngine:
         cap = self._capacity(cfg, h, w, capacity)
         kp, sc, de, cnt = self._outputs(b, cap, dev)
         nms = torch.empty_like(score) if return_nms else None
-        _native_spp.check(self.lib.spp_detect(
-            score.data_ptr(), dense.data_ptr(), b, h, w, cfg["nms_radius"], cfg["keypoint_threshold"], cfg["max_keypoints"],
-            cfg["remove_borders"], int(align_corners), cap, kp.data_ptr(), sc.data_ptr(), de.data_ptr(), cnt.data_ptr(),
-            nms.data_ptr() if return_nms else None, ws.data_ptr(), ws.numel(), stream_handle(dev)), "spp_detect")
+        self.call("spp_detect", dev, score, dense, b, h, w, cfg["nms_radius"], cfg["keypoint_threshold"], cfg["max_keypoints"],
+                  cfg["remove_borders"], int(align_corners), cap, kp, sc, de, cnt, nms, ws, ws.numel())
         return kp, sc, de, cnt, nms
 
-    @on_device
     def forward(self, image, cfg, align_corners, capacity=None):
         b, _, h, w = image.shape
         dev = image.device
         ws = self.workspace(b, h, w, dev)
         cap = self._capacity(cfg, h, w, capacity)
         kp, sc, de, cnt = self._outputs(b, cap, dev)
-        _native_spp.check(self.lib.spp_forward(
-            self.packed_weights(dev).data_ptr(), image.data_ptr(), b, h, w, cfg["nms_radius"], cfg["keypoint_threshold"],
-            cfg["max_keypoints"], cfg["remove_borders"], int(align_corners), cap, kp.data_ptr(), sc.data_ptr(), de.data_ptr(),
-            cnt.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(dev), self.flags()), "spp_forward")
+        self.call("spp_forward", dev, self.packed_weights(dev), image, b, h, w, cfg["nms_radius"], cfg["keypoint_threshold"],
+                  cfg["max_keypoints"], cfg["remove_borders"], int(align_corners), cap, kp, sc, de, cnt, ws, ws.numel(), self.flags())
         return kp, sc, de, cnt
 
 
@@ -165,10 +149,7 @@ class SuperPoint(nn.Module):
     def _check_image(self, inp):
         if not isinstance(inp, torch.Tensor) or inp.dim() != 4 or inp.shape[1] != 1:
             raise ValueError("expected a grayscale image batch [b, 1, H, W]")
-        if not inp.is_cuda:
-            raise RuntimeError(f"onepose_amd.SuperPoint runs only on a ROCm GPU (the image is on {inp.device}); "
-                               "there is no CPU fallback")
-        return inp.to(torch.float32).contiguous()
+        return gpu_tensor(inp, torch.float32, NO_CPU.format("the image", "{}"))
 
     @torch.no_grad()
     def forward_device(self, inp, capacity=None):
