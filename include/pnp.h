@@ -57,6 +57,18 @@ int pnp_ransac_epnp_matches(const float* kpts2d, const float* kpts3d, const int6
 int pnp_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, double* pose,
              void* workspace, size_t workspace_bytes, pnp_stream_t stream);
 
+/* Stages of pnp_ransac_epnp, for tests.  hyp: [iterations][12] doubles (device), row-major [R | t] in SCALED units,
+ * twelve NaNs where EPnP found no finite pose. */
+int pnp_hypotheses(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n,
+                   int iterations, uint64_t seed, double* hyp, pnp_stream_t stream);
+/* counts [iterations] int32 (device): the number of correspondences within reproj_error of each hypothesis */
+int pnp_score_hypotheses(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n,
+                         double reproj_error, const double* hyp, int iterations, int32_t* counts, pnp_stream_t stream);
+/* inlier_idx [n] int32: the ordered inlier list (first info[1] entries); info as in pnp_ransac_epnp */
+int pnp_select_best(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n,
+                    double reproj_error, const double* hyp, const int32_t* counts, int iterations,
+                    int32_t* inlier_mask, int32_t* inlier_idx, int32_t* info, pnp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

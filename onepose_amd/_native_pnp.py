@@ -16,6 +16,10 @@ SYMBOLS = {
     "pnp_ransac_epnp": (c_int, [F32, F32, _K, c_double, c_int, c_double, c_int, c_uint64] + _OUT),
     "pnp_ransac_epnp_matches": (c_int, [F32, F32, I64, c_int, _K, c_double, c_double, c_int, c_uint64] + _OUT),
     "pnp_epnp": (c_int, [F32, F32, _K, c_double, c_int, F64, RAW, c_size_t, STREAM]),
+    # the stages of pnp_ransac_epnp on caller-provided buffers (stage tests)
+    "pnp_hypotheses": (c_int, [F32, F32, _K, c_double, c_int, c_int, c_uint64, F64, STREAM]),
+    "pnp_score_hypotheses": (c_int, [F32, F32, _K, c_double, c_int, c_double, F64, c_int, I32, STREAM]),
+    "pnp_select_best": (c_int, [F32, F32, _K, c_double, c_int, c_double, F64, I32, c_int, I32, I32, I32, STREAM]),
 }
 
 _lib = None

@@ -178,6 +178,35 @@ __device__ __forceinline__ void procrustes_rotation(const double (&M)[3][3], dou
         U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
         U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
     }
+    // U = M V / sigma is orthonormal only to about eps (sigma_0 / sigma_k)^2: a minimal set with an outlier in it makes M
+    // ill-conditioned and R was a rotation to no better than 1e-7.  Where the Gram matrix of U is off by more than 1e-13,
+    // rebuild the frame from its best-conditioned column on (Gram-Schmidt, twice; third column = cross product with the
+    // orientation it had).  A well-conditioned U -- every all-inlier sample, the refit -- is left as it is.
+    double dev = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b)
+            dev = fmax(dev, fabs(U[0][a] * U[0][b] + U[1][a] * U[1][b] + U[2][a] * U[2][b] - (a == b ? 1.0 : 0.0)));
+    if (!(dev <= 1e-13)) {                                     // also taken for a NaN, which stays one
+        const double n0 = sqrt(U[0][0] * U[0][0] + U[1][0] * U[1][0] + U[2][0] * U[2][0]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) U[i][0] /= n0;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            const double d = U[0][0] * U[0][1] + U[1][0] * U[1][1] + U[2][0] * U[2][1];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) U[i][1] -= d * U[i][0];
+            const double n1 = sqrt(U[0][1] * U[0][1] + U[1][1] * U[1][1] + U[2][1] * U[2][1]);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) U[i][1] /= n1;
+        }
+        const double w[3] = {U[1][0] * U[2][1] - U[2][0] * U[1][1], U[2][0] * U[0][1] - U[0][0] * U[2][1],
+                             U[0][0] * U[1][1] - U[1][0] * U[0][1]};
+        const double sgn = w[0] * U[0][2] + w[1] * U[1][2] + w[2] * U[2][2] < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) U[i][2] = sgn * w[i];
+    }
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -718,6 +747,42 @@ int pnp_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, dou
     hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n, scale,
                        cam_of(K_host), (const int*)nullptr, (int32_t*)nullptr, pose);
     return check_launch(-1, "pnp_epnp");
+}
+
+// ---- the stages of pnp_ransac_epnp on caller-provided buffers (stage tests): the same kernels, the same launch shapes ----
+int pnp_hypotheses(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, int iterations,
+                   uint64_t seed, double* hyp, pnp_stream_t stream) {
+    if (!pts_3d || !pts_2d || !K_host || !hyp) return fail(-1, "null argument");
+    if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
+    if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
+    if (!(scale > 0.0)) return fail(-1, "scale must be positive");
+    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n,
+                       (const int*)nullptr, scale, cam_of(K_host), (unsigned long long)seed, iterations, hyp);
+    return check_launch(-1, "pnp_hypotheses");
+}
+
+int pnp_score_hypotheses(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, double reproj_error,
+                         const double* hyp, int iterations, int32_t* counts, pnp_stream_t stream) {
+    if (!pts_3d || !pts_2d || !K_host || !hyp || !counts) return fail(-1, "null argument");
+    if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
+    if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
+    if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
+    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n,
+                       (const int*)nullptr, scale, cam_of(K_host), reproj_error * reproj_error, iterations, hyp, counts);
+    return check_launch(-1, "pnp_score_hypotheses");
+}
+
+int pnp_select_best(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, double reproj_error,
+                    const double* hyp, const int32_t* counts, int iterations, int32_t* inlier_mask, int32_t* inlier_idx,
+                    int32_t* info, pnp_stream_t stream) {
+    if (!pts_3d || !pts_2d || !K_host || !hyp || !counts || !inlier_mask || !inlier_idx || !info) return fail(-1, "null argument");
+    if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
+    if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
+    if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
+    hipLaunchKernelGGL(best_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n, (const int*)nullptr,
+                       scale, cam_of(K_host), reproj_error * reproj_error, iterations, hyp, counts, (const int*)nullptr, inlier_mask,
+                       inlier_idx, info);
+    return check_launch(-1, "pnp_select_best");
 }
 
 }  // extern "C"
