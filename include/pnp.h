@@ -72,4 +72,6 @@ int pnp_select_best(const float* pts_3d, const float* pts_2d, const double* K_ho
 #ifdef __cplusplus
 }
 #endif
+
+#include "pnp_batch.h" /* the same solves for a batch of frames in one chain of launches (pnp_version() >= 2) */
 #endif

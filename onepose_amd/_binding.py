@@ -2,6 +2,7 @@
 
 A binding's ``SYMBOLS`` table mirrors its header: scalars and HOST pointers are ctypes types, a DEVICE pointer is the marker
 of its element type (``F32`` ``F64`` ``I32`` ``I64`` ``U8``; ``RAW`` for ``void*`` memory) and the stream slot is ``STREAM``.
+A library whose ABI spans a second header lists that header's symbols in ``MORE_SYMBOLS``, bound alike.
 ``bind()`` lowers the markers to ``c_void_p``, so a raw ``lib.fn(int, ...)`` call (bench.py, tools/, the tests) is plain ctypes;
 the front ends go through ``call(name, device, *tensors and scalars)``, which makes ``device`` current, fills the stream slot,
 refuses a tensor of the wrong device / dtype / layout before the library is entered and turns a return code into
@@ -96,7 +97,7 @@ def bind(ns, what, prefix, fallback="PyTorch"):
                 f"(run `python -m onepose_amd.build_ext`; needs hipcc).  There is no CPU / {fallback} fallback.")
         lib = ctypes.CDLL(path)
         bound = {}          # name -> (ctypes function, Signature) of THIS library
-        for name, (restype, argtypes) in ns["SYMBOLS"].items():
+        for name, (restype, argtypes) in {**ns["SYMBOLS"], **ns.get("MORE_SYMBOLS", {})}.items():   # MORE_SYMBOLS: of a second header
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = restype
             fn.argtypes = [ctypes.c_void_p if isinstance(t, DevicePointer) else t for t in argtypes]

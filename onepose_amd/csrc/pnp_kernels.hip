@@ -1,6 +1,8 @@
-// RANSAC-EPnP pose solver (C ABI: include/pnp.h; reference call site: src/utils/eval_utils.py:18-42).
+// RANSAC-EPnP pose solver (C ABI: include/pnp.h with include/pnp_batch.h; reference call site: src/utils/eval_utils.py:18-42).
 //
-// fp64 throughout, like the reference's float64 cv2 call.  Latency-bound small dense algebra, not MFMA work:
+// fp64 throughout, like the reference's float64 cv2 call.  Latency-bound small dense algebra, not MFMA work.  Every kernel takes
+// the frame from blockIdx.y: one chain of launches answers a batch of frames (pnp_ransac_epnp_batch), and the single-frame entry
+// points launch a batch of one.  Per frame:
 //   hyp_kernel    one thread per hypothesis: hash-sampled minimal set of 5 (sampling::distinct) -> EPnP -> [R | t]
 //   score_kernel  one wave per hypothesis: squared reprojection error of every correspondence, ballot count
 //   best_kernel   one workgroup: first arg-max of the inlier counts, inlier mask + ordered index list of the best model
@@ -490,13 +492,40 @@ __device__ __forceinline__ bool epnp_solve(int n_rt, Get get, const Cam& cam, do
 }
 
 // ---- kernels --------------------------------------------------------------------------------------------------
-// n_dev != nullptr: the number of correspondences is only known on the device (gather_matches_kernel)
-__global__ __launch_bounds__(64) void hyp_kernel(const float* __restrict__ p3, const float* __restrict__ p2, int n_host,
-                                                 const int* __restrict__ n_dev, double scale, Cam cam, unsigned long long seed,
-                                                 int iterations, double* __restrict__ hyp) {
-    const int h = blockIdx.x * 64 + threadIdx.x;
+// Every kernel serves a batch of frames, the frame being blockIdx.y; the single-frame entry points launch a batch of one, so a
+// frame runs the same machine code alone and in a batch.  What differs from frame to frame travels BY VALUE in the kernel
+// arguments (1.6 KB of the 4 KB there are); a frame's arrays are found by frame index x a stride that the shape alone fixes.
+struct Frame {
+    Cam cam;
+    unsigned long long seed;
+    int n;                                 // correspondences (query keypoints for gather_matches_kernel) of the frame
+};
+struct Batch {                             // the shape first, then the frames: a batch of one reads what it needs from the first 80 bytes
+    size_t p3_stride, p2_stride;           // bytes from one frame's correspondences to the next frame's
+    size_t ws_stride;                      // bytes from one frame's workspace slice to the next frame's
+    int cap;                               // length of a frame's inlier-mask row: entries past n are written as 0
+    Frame frame[PNP_MAX_ITEMS];
+};
+static_assert(sizeof(Batch) + 16 * sizeof(void*) + 64 <= 4096, "Batch must fit the kernel arguments");
+
+template <class T>
+__device__ __forceinline__ T* frame_of(T* p, size_t stride_bytes, int frame) {
+    using Byte = std::conditional_t<std::is_const_v<T>, const char, char>;
+    return p ? reinterpret_cast<T*>(reinterpret_cast<Byte*>(p) + stride_bytes * (size_t)frame) : nullptr;
+}
+
+// n_dev != nullptr: the number of correspondences is only known on the device (gather_matches_kernel; a workspace piece)
+__global__ __launch_bounds__(64) void hyp_kernel(const float* __restrict__ p3_all, const float* __restrict__ p2_all,
+                                                 const int* __restrict__ n_dev, double scale, Batch f, int iterations,
+                                                 double* __restrict__ hyp_all) {
+    const int h = blockIdx.x * 64 + threadIdx.x, frame = blockIdx.y;
     if (h >= iterations) return;
-    const int n = n_dev ? *n_dev : n_host;
+    const float* __restrict__ p3 = frame_of(p3_all, f.p3_stride, frame);
+    const float* __restrict__ p2 = frame_of(p2_all, f.p2_stride, frame);
+    double* __restrict__ hyp = frame_of(hyp_all, f.ws_stride, frame);
+    const Cam cam = f.frame[frame].cam;
+    const unsigned long long seed = f.frame[frame].seed;
+    const int n = n_dev ? *frame_of(n_dev, f.ws_stride, frame) : f.frame[frame].n;
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
     if (n < MODEL_POINTS) {                                  // too few matches: no model (eval_utils.py:40-42)
         for (int k = 0; k < 12; ++k) hyp[(size_t)h * 12 + k] = nan;
@@ -533,12 +562,17 @@ __device__ __forceinline__ bool is_inlier(const double* __restrict__ P, const fl
     return du * du + dv * dv <= thr2;      // false for NaN poses / points at infinity
 }
 
-__global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ p3, const float* __restrict__ p2, int n_host,
-                                                    const int* __restrict__ n_dev, double scale, Cam cam, double thr2, int iterations,
-                                                    const double* __restrict__ hyp, int* __restrict__ counts) {
-    const int h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+__global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ p3_all, const float* __restrict__ p2_all,
+                                                    const int* __restrict__ n_dev, double scale, Batch f, double thr2, int iterations,
+                                                    const double* __restrict__ hyp_all, int* __restrict__ counts_all) {
+    const int h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, frame = blockIdx.y;
     if (h >= iterations) return;
-    const int n = n_dev ? *n_dev : n_host;
+    const float* __restrict__ p3 = frame_of(p3_all, f.p3_stride, frame);
+    const float* __restrict__ p2 = frame_of(p2_all, f.p2_stride, frame);
+    const double* __restrict__ hyp = frame_of(hyp_all, f.ws_stride, frame);
+    int* __restrict__ counts = frame_of(counts_all, f.ws_stride, frame);
+    const Cam cam = f.frame[frame].cam;
+    const int n = n_dev ? *frame_of(n_dev, f.ws_stride, frame) : f.frame[frame].n;
     double P[12];
     for (int k = 0; k < 12; ++k) P[k] = hyp[(size_t)h * 12 + k];
     int cnt = 0;
@@ -551,15 +585,24 @@ __global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ p3
 }
 
 // src != nullptr: correspondence i came from query keypoint src[i]; the inlier mask is indexed by query keypoint
-// (pre-zeroed by gather_matches_kernel)
-__global__ __launch_bounds__(1024) void best_kernel(const float* __restrict__ p3, const float* __restrict__ p2, int n_host,
-                                                    const int* __restrict__ n_dev, double scale, Cam cam, double thr2, int iterations,
-                                                    const double* __restrict__ hyp, const int* __restrict__ counts,
-                                                    const int* __restrict__ src, int32_t* __restrict__ mask,
-                                                    int* __restrict__ inl_idx, int32_t* __restrict__ info) {
+// (pre-zeroed by gather_matches_kernel, its padding included).  src == nullptr: the mask's padding n .. cap is zeroed here.
+__global__ __launch_bounds__(1024) void best_kernel(const float* __restrict__ p3_all, const float* __restrict__ p2_all,
+                                                    const int* __restrict__ n_dev, double scale, Batch f, double thr2, int iterations,
+                                                    const double* __restrict__ hyp_all, const int* __restrict__ counts_all,
+                                                    const int* __restrict__ src_all, int32_t* __restrict__ mask_all,
+                                                    int* __restrict__ inl_all, int32_t* __restrict__ info_all) {
     __shared__ int sc[1024], si[1024], wsum[16];
-    const int tid = threadIdx.x;
-    const int n = n_dev ? *n_dev : n_host;
+    const int tid = threadIdx.x, frame = blockIdx.y;
+    const float* __restrict__ p3 = frame_of(p3_all, f.p3_stride, frame);
+    const float* __restrict__ p2 = frame_of(p2_all, f.p2_stride, frame);
+    const double* __restrict__ hyp = frame_of(hyp_all, f.ws_stride, frame);
+    const int* __restrict__ counts = frame_of(counts_all, f.ws_stride, frame);
+    const int* __restrict__ src = frame_of(src_all, f.ws_stride, frame);
+    int* __restrict__ inl_idx = frame_of(inl_all, f.ws_stride, frame);
+    int32_t* __restrict__ mask = mask_all + (size_t)frame * f.cap;
+    int32_t* __restrict__ info = info_all + (size_t)frame * 4;
+    const Cam cam = f.frame[frame].cam;
+    const int n = n_dev ? *frame_of(n_dev, f.ws_stride, frame) : f.frame[frame].n;
     int bc = -1, bi = 0x7FFFFFFF;
     for (int h = tid; h < iterations; h += 1024) {
         const int c = counts[h];
@@ -587,19 +630,32 @@ __global__ __launch_bounds__(1024) void best_kernel(const float* __restrict__ p3
         if (in) inl_idx[run + pos] = i;
         run += tot;
     }
+    if (!src)
+        for (int i = n + tid; i < f.cap; i += 1024) mask[i] = 0;
     if (tid == 0) {
         info[0] = ok; info[1] = ok ? run : 0; info[2] = ok ? best : -1; info[3] = bcount < 0 ? 0 : bcount;
     }
 }
 
 // inference.py:148-152 on the device: valid = matches0 > -1; mkpts2d = kpts2d[valid]; mkpts3d = kpts3d[matches0[valid]] --
-// ordered compaction by one workgroup; also zeroes the per-keypoint inlier mask
-__global__ __launch_bounds__(1024) void gather_matches_kernel(const float* __restrict__ kpts2d, const float* __restrict__ kpts3d,
-                                                              const long long* __restrict__ matches0, int n1, float* __restrict__ p2,
-                                                              float* __restrict__ p3, int* __restrict__ src, int* __restrict__ count,
-                                                              int32_t* __restrict__ mask) {
+// ordered compaction by one workgroup per frame; also zeroes the per-keypoint inlier mask (all f.cap entries of the row).
+// Rows of f.cap query keypoints per frame; k3_stride: floats from one frame's database points to the next frame's (0: shared).
+__global__ __launch_bounds__(1024) void gather_matches_kernel(const float* __restrict__ kpts2d_all, const float* __restrict__ kpts3d_all,
+                                                              const long long* __restrict__ matches0_all, Batch f, size_t k3_stride,
+                                                              float* __restrict__ p2_all, float* __restrict__ p3_all,
+                                                              int* __restrict__ src_all, int* __restrict__ count_all,
+                                                              int32_t* __restrict__ mask_all) {
     __shared__ int wsum[16];
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, frame = blockIdx.y;
+    const int n1 = f.frame[frame].n;
+    const float* __restrict__ kpts2d = kpts2d_all + (size_t)frame * f.cap * 2;
+    const float* __restrict__ kpts3d = kpts3d_all + (size_t)frame * k3_stride;
+    const long long* __restrict__ matches0 = matches0_all + (size_t)frame * f.cap;
+    float* __restrict__ p2 = frame_of(p2_all, f.ws_stride, frame);
+    float* __restrict__ p3 = frame_of(p3_all, f.ws_stride, frame);
+    int* __restrict__ src = frame_of(src_all, f.ws_stride, frame);
+    int* __restrict__ count = frame_of(count_all, f.ws_stride, frame);
+    int32_t* __restrict__ mask = mask_all + (size_t)frame * f.cap;
     int run = 0;
     for (int i0 = 0; i0 < n1; i0 += 1024) {
         const int i = i0 + tid;
@@ -617,16 +673,23 @@ __global__ __launch_bounds__(1024) void gather_matches_kernel(const float* __res
         }
         run += tot;
     }
+    for (int i = n1 + tid; i < f.cap; i += 1024) mask[i] = 0;
     if (tid == 0) *count = run;
 }
 
-// EPnP over the listed correspondences (idx == nullptr: all n); info != nullptr: RANSAC refit (count from info[1])
-__global__ __launch_bounds__(64) void refit_kernel(const float* __restrict__ p3, const float* __restrict__ p2, int n_all, double scale,
-                                                   Cam cam, const int* __restrict__ idx, int32_t* __restrict__ info,
-                                                   double* __restrict__ pose) {
-    const int lane = threadIdx.x;
+// EPnP over the listed correspondences (idx == nullptr: all f.frame[frame].n); info != nullptr: RANSAC refit (count from info[1])
+__global__ __launch_bounds__(64) void refit_kernel(const float* __restrict__ p3_all, const float* __restrict__ p2_all, double scale,
+                                                   Batch f, const int* __restrict__ idx_all, int32_t* __restrict__ info_all,
+                                                   double* __restrict__ pose_all) {
+    const int lane = threadIdx.x, frame = blockIdx.y;
+    const float* __restrict__ p3 = frame_of(p3_all, f.p3_stride, frame);
+    const float* __restrict__ p2 = frame_of(p2_all, f.p2_stride, frame);
+    const int* __restrict__ idx = frame_of(idx_all, f.ws_stride, frame);
+    int32_t* __restrict__ info = info_all ? info_all + (size_t)frame * 4 : nullptr;
+    double* __restrict__ pose = pose_all + (size_t)frame * 12;
+    const Cam cam = f.frame[frame].cam;
     bool ok = true;
-    int n = n_all;
+    int n = f.frame[frame].n;
     if (info) { ok = info[0] != 0; n = info[1]; }
     double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
     if (ok && n >= 4) {
@@ -652,6 +715,8 @@ __global__ __launch_bounds__(64) void refit_kernel(const float* __restrict__ p3,
     }
 }
 
+// One frame's slice of the workspace.  The batched entry points lay b slices of (cap, iterations) end to end: a slice's
+// size, and so every frame's addresses, depend on the shape alone.
 struct Workspace {
     double* hyp;
     int *counts, *inl, *src, *count;
@@ -679,16 +744,74 @@ using namespace capi;
 
 namespace {
 Cam cam_of(const double* K) { return Cam{K[0], K[4], K[2], K[5]}; }
+
+// the batch of one frame the single-frame entry points launch
+Batch one_frame(const double* K, int n, uint64_t seed) {
+    Batch f = {};
+    f.frame[0] = Frame{cam_of(K), seed, n};
+    f.cap = n;
+    return f;
+}
+
+// hypotheses -> scores -> selection -> refit of every frame of f, over correspondences p3 / p2 (n_dev: their counts, when only
+// the device knows them; src: the query keypoint of each, for the mask)
+void launch_solve(const float* p3, const float* p2, const int* n_dev, const int* src, const Batch& f, int b, double scale,
+                  double thr2, int iterations, const Workspace& w, double* pose, int32_t* mask, int32_t* info, hipStream_t s) {
+    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64, b), dim3(64), 0, s, p3, p2, n_dev, scale, f, iterations, w.hyp);
+    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4, b), dim3(256), 0, s, p3, p2, n_dev, scale, f, thr2, iterations, w.hyp,
+                       w.counts);
+    hipLaunchKernelGGL(best_kernel, dim3(1, b), dim3(1024), 0, s, p3, p2, n_dev, scale, f, thr2, iterations, w.hyp, w.counts, src, mask,
+                       w.inl, info);
+    hipLaunchKernelGGL(refit_kernel, dim3(1, b), dim3(64), 0, s, p3, p2, scale, f, (const int*)w.inl, info, pose);
+}
+
+// what the two batched entry points check alike; 0 or the code to return
+int check_batch(const double* K_host, const int32_t* n, const uint64_t* seeds, int b, int cap, double scale, double reproj_error,
+                int iterations, const void* pose, const void* inlier_mask, const void* info, const char* cap_name) {
+    if (b < 1 || b > PNP_MAX_ITEMS) return fail(-1, "b must be in [1, %d] (got %d)", PNP_MAX_ITEMS, b);
+    if (cap < 1) return fail(-1, "%s must be >= 1 (got %d)", cap_name, cap);
+    if (!K_host || !n || !seeds || !pose || !inlier_mask || !info) return fail(-1, "null argument");
+    for (int i = 0; i < b; ++i)
+        if (n[i] < 0 || n[i] > cap) return fail(-1, "frame %d: n = %d is outside [0, %s = %d]", i, n[i], cap_name, cap);
+    if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
+    if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
+    return 0;
+}
+
+int check_batch_workspace(const void* workspace, size_t workspace_bytes, int b, int cap, int iterations) {
+    if (!workspace) return fail(-1, "workspace is null");
+    const size_t need = (size_t)b * carve(nullptr, cap, iterations).bytes;
+    if (workspace_bytes < need) return fail(-2, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    return 0;
+}
+
+Batch batch_of(const double* K_host, const int32_t* n, const uint64_t* seeds, int b, int cap, size_t ws_stride) {
+    Batch f = {};
+    for (int i = 0; i < b; ++i) {
+        f.frame[i] = Frame{cam_of(K_host + 9 * i), (unsigned long long)seeds[i], n[i]};
+    }
+    f.cap = cap;
+    f.ws_stride = ws_stride;
+    return f;
+}
 }  // namespace
 
 extern "C" {
 
-int pnp_version(void) { return 1; }
+int pnp_version(void) { return 2; }
 const char* pnp_last_error(void) { return g_err; }
 
 size_t pnp_workspace_bytes(int n, int iterations) {
     if (n < 1 || iterations < 1) { fail(-1, "n and iterations must be >= 1"); return 0; }
     return carve(nullptr, n, iterations).bytes;
+}
+
+size_t pnp_batch_workspace_bytes(int b, int cap, int iterations) {
+    if (b < 1 || b > PNP_MAX_ITEMS || cap < 1 || iterations < 1 || iterations > (1 << 24)) {
+        fail(-1, "b must be in [1, %d], cap >= 1 and iterations in [1, 2^24]", PNP_MAX_ITEMS);
+        return 0;
+    }
+    return (size_t)b * carve(nullptr, cap, iterations).bytes;
 }
 
 int pnp_ransac_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, double reproj_error,
@@ -700,18 +823,24 @@ int pnp_ransac_epnp(const float* pts_3d, const float* pts_2d, const double* K_ho
     if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
     Workspace w = carve(workspace, n, iterations);
     if (workspace_bytes < w.bytes) return fail(-1, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const Cam cam = cam_of(K_host);
-    const double thr2 = reproj_error * reproj_error;
-    const int* nd = nullptr;
-    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64), dim3(64), 0, s, pts_3d, pts_2d, n, nd, scale, cam,
-                       (unsigned long long)seed, iterations, w.hyp);
-    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4), dim3(256), 0, s, pts_3d, pts_2d, n, nd, scale, cam, thr2,
-                       iterations, w.hyp, w.counts);
-    hipLaunchKernelGGL(best_kernel, dim3(1), dim3(1024), 0, s, pts_3d, pts_2d, n, nd, scale, cam, thr2, iterations, w.hyp, w.counts,
-                       nd, inlier_mask, w.inl, info);
-    hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(64), 0, s, pts_3d, pts_2d, n, scale, cam, w.inl, info, pose);
+    launch_solve(pts_3d, pts_2d, nullptr, nullptr, one_frame(K_host, n, seed), 1, scale, reproj_error * reproj_error, iterations, w,
+                 pose, inlier_mask, info, reinterpret_cast<hipStream_t>(stream));
     return check_launch(-1, "pnp_ransac_epnp");
+}
+
+int pnp_ransac_epnp_batch(const float* pts_3d, const float* pts_2d, const double* K_host, const int32_t* n, const uint64_t* seeds,
+                          int b, int cap, double scale, double reproj_error, int iterations, double* pose, int32_t* inlier_mask,
+                          int32_t* info, void* workspace, size_t workspace_bytes, pnp_stream_t stream) {
+    if (const int rc = check_batch(K_host, n, seeds, b, cap, scale, reproj_error, iterations, pose, inlier_mask, info, "cap")) return rc;
+    if (!pts_3d || !pts_2d) return fail(-1, "null argument");
+    if (const int rc = check_batch_workspace(workspace, workspace_bytes, b, cap, iterations)) return rc;
+    Workspace w = carve(workspace, cap, iterations);
+    Batch f = batch_of(K_host, n, seeds, b, cap, w.bytes);
+    f.p3_stride = sizeof(float) * 3 * (size_t)cap;
+    f.p2_stride = sizeof(float) * 2 * (size_t)cap;
+    launch_solve(pts_3d, pts_2d, nullptr, nullptr, f, b, scale, reproj_error * reproj_error, iterations, w, pose, inlier_mask, info,
+                 reinterpret_cast<hipStream_t>(stream));
+    return check_launch(-1, "pnp_ransac_epnp_batch");
 }
 
 int pnp_ransac_epnp_matches(const float* kpts2d, const float* kpts3d, const int64_t* matches0, int n1, const double* K_host,
@@ -724,18 +853,30 @@ int pnp_ransac_epnp_matches(const float* kpts2d, const float* kpts3d, const int6
     Workspace w = carve(workspace, n1, iterations);
     if (workspace_bytes < w.bytes) return fail(-1, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const Cam cam = cam_of(K_host);
-    const double thr2 = reproj_error * reproj_error;
-    hipLaunchKernelGGL(gather_matches_kernel, dim3(1), dim3(1024), 0, s, kpts2d, kpts3d, reinterpret_cast<const long long*>(matches0),
-                       n1, w.p2, w.p3, w.src, w.count, inlier_mask);
-    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64), dim3(64), 0, s, w.p3, w.p2, 0, w.count, scale, cam,
-                       (unsigned long long)seed, iterations, w.hyp);
-    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4), dim3(256), 0, s, w.p3, w.p2, 0, w.count, scale, cam, thr2, iterations,
-                       w.hyp, w.counts);
-    hipLaunchKernelGGL(best_kernel, dim3(1), dim3(1024), 0, s, w.p3, w.p2, 0, w.count, scale, cam, thr2, iterations, w.hyp, w.counts,
-                       w.src, inlier_mask, w.inl, info);
-    hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(64), 0, s, w.p3, w.p2, 0, scale, cam, w.inl, info, pose);
+    const Batch f = one_frame(K_host, n1, seed);
+    hipLaunchKernelGGL(gather_matches_kernel, dim3(1, 1), dim3(1024), 0, s, kpts2d, kpts3d, reinterpret_cast<const long long*>(matches0),
+                       f, (size_t)0, w.p2, w.p3, w.src, w.count, inlier_mask);
+    launch_solve(w.p3, w.p2, w.count, w.src, f, 1, scale, reproj_error * reproj_error, iterations, w, pose, inlier_mask, info, s);
     return check_launch(-1, "pnp_ransac_epnp_matches");
+}
+
+int pnp_ransac_epnp_matches_batch(const float* kpts2d, const float* kpts3d, const int64_t* matches0, const double* K_host,
+                                  const int32_t* n1, const uint64_t* seeds, int b, int cap1, int n3, int shared3d, double scale,
+                                  double reproj_error, int iterations, double* pose, int32_t* inlier_mask, int32_t* info,
+                                  void* workspace, size_t workspace_bytes, pnp_stream_t stream) {
+    if (const int rc = check_batch(K_host, n1, seeds, b, cap1, scale, reproj_error, iterations, pose, inlier_mask, info, "cap1")) return rc;
+    if (!kpts2d || !kpts3d || !matches0) return fail(-1, "null argument");
+    if (n3 < 1) return fail(-1, "n3 must be >= 1 (got %d)", n3);
+    if (shared3d != 0 && shared3d != 1) return fail(-1, "shared3d must be 0 or 1 (got %d)", shared3d);
+    if (const int rc = check_batch_workspace(workspace, workspace_bytes, b, cap1, iterations)) return rc;
+    Workspace w = carve(workspace, cap1, iterations);
+    Batch f = batch_of(K_host, n1, seeds, b, cap1, w.bytes);
+    f.p3_stride = f.p2_stride = w.bytes;                  // the gathered correspondences are pieces of the workspace slices
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(gather_matches_kernel, dim3(1, b), dim3(1024), 0, s, kpts2d, kpts3d, reinterpret_cast<const long long*>(matches0),
+                       f, shared3d ? (size_t)0 : (size_t)3 * n3, w.p2, w.p3, w.src, w.count, inlier_mask);
+    launch_solve(w.p3, w.p2, w.count, w.src, f, b, scale, reproj_error * reproj_error, iterations, w, pose, inlier_mask, info, s);
+    return check_launch(-1, "pnp_ransac_epnp_matches_batch");
 }
 
 int pnp_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, double* pose, void* workspace,
@@ -744,8 +885,8 @@ int pnp_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, dou
     if (!pts_3d || !pts_2d || !K_host || !pose) return fail(-1, "null argument");
     if (n < 4) return fail(-1, "EPnP needs at least 4 correspondences (got %d)", n);
     if (!(scale > 0.0)) return fail(-1, "scale must be positive");
-    hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n, scale,
-                       cam_of(K_host), (const int*)nullptr, (int32_t*)nullptr, pose);
+    hipLaunchKernelGGL(refit_kernel, dim3(1, 1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, scale,
+                       one_frame(K_host, n, 0), (const int*)nullptr, (int32_t*)nullptr, pose);
     return check_launch(-1, "pnp_epnp");
 }
 
@@ -756,8 +897,8 @@ int pnp_hypotheses(const float* pts_3d, const float* pts_2d, const double* K_hos
     if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
     if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
     if (!(scale > 0.0)) return fail(-1, "scale must be positive");
-    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n,
-                       (const int*)nullptr, scale, cam_of(K_host), (unsigned long long)seed, iterations, hyp);
+    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64, 1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d,
+                       (const int*)nullptr, scale, one_frame(K_host, n, seed), iterations, hyp);
     return check_launch(-1, "pnp_hypotheses");
 }
 
@@ -767,8 +908,8 @@ int pnp_score_hypotheses(const float* pts_3d, const float* pts_2d, const double*
     if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
     if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
     if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
-    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n,
-                       (const int*)nullptr, scale, cam_of(K_host), reproj_error * reproj_error, iterations, hyp, counts);
+    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4, 1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d,
+                       (const int*)nullptr, scale, one_frame(K_host, n, 0), reproj_error * reproj_error, iterations, hyp, counts);
     return check_launch(-1, "pnp_score_hypotheses");
 }
 
@@ -779,9 +920,9 @@ int pnp_select_best(const float* pts_3d, const float* pts_2d, const double* K_ho
     if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
     if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
     if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
-    hipLaunchKernelGGL(best_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, n, (const int*)nullptr,
-                       scale, cam_of(K_host), reproj_error * reproj_error, iterations, hyp, counts, (const int*)nullptr, inlier_mask,
-                       inlier_idx, info);
+    hipLaunchKernelGGL(best_kernel, dim3(1, 1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, (const int*)nullptr,
+                       scale, one_frame(K_host, n, 0), reproj_error * reproj_error, iterations, hyp, counts, (const int*)nullptr,
+                       inlier_mask, inlier_idx, info);
     return check_launch(-1, "pnp_select_best");
 }
 

@@ -54,6 +54,39 @@ class FrameMatcher:
         return pose, mask, info, det
 
     @torch.no_grad()
+    def solve_poses_device(self, images, K_crops, scale=1000, seeds=0):
+        """A list (or [B,1,H,W] batch) of crops -> (poses [B,3,4] float64, masks [B,cap1] per query keypoint, infos [B,4],
+        detections), all left on the GPU.  Extractor and matcher run frame by frame exactly as in ``solve_pose_device`` (each frame
+        keeps its own keypoint count); their keypoints and matches go into padded [B, cap1] buffers, cap1 the largest count, and ONE
+        batched solve (``pnp_ransac_epnp_matches_batch``) answers all frames: frame i bitwise as ``solve_pose_device`` answers it with
+        ``K_crops[i]`` and ``seeds[i]``.  K_crops: [3,3] or B of them; seeds: an int or B ints."""
+        from . import pnp
+        frames = [images[i:i + 1] for i in range(images.shape[0])] if isinstance(images, torch.Tensor) else list(images)
+        if not frames:
+            raise ValueError("solve_poses_device needs at least one image")
+        dets, matches = [], []
+        for image in frames:
+            det = self.extractor(image)
+            kpts2d = det["keypoints"][0]
+            inp = {"keypoints2d": kpts2d[None], "keypoints3d": self.db["keypoints3d"],
+                   "descriptors2d_query": det["descriptors"][0][None].contiguous(), "descriptors3d_db": self.db["descriptors3d_db"],
+                   "descriptors2d_db": self.db["descriptors2d_db"]}
+            pred, _ = self.matcher(inp, database=self.db_cache) if self.db_cache is not None else self.matcher(inp)
+            dets.append(det)
+            matches.append(pred["matches0"].reshape(-1))
+        counts = [d["keypoints"][0].shape[0] for d in dets]
+        dev = dets[0]["keypoints"][0].device
+        cap1 = max(max(counts), 1)
+        kpts = torch.zeros(len(frames), cap1, 2, device=dev, dtype=torch.float32)
+        m0 = torch.full((len(frames), cap1), -1, device=dev, dtype=torch.int64)
+        for i, (det, m, n1) in enumerate(zip(dets, matches, counts)):
+            kpts[i, :n1] = det["keypoints"][0]
+            m0[i, :n1] = m
+        poses, masks, infos = pnp.ransac_pnp_from_matches_batch(K_crops, kpts, self.db["keypoints3d"][0], m0, counts=counts, scale=scale,
+                                                                seeds=seeds)
+        return poses, masks, infos, dets
+
+    @torch.no_grad()
     def solve_pose(self, image, K_crop, scale=1000, seed=0):
         """image -> (pose_pred [3,4], pose_pred_homo [4,4], inliers [m,1]) like inference.py:140-155; numpy outputs, identity
         when fewer than 5 matches survive or the solve fails (eval_utils.py:40-42)."""
