@@ -78,6 +78,9 @@ int spp_dense(const float* packed, const float* image, int b, int H, int W, floa
 
 /* Discrete stages (:163-195) from given dense tensors: NMS, threshold, border removal, top-k,
  * (h,w)->(x,y), descriptor normalisation + bilinear sampling + normalisation.
+ *   score_map      PRECONDITION: every score is >= 0 and none is NaN (a cell softmax gives nothing else).  The top-k is a radix
+ *                  selection on the fp32 bit patterns read as unsigned integers; for non-negative, NaN-free floats that order is
+ *                  the order of the values.  A negative score or a NaN would be ranked above every ordinary one.
  *   max_keypoints  >= 0: keep the k highest scores, ordered by descending score (ties: lower row-major
  *                  pixel index first -- torch.topk leaves tie order unspecified); -1: keep all, row-major order.
  *   capacity       slots per image in the outputs; with max_keypoints >= 0 it must be >= max_keypoints.

@@ -260,15 +260,20 @@ def test_bad_arguments_raise():
         mod(torch.zeros(1, 1, 64, 64).cuda())
 
 
+SMALL_SHAPES = [(1, 8, 8), (2, 8, 24), (1, 16, 512), (3, 40, 72), (1, 15, 9), (2, 67, 130), (1, 129, 66)]
+
+
 @pytest.mark.parametrize("precision", SPP_PRECISIONS)
-@pytest.mark.parametrize("b,h,w", [(1, 8, 8), (2, 8, 24), (1, 16, 512), (3, 40, 72), (1, 15, 9), (2, 67, 130), (1, 129, 66)])
-def test_small_and_skinny_images_vs_oracle(b, h, w, precision):
-    """Smallest legal image (one 8x8 cell), single-cell rows, very skinny planes, odd batch."""
+@pytest.mark.parametrize("b,h,w,align", [pytest.param(*s, True, id="-".join(map(str, s))) for s in SMALL_SHAPES]
+                         + [pytest.param(*s, False, id="-".join(map(str, s)) + "-noalign") for s in SMALL_SHAPES])
+def test_small_and_skinny_images_vs_oracle(b, h, w, align, precision):
+    """Smallest legal image (one 8x8 cell), single-cell rows, very skinny planes, odd batch; both align_corners modes (the
+    position-major descriptor view of sample_kernel is reached only through spp_forward)."""
     cfg = {"nms_radius": 2, "remove_borders": 0, "keypoint_threshold": 0.001, "max_keypoints": -1}
-    mod, sd = make_module(b + h, cfg, precision=precision)
+    mod, sd = make_module(b + h, cfg, align=align, precision=precision)
     img = synthetic.make_image(b, h, w, 7 * h + w)
     out = mod(torch.from_numpy(img).cuda())
-    ref = so.forward(sd, img, cfg)
+    ref = so.forward(sd, img, cfg, align_corners=align)
     for i in range(b):
         kp, rk = out["keypoints"][i].cpu().numpy(), ref["keypoints"][i]
         diff = set(map(tuple, kp.tolist())) ^ set(map(tuple, rk.tolist()))
