@@ -76,6 +76,18 @@ size_t spp_workspace_bytes(int b, int H, int W);
 int spp_dense(const float* packed, const float* image, int b, int H, int W, float* score_map, float* dense_desc,
               void* workspace, size_t workspace_bytes, spp_stream_t stream, int flags);
 
+/* One stage of spp_dense, for tests: enqueues exactly the launches spp_dense enqueues for this (b, H, W, flags) up to and including
+ * the one that produces `stage`, then copies that activation, without the library's padding, to out [b][C][Hk][Wk]:
+ *   0 relu(conv1a) [64][H][W]            1 pool(relu(conv1b)) [64][H/2][W/2]    2 relu(conv2a) [64][H/2][W/2]
+ *   3 pool(relu(conv2b)) [64][H/4][W/4]  4 relu(conv3a) [128][H/4][W/4]         5 pool(relu(conv3b)) [128][H/8][W/8]
+ *   6 relu(conv4a) [128][H/8][W/8]       7 relu(conv4b) [128][H/8][W/8]
+ *   8 relu(convPa) stacked on relu(convDa) [512][H/8][W/8]      9 logits [65][H/8][W/8]
+ *   10 descriptors, not normalised [256][H/8][W/8] (spp_dense's dense_desc)
+ * (integer divisions).  Refuses what spp_dense refuses, and stage 0 under SPP_FLAG_PREC_FP16X4 with even H: that plane is never
+ * written there (see above). */
+int spp_dense_stage(const float* packed, const float* image, int b, int H, int W, int stage, float* out, void* workspace,
+                    size_t workspace_bytes, spp_stream_t stream, int flags);
+
 /* Discrete stages (:163-195) from given dense tensors: NMS, threshold, border removal, top-k,
  * (h,w)->(x,y), descriptor normalisation + bilinear sampling + normalisation.
  *   score_map      PRECONDITION: every score is >= 0 and none is NaN (a cell softmax gives nothing else).  The top-k is a radix

@@ -27,6 +27,9 @@ class RawWeights(ctypes.Structure):
 FLAG_PREC_FP16X4 = 0x800
 PRECISIONS = {"fp32": 0, "fp16x4": FLAG_PREC_FP16X4}   # arithmetic of the GEMM convolutions, a `flags` bit per call
 
+# spp_dense_stage: (channels, log2 of the down-sampling) of stage 0 .. 10
+DENSE_STAGES = ((64, 0), (64, 1), (64, 1), (64, 2), (128, 2), (128, 3), (128, 3), (128, 3), (512, 3), (65, 3), (256, 3))
+
 _DETECT = [c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, F32, F32, F32, I32]   # b, H, W, nms_radius .. counts
 _WS = [RAW, c_size_t, STREAM]
 _FWD = [F32, F32] + _DETECT + _WS + [c_int]
@@ -39,6 +42,7 @@ SYMBOLS = {
     "spp_pack_weights": (c_int, [POINTER(RawWeights), F32, STREAM]),
     "spp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "spp_dense": (c_int, [F32, F32, c_int, c_int, c_int, F32, F32] + _WS + [c_int]),
+    "spp_dense_stage": (c_int, [F32, F32, c_int, c_int, c_int, c_int, F32] + _WS + [c_int]),      # ... stage, out (stage tests)
     "spp_detect": (c_int, [F32, F32] + _DETECT + [F32] + _WS),
     "spp_forward": (c_int, _FWD),
     "spp_forward_profiled": (c_int, _FWD + [c_int, c_int, c_void_p, c_void_p]),      # ... kernel_id, occurrence, two hipEvent_t

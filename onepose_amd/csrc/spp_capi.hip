@@ -61,7 +61,7 @@ int forward_impl(const float* packed, const float* image, int b, int H, int W, i
     if (int e = check_detect(nms_radius, max_keypoints, remove_borders, capacity, dp, thr, align_corners)) return e;
     if (!packed || !image || !keypoints || !scores || !descriptors || !counts) return fail(-1, "null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    launch_dense(packed, image, w, s, hk);
+    launch_dense(packed, image, w, s, hk, DENSE_ALL);
     launch_score_map(w, w.score, s, hk);
     launch_detect(w.score, padded_view(w), w, dp, keypoints, scores, descriptors, counts, nullptr, s, hk);
     return check_launch(-1, "spp_forward");
@@ -95,10 +95,27 @@ int spp_dense(const float* packed, const float* image, int b, int H, int W, floa
     if (int e = check_flags(flags, w)) return e;
     if (!packed || !image || !score_map || !dense_desc) return fail(-1, "null argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    launch_dense(packed, image, w, s, nullptr);
+    launch_dense(packed, image, w, s, nullptr, DENSE_ALL);
     launch_score_map(w, score_map, s, nullptr);
     launch_export_dense(w, dense_desc, s);
     return check_launch(-1, "spp_dense");
+}
+
+int spp_dense_stage(const float* packed, const float* image, int b, int H, int W, int stage, float* out, void* workspace,
+                    size_t workspace_bytes, spp_stream_t stream, int flags) {
+    Workspace w;
+    if (int e = check_ws(workspace, workspace_bytes, b, H, W, w)) return e;
+    if (int e = check_flags(flags, w)) return e;
+    if (!packed || !image || !out) return fail(-1, "null argument");
+    if (stage < 0 || stage > DENSE_ALL) return fail(-1, "stage must be in [0, %d] (got %d)", DENSE_ALL, stage);
+    if (!dense_stage_exists(w, stage))
+        return fail(-1, "stage %d does not exist in this configuration: under SPP_FLAG_PREC_FP16X4 with even H conv1a is recomputed "
+                        "inside conv1b's fused kernel and its plane is never written", stage);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    launch_dense(packed, image, w, s, nullptr, stage);
+    if (stage == DENSE_ALL) launch_export_dense(w, out, s);
+    else launch_export_stage(w, stage, out, s);
+    return check_launch(-1, "spp_dense_stage");
 }
 
 int spp_detect(const float* score_map, const float* dense_desc, int b, int H, int W, int nms_radius, float keypoint_threshold,

@@ -159,8 +159,11 @@ struct DetectParams {
 
 // spp_conv_kernels.hip
 void launch_pack_weights(const void* raw_host, float* packed, hipStream_t s);
-void launch_dense(const float* packed, const float* image, const Workspace& w, hipStream_t s, ProfileHook* hk);
+constexpr int DENSE_ALL = 10;     // the last dense stage (superpoint.h: spp_dense_stage), i.e. every launch
+void launch_dense(const float* packed, const float* image, const Workspace& w, hipStream_t s, ProfileHook* hk, int last);
 void launch_export_dense(const Workspace& w, float* dense_desc, hipStream_t s);
+bool dense_stage_exists(const Workspace& w, int stage);     // false: out of range, or conv1a's plane under the fused first layer
+void launch_export_stage(const Workspace& w, int stage, float* out, hipStream_t s);   // an existing stage 0 .. 9 -> [b][C][Hk][Wk]
 // spp_detect_kernels.hip
 void launch_score_map(const Workspace& w, float* score_map, hipStream_t s, ProfileHook* hk);
 // dense descriptors are read through (ptr, channel stride, image stride, row stride, x stride, origin offset).  The extractor's own

@@ -804,6 +804,16 @@ __global__ __launch_bounds__(256) void export_dense_kernel(const float* __restri
     }
 }
 
+// one channel-major padded plane ([C][b * ld]) without its padding: [b][C][H][W] (spp_dense_stage, for tests)
+__global__ __launch_bounds__(256) void export_plane_kernel(const float* __restrict__ X, FeatLayout L, int C, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y, im = blockIdx.z;
+    const int HW = L.H * L.W;
+    if (i >= HW) return;
+    const int y = i / L.W, x = i - y * L.W;
+    out[((size_t)im * C + c) * HW + i] = X[(size_t)c * L.ldt + (size_t)im * L.ld + (size_t)(y + 1) * L.Wp + x + 1];
+}
+
 // =====================================================================================================
 // weight packing
 // =====================================================================================================
@@ -881,6 +891,13 @@ static bool patch_tiling() {
     static const bool on = !(tuning_env("SPP_PATCH") && atoi(tuning_env("SPP_PATCH")) == 0);   // SPP_PATCH=0: flat tiles (A/B timing)
     return on;
 }
+
+static bool fuse_conv1() {
+    static const bool on = !(tuning_env("SPP_FUSE_CONV1") && atoi(tuning_env("SPP_FUSE_CONV1")) == 0);   // 0: separate conv1a / conv1b (A/B timing)
+    return on;
+}
+// split-fp16 with even H: conv1a is recomputed inside conv1b's workgroups, its plane never exists
+static bool fused_first_layer(const Workspace& w) { return w.prec == 4 && fuse_conv1() && (w.L1.H & 1) == 0; }
 
 template <class T, int CIN, int TAPS, int PREC>
 static void launch_conv_t(int gi, int kid, const float* packed, const float* X, float* Y, const FeatLayout& L, int relu,
@@ -973,13 +990,14 @@ static void launch_conv_pool(int gi, int kid, const float* packed, const float* 
     else go(conv_pool_kernel<Tile64x128, CIN, 0>, Tile64x128::THREADS, smem_bytes<Tile64x128>());
 }
 
-void launch_dense(const float* packed, const float* image, const Workspace& w, hipStream_t s, ProfileHook* hk) {
+// `last`: the dense stage (superpoint.h) whose launch ends the sequence; DENSE_ALL for the whole stack.  The launches in front
+// of it are the same for every `last`.
+void launch_dense(const float* packed, const float* image, const Workspace& w, hipStream_t s, ProfileHook* hk, int last) {
     PadPlanes pp{{w.a2, w.b2, w.a3, w.b3, w.a4, w.b4}, {w.L2, w.L2, w.L3, w.L3, w.L4, w.L4}, {64, 64, 64, 128, 128, 128}, 192};
     const int pr = w.prec;
     static const int c1slots = tuning_env("SPP_C1_SLOTS") ? atoi(tuning_env("SPP_C1_SLOTS")) : 64;
     static const int c1delay = tuning_env("SPP_C1_DELAY") ? atoi(tuning_env("SPP_C1_DELAY")) : C1_PHASE_DELAY;
     static const int c1abl = tuning_env("SPP_C1_ABL") ? atoi(tuning_env("SPP_C1_ABL")) : 0;
-    static const bool fuse1 = !(tuning_env("SPP_FUSE_CONV1") && atoi(tuning_env("SPP_FUSE_CONV1")) == 0);   // 0: separate conv1a / conv1b (A/B timing)
     static const bool resident = !(tuning_env("SPP_RESIDENT") && atoi(tuning_env("SPP_RESIDENT")) == 0);   // 0: generic loop for conv2a / conv2b / conv3a
     // the resident-block kernel (split-fp16 only): gi = GEMM convolution, X = input (the image for the first layer), Y = output plane
     auto resident_conv = [&](auto c1a, auto pool, int gi, int kid, const float* X, float* Y, const FeatLayout& L, const FeatLayout& LY) {
@@ -1006,30 +1024,53 @@ void launch_dense(const float* packed, const float* image, const Workspace& w, h
     using std::true_type;
     using std::false_type;
     auto fits = [](const FeatLayout& L) { return (L.H & 1) == 0 && L.W % 64 == 0; };
-    if (pr == 4 && fuse1 && (w.L1.H & 1) == 0) {
+    if (fused_first_layer(w)) {
         // split-fp16: conv1a is recomputed inside conv1b's workgroups (its 64-channel full-resolution plane never exists)
         resident_conv(true_type{}, true_type{}, 0, KID_CONV1B, image, w.a2, w.L1, w.L2);
     } else {
         SPP_LAUNCH(hk, KID_CONV1A, s, conv1a_kernel, dim3((w.L1.ld + 255) / 256 + pp.nblocks, w.L1.b), dim3(256), 0, s, image,
                    packed + PW_C1A_W, packed + PW_C1A_B, w.a1, w.L1, pp);
+        if (last == 0) return;
         launch_conv_pool<64>(0, KID_CONV1B, packed, w.a1, w.b1, w.a2, w.L1, w.L2, s, hk, pr);     // conv1b + pool
     }
+    if (last == 1) return;
     if (pr == 4 && resident && fits(w.L2)) {
         resident_conv(false_type{}, false_type{}, 1, KID_CONV2, w.a2, w.b2, w.L2, w.L2);           // conv2a
+        if (last == 2) return;
         resident_conv(false_type{}, true_type{}, 2, KID_CONV2, w.b2, w.a3, w.L2, w.L3);            // conv2b + pool
     } else {
         launch_conv<64, 9>(1, KID_CONV2, packed, w.a2, w.b2, w.L2, 1, s, hk, pr);
+        if (last == 2) return;
         launch_conv_pool<64>(2, KID_CONV2, packed, w.b2, w.a2, w.a3, w.L2, w.L3, s, hk, pr);      // conv2b + pool (a2 is free: scratch)
     }
+    if (last == 3) return;
     if (pr == 4 && resident && fits(w.L3)) resident_conv(false_type{}, false_type{}, 3, KID_CONV3A, w.a3, w.b3, w.L3, w.L3);   // conv3a
     else launch_conv<64, 9>(3, KID_CONV3A, packed, w.a3, w.b3, w.L3, 1, s, hk, pr);
+    if (last == 4) return;
     launch_conv_pool<128>(4, KID_CONV3B, packed, w.b3, w.c3, w.a4, w.L3, w.L4, s, hk, pr);    // conv3b + pool
+    if (last == 5) return;
     launch_conv<128, 9>(5, KID_CONV4, packed, w.a4, w.b4, w.L4, 1, s, hk, pr);
+    if (last == 6) return;
     launch_conv<128, 9>(6, KID_CONV4, packed, w.b4, w.a4, w.L4, 1, s, hk, pr);
+    if (last == 7) return;
     launch_conv<128, 9>(7, KID_HEADS, packed, w.a4, w.hd, w.L4, 1, s, hk, pr);                                  // relu(convPa), relu(convDa)
+    if (last == 8) return;
     launch_conv<256, 1>(8, KID_CONVPB, packed, w.hd, w.lg, w.L4, 0, s, hk, pr);                                 // logits
+    if (last == 9) return;
     launch_conv<256, 1>(9, KID_CONVDB, packed, w.hd + (size_t)256 * w.L4.ldt, w.dd, w.L4, 0, s, hk, pr);       // descriptors
 }
+
+// the plane a dense stage leaves behind, channel-major stages only (stage 10, the descriptors, is position-major: launch_export_dense)
+void launch_export_stage(const Workspace& w, int stage, float* out, hipStream_t s) {
+    const float* planes[10] = {w.a1, w.a2, w.b2, w.a3, w.b3, w.a4, w.b4, w.a4, w.hd, w.lg};
+    const FeatLayout* layouts[10] = {&w.L1, &w.L2, &w.L2, &w.L3, &w.L3, &w.L4, &w.L4, &w.L4, &w.L4, &w.L4};
+    const int channels[10] = {64, 64, 64, 64, 128, 128, 128, 128, 512, 65};
+    const FeatLayout& L = *layouts[stage];
+    hipLaunchKernelGGL(export_plane_kernel, dim3((L.H * L.W + 255) / 256, channels[stage], L.b), dim3(256), 0, s, planes[stage], L,
+                       channels[stage], out);
+}
+
+bool dense_stage_exists(const Workspace& w, int stage) { return stage >= 0 && stage <= DENSE_ALL && !(stage == 0 && fused_first_layer(w)); }
 
 void launch_export_dense(const Workspace& w, float* dense_desc, hipStream_t s) {
     hipLaunchKernelGGL(export_dense_kernel, dim3((w.L4.H * w.L4.W + 63) / 64, DD / 64, w.L4.b), dim3(256), 0, s, w.dd, w.L4,

@@ -52,14 +52,26 @@ class SuperPointEngine(Engine):
         return _native_spp.PRECISIONS[self.module.precision]
 
     # ---- stages (tests) ----
-    def dense(self, image):
+    def dense(self, image, workspace=None):
         b, _, h, w = image.shape
         dev = image.device
-        ws = self.workspace(b, h, w, dev)
+        ws = self.workspace(b, h, w, dev) if workspace is None else workspace
         score = torch.empty(b, h // 8 * 8, w // 8 * 8, device=dev, dtype=torch.float32)
         dense = torch.empty(b, 256, h // 8, w // 8, device=dev, dtype=torch.float32)
         self.call("spp_dense", dev, self.packed_weights(dev), image, b, h, w, score, dense, ws, ws.numel(), self.flags())
         return score, dense
+
+    def dense_stage(self, image, stage, workspace=None, out=None):
+        """One activation of the dense stack ([b, C, H >> k, W >> k]; ``_native_spp.DENSE_STAGES``) after exactly the launches
+        ``dense`` makes up to it.  ``workspace``: a uint8 tensor of at least ``spp_workspace_bytes`` in place of the cached one."""
+        b, _, h, w = image.shape
+        dev = image.device
+        ws = self.workspace(b, h, w, dev) if workspace is None else workspace
+        c, k = _native_spp.DENSE_STAGES[stage]
+        if out is None:
+            out = torch.empty(b, c, h >> k, w >> k, device=dev, dtype=torch.float32)
+        self.call("spp_dense_stage", dev, self.packed_weights(dev), image, b, h, w, stage, out, ws, ws.numel(), self.flags())
+        return out
 
     def _outputs(self, b, capacity, dev):
         return (torch.empty(b, capacity, 2, device=dev, dtype=torch.float32),

@@ -59,7 +59,7 @@ def test_every_declared_symbol_is_exported():
     text = open(os.path.join(ROOT, "include", "superpoint.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     names = sorted(set(re.findall(r"\b(spp_[a-z0-9_]+)\s*\(", text)))
-    assert len(names) == 9
+    assert len(names) == 10
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/superpoint.h but not exported"
     assert set(names) == set(_native_spp.SYMBOLS)
