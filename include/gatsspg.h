@@ -159,6 +159,36 @@ int gatsspg_forward_cached(const float* packed, const float* desc2d_query, const
                            float match_threshold, float* conf, int64_t* matches0, int64_t* matches1,
                            float* mscores0, float* mscores1, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ragged frame batch against ONE database (the serving case: many frames of one object) ----------------
+ * b <= GATSSPG_MAX_FRAMES frames in one chain of launches; frame i has its own query count n1[i], 2 <= n1[i] <= cap1, and all
+ * frames run against one database and ONE b = 1 cache (gatsspg_prepare_database(b = 1)): nothing of the database is replicated.
+ *   desc2d_query [b,256,cap1]: frame i's descriptors in columns [0, n1[i]); the columns behind them are never read
+ *   n1: HOST memory, b int32 entries, read when the call is enqueued (the counts travel by value in the kernel arguments: nothing is
+ *       allocated, copied or synchronised, and the call can be captured into a graph -- which then holds these counts)
+ *   desc2d_db [1,256,n2*num_leaf]; cache / cache_bytes: as for gatsspg_forward_cached with b = 1
+ *   conf [b,cap1,n2]; matches0 [b,cap1]; matches1 [b,n2]; mscores0 [b,cap1]; mscores1 [b,n2]
+ *   ws: at least gatsspg_workspace_bytes(b, cap1, n2, num_leaf)
+ * Frame i's outputs -- conf rows [0, n1[i]), matches0 / mscores0 [0, n1[i]), matches1 / mscores1 -- are BIT FOR BIT what
+ * gatsspg_forward_cached(b = 1, n1 = n1[i]) returns for that frame alone, in every arithmetic and flag combination: every loop
+ * bound, mask, partial count and partition is the frame's own, and a stage whose kernel form depends on the launch size runs every
+ * frame on the form it takes alone.  Past a count: matches0 = -1 and mscores0 = 0; the conf rows [n1[i], cap1) of frame i are NOT
+ * WRITTEN (28 KB each at 7000 points): they keep whatever the buffer held.
+ * Refused with a message, before any launch: b < 1, b > GATSSPG_MAX_FRAMES, a count below 2 or above cap1, a null pointer, a
+ * cache smaller than gatsspg_db_cache_bytes(1, n2). */
+#define GATSSPG_MAX_FRAMES 32
+int gatsspg_forward_frames(const float* packed, const float* desc2d_query, const int32_t* n1, const float* desc2d_db,
+                           const void* cache, size_t cache_bytes, int b, int cap1, int n2, int num_leaf, int flags,
+                           float scale_factor, float match_threshold, float* conf, int64_t* matches0, int64_t* matches1,
+                           float* mscores0, float* mscores1, void* ws, size_t ws_bytes, void* stream);
+
+/* One GATs layer (layer = 0..3) of a frame batch, on the state of a (b, cap1, n2) workspace: the 3D sides of the b frames against ONE
+ * database's leaves desc2d_db [1,256,n2*num_leaf].  leaf_logits: NULL, or that layer's cached logits ([tiles][32] floats; num_leaf == 8
+ * without the linear transform).  shared_leaf != 0: the kernel that reads each 4-point leaf tile once for a group of 4 frames (what
+ * gatsspg_forward_frames runs; num_leaf == 8 without the linear transform only); 0: the per-frame kernel with the database at frame
+ * stride 0.  Both write, frame by frame, bit for bit what gatsspg_gats_layer writes for that frame with its own copy of the leaves. */
+int gatsspg_gats_layer_frames(const float* packed, int layer, const float* desc2d_db, const float* leaf_logits, int b, int cap1,
+                              int n2, int num_leaf, int flags, int shared_leaf, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- per-stage entry points (the stages gatsspg_forward is made of; used by the parity
  *      tests to check each kernel against the oracle).  They operate on the workspace state. */
 

@@ -6,7 +6,7 @@ fallback: if the shared object is missing, ``load()`` raises.
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_size_t, c_void_p
 
 from ._binding import F32, I64, RAW, STREAM, NativeError, bind  # noqa: F401
 from .build_ext import LIB_PATH
@@ -22,6 +22,7 @@ KERNEL_IDS = {"load_state": 0, "gats": 1, "qkv_kv": 2, "kv_final": 3, "mlp0": 5,
               "mlp3": 7, "final_proj_norm": 8, "score_exp": 9, "conf_finalize": 10, "match_tail": 11, "gats_wlt": 12,
               "softmax_stats": 13}
 LAYER_SELF, LAYER_CROSS = 0, 1
+MAX_FRAMES = 32      # GATSSPG_MAX_FRAMES: frames per gatsspg_forward_frames call
 
 
 class RawWeights(ctypes.Structure):
@@ -58,6 +59,10 @@ SYMBOLS = {
     "gatsspg_prepare_database": (c_int, [F32, F32, F32, c_int, c_int, c_int, c_int, RAW, c_size_t, RAW, c_size_t, STREAM]),
     "gatsspg_forward_cached": (c_int, [F32, F32, F32, RAW, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_float]
                                + _FWD_OUT),
+    # packed, desc2d_query [b,256,cap1], n1 (HOST int32 array, b entries), desc2d_db, cache, cache_bytes, b, cap1, n2, num_leaf, flags, ...
+    "gatsspg_forward_frames": (c_int, [F32, F32, POINTER(c_int32), F32, RAW, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_float]
+                               + _FWD_OUT),
+    "gatsspg_gats_layer_frames": (c_int, [F32, c_int, F32, F32, c_int, c_int, c_int, c_int, c_int, c_int, RAW, c_size_t, STREAM]),
     "gatsspg_load_state": (c_int, [F32, F32] + _STATE + [RAW, c_size_t, STREAM]),
     "gatsspg_store_state": (c_int, [c_int, F32, F32] + _STATE + [RAW, c_size_t, STREAM]),
     "gatsspg_gats_layer": (c_int, [F32, c_int, F32] + _STATE + [c_int, RAW, c_size_t, STREAM]),

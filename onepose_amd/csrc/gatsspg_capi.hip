@@ -138,7 +138,7 @@ int forward_impl(const float* packed, const float* desc2d_query, const float* de
 
 extern "C" {
 
-int gatsspg_version(void) { return 411; }   // 411: same layouts as 410; the bound data in the KV partials / database cache changed meaning (slots 0..3: per-wave largest key sum of the tile, summed by kv_final; 4..7: max |V|): a cache written by a 410 library must be re-prepared; 410: message-operator scale of the fp16 modes from a data bound (KV partials carry operand maxima: packed-weights, workspace and database-cache layouts changed); 400: split-16-bit GEMMs on the LDS-DMA loop, power-of-two operand scales of the fp16 modes (packed-weights and workspace layouts changed)
+int gatsspg_version(void) { return 412; }   // 412: gatsspg_forward_frames added, nothing else changed (layouts as 411); 411: same layouts as 410; the bound data in the KV partials / database cache changed meaning (slots 0..3: per-wave largest key sum of the tile, summed by kv_final; 4..7: max |V|): a cache written by a 410 library must be re-prepared; 410: message-operator scale of the fp16 modes from a data bound (KV partials carry operand maxima: packed-weights, workspace and database-cache layouts changed); 400: split-16-bit GEMMs on the LDS-DMA loop, power-of-two operand scales of the fp16 modes (packed-weights and workspace layouts changed)
 const char* gatsspg_last_error(void) { return g_err; }
 
 size_t gatsspg_packed_weights_bytes(void) { return PACKED_BYTES; }
@@ -304,6 +304,59 @@ int gatsspg_forward_cached(const float* packed, const float* desc2d_query, const
                    gats_caches_leaf_logits(num_leaf, flags) ? c.LL : nullptr, c.ll_layer);
     enqueue_tail(packed, w, scale_factor, match_threshold, out, s, nullptr);
     return check_launch(1, "forward_cached");
+}
+
+// The cached chain of gatsspg_forward_cached on a frames layout (gatsspg_common.h): the workspace and the outputs are carved for the capacity
+// cap1, every kernel takes the frames' own counts by value in its arguments, the cache of ONE database serves every frame with stride 0.
+int gatsspg_forward_frames(const float* packed, const float* desc2d_query, const int32_t* n1, const float* desc2d_db, const void* cache,
+                           size_t cache_bytes, int b, int cap1, int n2, int num_leaf, int flags, float scale_factor,
+                           float match_threshold, float* conf, int64_t* matches0, int64_t* matches1, float* mscores0,
+                           float* mscores1, void* ws, size_t ws_bytes, void* stream) {
+    Workspace w;
+    const MatchOut out = {conf, matches0, matches1, mscores0, mscores1};
+    if (b < 1 || b > MAX_FRAMES) return fail(1, "forward_frames takes 1 to %d frames (got %d)", MAX_FRAMES, b);
+    if (!n1) return fail(1, "null pointer to the query counts");
+    if (int e = check_ws(ws, ws_bytes, b, cap1, n2, num_leaf, w, flags)) return e;
+    for (int f = 0; f < b; ++f)
+        if (n1[f] < 2 || n1[f] > cap1) return fail(1, "query count of frame %d must be in [2, cap1 = %d] (got %d)", f, cap1, n1[f]);
+    if (!packed || !desc2d_query || !desc2d_db || !cache) return fail(1, "null input pointer");
+    if (int e = check_out(out)) return e;
+    if (int e = check_scale(scale_factor)) return e;
+    const DbCache c = carve_cache(const_cast<void*>(cache), 1, n2);
+    if (cache_bytes < c.bytes) return fail(1, "database cache too small: %zu < %zu bytes (the cache of ONE database, b = 1)", cache_bytes, c.bytes);
+    w.frames = true;
+    w.shared_leaf = true;
+    for (int f = 0; f < MAX_FRAMES; ++f) w.fcnt[f] = f < b ? n1[f] : 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Workspace wx = windowed(w, 0);
+    launch_load_state(desc2d_query, c.Y2, w, s);                            // state = [X0 of every frame | the cached Y2]
+    enqueue_attn(packed, 0, GATSSPG_LAYER_SELF, wx, s);                     // gnn.layers.1, query side only
+    const AttnLayer a1 = attn_layer(packed, 1);
+    launch_qkv_kv(a1, wx, s);                                               // gnn.layers.2: query-side Q, KV, ksum
+    launch_load_columns(nullptr, c.QY, w.Q, w, s);                          // 3D-side Q from the cache
+    launch_kv_final(a1, w, 1, c.kvY, s);
+    launch_mlp(a1, w, s);
+    enqueue_rounds(packed, 1, desc2d_db, num_leaf, flags, w, s, nullptr, nullptr, nullptr,
+                   gats_caches_leaf_logits(num_leaf, flags) ? c.LL : nullptr, c.ll_layer);
+    enqueue_tail(packed, w, scale_factor, match_threshold, out, s, nullptr);
+    return check_launch(1, "forward_frames");
+}
+
+// One GATs layer of a frame batch on the state of a (b, cap1, n2) workspace: the b frames' 3D sides against ONE database's leaves.
+int gatsspg_gats_layer_frames(const float* packed, int layer, const float* desc2d_db, const float* leaf_logits, int b, int cap1, int n2,
+                              int num_leaf, int flags, int shared_leaf, void* ws, size_t ws_bytes, void* stream) {
+    Workspace w;
+    if (b < 1 || b > MAX_FRAMES) return fail(1, "gats_layer_frames takes 1 to %d frames (got %d)", MAX_FRAMES, b);
+    if (int e = check_ws(ws, ws_bytes, b, cap1, n2, num_leaf, w, flags)) return e;
+    if (!packed || !desc2d_db) return fail(1, "null argument");
+    if (layer < 0 || layer >= GATSSPG_NUM_GATS_LAYERS) return fail(1, "GATs layer index %d out of range", layer);
+    if (shared_leaf && !gats_caches_leaf_logits(num_leaf, flags)) return fail(1, "the shared-leaf form serves num_leaf == 8 without the linear transform");
+    if (leaf_logits && !gats_caches_leaf_logits(num_leaf, flags)) return fail(1, "leaf logits exist for num_leaf == 8 without the linear transform only");
+    w.frames = true;
+    w.shared_leaf = shared_leaf != 0;
+    for (int f = 0; f < MAX_FRAMES; ++f) w.fcnt[f] = f < b ? cap1 : 0;   // (a GATs layer touches the 3D side only: the counts do not enter)
+    enqueue_gats(packed, layer, desc2d_db, num_leaf, flags, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, leaf_logits);
+    return check_launch(1, "gats_layer_frames");
 }
 
 size_t gatsspg_kenc_scratch_bytes(int b, int n) { return (b < 1 || n < 1) ? 0 : kenc_scratch_bytes(b, n); }

@@ -63,18 +63,51 @@ __host__ __device__ inline int global_tile(const ColLayout& L, int t) {
     return (t / L.tw_count) * (L.np / 64) + L.tw_first + t % L.tw_count;
 }
 
+// Ragged frame batch against ONE shared database (gatsspg_forward_frames): the same column layout with n1 / n1p as the
+// CAPACITY of every frame's query side -- addresses: segment starts, MDT rows, partial strides, the frame stride of conf -- and the
+// frames' own query counts beside it, by value in the kernel arguments.  Every bound of a loop, mask, partition or tile count takes
+// the frame's own count (q_n / q_np below): what the frame would see alone.  The database-side inputs (cache, leaves) are read with
+// frame stride 0 (db_frame).  `skip`: frames a launch leaves out (bit f) -- a stage whose kernel form is chosen by the size of the
+// frame ALONE runs once per form, each launch on the frames of its form.
+// The kernels take the layout type as a template argument; on a ColLayout the accessors are the plain fields.
+constexpr int MAX_FRAMES = 32;
+struct FramesLayout : ColLayout {
+    unsigned skip;
+    int cnt[MAX_FRAMES];
+};
+template <class LT> inline constexpr bool is_frames = false;
+template <> inline constexpr bool is_frames<FramesLayout> = true;
+// frame f's own query count, and its padded count (what make_layout gives the frame alone)
+__host__ __device__ inline int q_n(const ColLayout& L, int) { return L.n1; }
+__host__ __device__ inline int q_n(const FramesLayout& L, int f) { return L.cnt[f]; }
+__host__ __device__ inline int q_np(const ColLayout& L, int) { return L.n1p; }
+__host__ __device__ inline int q_np(const FramesLayout& L, int f) { return round_up(L.cnt[f], CP); }
+// frame index into the database-side inputs
+__host__ __device__ inline int db_frame(const ColLayout&, int f) { return f; }
+__host__ __device__ inline int db_frame(const FramesLayout&, int) { return 0; }
+// a count of partials over the query rows of frame f (`per` rows each): the launch's own (capacity) count on a ColLayout
+__host__ __device__ inline int q_parts(const ColLayout&, int, int, int launch_count) { return launch_count; }
+__host__ __device__ inline int q_parts(const FramesLayout& L, int f, int per, int) { return (L.cnt[f] + per - 1) / per; }
+// true for a column tile at c0 that the launch leaves alone: a skipped frame, or query-side columns past the frame's own padded count
+__host__ __device__ inline bool tile_dead(const ColLayout&, int) { return false; }
+__host__ __device__ inline bool tile_dead(const FramesLayout& L, int c0) {
+    const int f = c0 / L.np, r = c0 - f * L.np;
+    return ((L.skip >> f) & 1) || (r < L.n1p && r >= round_up(L.cnt[f], CP));
+}
+
 struct TileSeg {
     int frame, side, seg, seg_start, valid;  // valid = number of real (non-pad) columns in the tile
 };
 
-__host__ __device__ inline TileSeg tile_seg(const ColLayout& L, int c0, int bn) {
+template <class LT>
+__host__ __device__ inline TileSeg tile_seg(const LT& L, int c0, int bn) {
     TileSeg t;
     t.frame = c0 / L.np;
     int r = c0 - t.frame * L.np;
     t.side = r >= L.n1p ? 1 : 0;
     t.seg = t.frame * 2 + t.side;
     t.seg_start = t.frame * L.np + (t.side ? L.n1p : 0);
-    int v = t.seg_start + (t.side ? L.n2 : L.n1) - c0;
+    int v = t.seg_start + (t.side ? L.n2 : q_n(L, t.frame)) - c0;
     t.valid = v < 0 ? 0 : (v > bn ? bn : v);
     return t;
 }
@@ -189,7 +222,50 @@ struct Workspace {
     float *rmax_v, *cmax_v, *rshift, *cshift;   // rshift / cshift: row / column maxima of the max-subtracting dual softmax
     int *rmax_i, *cmax_i;
     size_t bytes;
+    // ragged frame batch (gatsspg_forward_frames): the frames' own query counts; L then holds the capacity.  Host side only: a launcher
+    // hands its kernel frames_layout(w) instead of w.L.
+    bool frames;
+    unsigned skip;             // frames the next launch leaves out (FramesLayout::skip)
+    bool shared_leaf;          // GATs layers (num_leaf == 8, no linear transform) on the shared-leaf kernel: each leaf tile read once per group of frames
+    int fcnt[MAX_FRAMES];
 };
+inline FramesLayout frames_layout(const Workspace& w) {
+    FramesLayout F;
+    static_cast<ColLayout&>(F) = w.L;
+    F.skip = w.skip;
+    for (int i = 0; i < MAX_FRAMES; ++i) F.cnt[i] = i < w.L.b ? w.fcnt[i] : 0;
+    return F;
+}
+// calls f with the layout a kernel of this launch takes: w.L, or the frames layout
+template <class F>
+inline void with_layout(const Workspace& w, F&& f) {
+    if (w.frames) f(frames_layout(w));
+    else f(w.L);
+}
+inline unsigned all_frames(const Workspace& w) { return w.L.b >= 32 ? ~0u : (1u << w.L.b) - 1u; }
+// 64-column tiles the launch window holds of frame f ALONE (what active_tiles is at b = 1): the figure the shape thresholds between two
+// kernel forms go by
+inline int alone_tiles(const Workspace& w, int f) {
+    const int n1p = w.frames ? round_up(w.fcnt[f], CP) : w.L.n1p;
+    return ((w.L.side_mask & 1) ? n1p / 64 : 0) + ((w.L.side_mask & 2) ? w.L.n2p / 64 : 0);
+}
+// A stage with two kernel forms chosen by a shape threshold `first(tiles)`: one launch as ever on a uniform layout; on a frames layout
+// every frame takes the form it would take alone, so the stage is up to two launches, each skipping the other form's frames.
+template <class Pred, class FA, class FB>
+inline void launch_by_form(const Workspace& w, Pred first, FA fa, FB fb) {
+    if (!w.frames) {
+        if (first(active_tiles(w.L))) fa(w);
+        else fb(w);
+        return;
+    }
+    unsigned ma = 0;
+    for (int f = 0; f < w.L.b; ++f)
+        if (first(alone_tiles(w, f))) ma |= 1u << f;
+    const unsigned mb = all_frames(w) & ~ma;
+    Workspace v = w;
+    if (ma) { v.skip = w.skip | mb; fa(v); }
+    if (mb) { v.skip = w.skip | ma; fb(v); }
+}
 
 // M_t of segment `seg`: element (r, c), c = h*64 + d, at mop_seg(Mop, seg)[r * MOP_LD + c]
 __host__ __device__ inline float* mop_seg(float* Mop, int seg) { return Mop + (size_t)(seg >> 1) * 512 * MOP_LD + ((seg & 1) ? 0 : 256); }
@@ -201,6 +277,7 @@ inline Workspace carve_workspace(void* base, int b, int n1, int n2) {
     Workspace w;
     w.L = make_layout(b, n1, n2);
     w.prec = FP32;
+    w.frames = false; w.skip = 0; w.shared_leaf = false;
     const ColLayout& L = w.L;
     w.nt64 = L.ld / 64;
     w.nseg = 2 * b;

@@ -113,6 +113,10 @@ __device__ __forceinline__ void read_bias16(const float* tab, int wm, int half, 
 constexpr int STATCNT_PER_SEG = 8;   // row tiles of mlp.0 per segment (512 / 64 at most)
 __device__ __forceinline__ void stat_partial_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // PENDING: vector-memory instructions this thread issued AFTER its partial stores (the tile's own stores), which may stay in flight
+// NOT VALID ON A FRAMES LAYOUT (FramesLayout, gatsspg_common.h): the arrival count nwg, the tile count nt and n below are the CAPACITY's there,
+// while the workgroups past a frame's own tiles never arrive and the frame's sums run over its own tiles (stat_final_kernel takes q_n / q_np).
+// Every launcher passes statcnt = nullptr, so the call is compiled in and never taken; whoever switches the fused form back on must first
+// make this function take the layout type and use q_n / q_np, as stat_final_kernel does.
 template <class T, int PENDING>
 __device__ __forceinline__ void stat_last_block(const float* statpart, float* stats, int* cnt, const ColLayout& L, const TileSeg& ts, int rt,
                                                 void* smem_v) {
@@ -234,12 +238,14 @@ __device__ __forceinline__ void mlp0_tile_statistics(const float* Tl, float* sta
 //   TS / SKEW: row stride of the staged tile and the bank skew of the row-sum walk (fp32 kernel: BN + 1, none; split kernel: BN + 4 --
 //   conflict-free 16-byte row reads, see mlp0_sp_kernel -- and rows 4 banks apart, the two lanes of a row 32 banks apart).
 // ---------------------------------------------------------------------------------------------------------------------
-template <class T, int TS, bool SKEW, bool RAW, bool PRESCALED>
+// LT: ColLayout, or FramesLayout -- conf rows and the row masks then go by the frame's own count n1 = q_n(L, frame), addresses by the capacity L.n1.
+template <class T, int TS, bool SKEW, bool RAW, bool PRESCALED, class LT>
 __device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[T::TM][T::TN], float* Tl, float* conf, float* rowpart, float* colpart,
-                                               const ColLayout& L, int frame, int rt, int ct, int nrt, int nct, float inv, float scale) {
+                                               const LT& L, int frame, int rt, int ct, int nrt, int nct, float inv, float scale) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
     float* cf = conf + (size_t)frame * L.n1 * L.n2;
+    const int n1 = q_n(L, frame);
 #pragma unroll
     for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
@@ -248,7 +254,7 @@ __device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[T::TM][T::TN]
             const int col = wn * 32 + l31;
             const int gi = rt * T::BM + row, gj = ct * T::BN + col;
             const float sc = PRESCALED ? (acc[tm][0][r] * inv) / scale : acc[tm][0][r] / scale;
-            Tl[row * TS + col] = (gi < L.n1 && gj < L.n2) ? (RAW ? sc : expf(sc)) : 0.f;
+            Tl[row * TS + col] = (gi < n1 && gj < L.n2) ? (RAW ? sc : expf(sc)) : 0.f;
         }
     __syncthreads();
     // the tile leaves through LDS: 16 lanes cover one 256-byte row segment (16-byte stores when the rows of conf are
@@ -257,7 +263,7 @@ __device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[T::TM][T::TN]
         for (int idx = tid; idx < T::BM * (T::BN / 4); idx += T::THREADS) {
             const int row = idx / (T::BN / 4), c4 = (idx % (T::BN / 4)) * 4;
             const int gi = rt * T::BM + row, gj = ct * T::BN + c4;
-            if (gi < L.n1 && gj < L.n2) {
+            if (gi < n1 && gj < L.n2) {
                 const float* t = Tl + row * TS + c4;
                 vf4 v;
                 if constexpr (TS % 4 == 0) v = *reinterpret_cast<const vf4*>(t);
@@ -269,7 +275,7 @@ __device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[T::TM][T::TN]
         for (int idx = tid; idx < T::BM * T::BN; idx += T::THREADS) {
             const int row = idx / T::BN, col = idx % T::BN;
             const int gi = rt * T::BM + row, gj = ct * T::BN + col;
-            if (gi < L.n1 && gj < L.n2) cf[(size_t)gi * L.n2 + gj] = Tl[row * TS + col];
+            if (gi < n1 && gj < L.n2) cf[(size_t)gi * L.n2 + gj] = Tl[row * TS + col];
         }
     }
     if constexpr (!RAW) {

@@ -5,6 +5,8 @@
 #include "gatsspg_epilogue.h"
 #include "gatsspg_launch.h"
 
+#include <type_traits>
+
 namespace gatsspg {
 
 // dynamic LDS of a main loop (operand stages; the epilogues re-use it)
@@ -40,19 +42,20 @@ using QkvTileW8 = GemmTile<128, QKV_BN, 4, 2, false>;     // both arithmetics: 8
 // round -- was measured: kernel -2 %, frames/s in flight unchanged; not kept)
 // DS: the Q tiles leave straight from the accumulators (store_tile_regs) instead of through an LDS staging tile
 // QF: quarter-fragment main loop (gemm_f32_mfma.h; fp32 arithmetic only)
-template <class T, int PREC = 0, int BT = 0, int DS = 0, int QF = 0>
+template <class T, int PREC = 0, int BT = 0, int DS = 0, int QF = 0, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void qkv_kv_kernel(const float* __restrict__ Wqkv, const float* __restrict__ bqkv,
                                                             const unsigned short* __restrict__ Whi,
                                                             const unsigned short* __restrict__ Wlo,
                                                             const unsigned short* __restrict__ Wl2,
                                                             const float* __restrict__ Z, float* __restrict__ Qbuf,
-                                                            float* __restrict__ kvpart, ColLayout L) {
+                                                            float* __restrict__ kvpart, LT L) {
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: qkv_kv_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
     if (!xcd_tile_map(6, active_tiles(L), rt, ct)) return;
     ct = global_tile(L, ct);
     const int c0 = ct * T::BN;
+    if (tile_dead(L, c0)) return;
     const int ld = L.ld;
     const float* A = Wqkv + (size_t)rt * 128 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -199,12 +202,12 @@ static_assert(KVP % 4 == 0, "KV partials are summed as float4");
 // partial read once.  (2, two workgroups per d block each repeating the reduction, lost: profiles/r04_ab_live_kv_final.txt; removed.)
 // abl: 0.  (The operator-phase ablations behind it are gone; the parameter and its branches stay because without them hipcc gives the
 // kernel 110 instead of 94 VGPRs.)
-template <int KVF_RS>
+template <int KVF_RS, class LT = ColLayout>
 __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict__ kvpart, const float* __restrict__ kv_src,
                                                         float* __restrict__ kvfin, const float* __restrict__ W0,
                                                         float* __restrict__ Mop, unsigned short* __restrict__ Mpl,
                                                         float* __restrict__ ksumT, float* __restrict__ zsc, int* __restrict__ statcnt,
-                                                        const float* __restrict__ sc, ColLayout L, int cross, int prec, int abl) {
+                                                        const float* __restrict__ sc, LT L, int cross, int prec, int abl) {
     __shared__ float4 red[16][64];
     __shared__ float4 kvs[64];   // this block's final KV^T rows: [4 d][16 float4 of q]
     __shared__ float opsum[16];      // per wave: sum over its tiles of the tile's largest key-sum bound (bound data, slots 0..3)
@@ -235,7 +238,7 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
     // kvfin (and through it the database cache) stores the REDUCED slots -- (ksb, 0, 0, 0) and (vmax, 0, 0, 0) -- so that a cached source, read
     // as a single partial, yields bit for bit the scale of the plain forward (0 + x and max(0, x) are exact).
     // mlp0 folds head h with z_h * zsc_h, zsc_h = (W0 scale) / sM_h: exact.
-    const int nsrc = side ? L.n2 : L.n1;
+    const int nsrc = side ? L.n2 : q_n(L, frame);
     // operator phase: thread = (row pair rp, q quarter qq); lane qq takes the float4s qq, qq + 4, qq + 8, qq + 12 of the 64 q of a
     // row (the 4 lanes of a row read 64 contiguous bytes per load).  The weights do not depend on the reduction: requested first.
     const int rp = (tid >> 2) & (KVF_ROWS / 2 - 1), qq = tid & 3;
@@ -255,9 +258,9 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
             for (int i = 0; i < 4; ++i) wv[e][i] = (vf4){1.f, 2.f, 3.f, 4.f};
     }
     const bool cached = kv_src != nullptr && side == 1;
-    const float* base = cached ? kv_src + ((size_t)frame * H + h) * KVP
+    const float* base = cached ? kv_src + ((size_t)db_frame(L, frame) * H + h) * KVP
                                : kvpart + ((size_t)((frame * L.np + (side ? L.n1p : 0)) / QKV_BN) * H + h) * KVP;
-    const int nt = cached ? 1 : (side ? L.n2p : L.n1p) / QKV_BN;
+    const int nt = cached ? 1 : (side ? L.n2p : q_np(L, frame)) / QKV_BN;
     const int per = (nt + 15) / 16;
     const int tb = part * per, te = min(nt, tb + per);
     // operand maxima of the source's tiles (fp16 modes; requested in front of the reduction's loads, consumed behind them)
@@ -426,7 +429,7 @@ static constexpr unsigned long long* g_trace = nullptr;
 // QF: quarter-fragment main loop (gemm_f32_mfma.h; fp32 arithmetic on the 8-wave tile only)
 // SF: the fused InstanceNorm reducer (stat_last_block) is compiled in, never taken (statcnt = nullptr; the retired STAT_FUSED form).  Only
 //     the split-bf16 instantiations keep it, to keep their code (launch_mlp0_t); in fp32 its 64 staging registers set the count (118 of 126).
-template <class T, int PREC = 0, int BT = 0, int QF = 0, int SF = 0>
+template <class T, int PREC = 0, int BT = 0, int QF = 0, int SF = 0, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1)) void mlp0_kernel(const float* __restrict__ W0, const float* __restrict__ b0,
                                                    const unsigned short* __restrict__ Whi, const unsigned short* __restrict__ Wlo,
                                                    const unsigned short* __restrict__ Wl2,
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1))
                                                    const float* __restrict__ Mop, const unsigned short* __restrict__ Mpl,
                                                    const float* __restrict__ ksumT,
                                                    float* __restrict__ U, float* __restrict__ statpart, float* __restrict__ stats,
-                                                   int* __restrict__ statcnt, ColLayout L, unsigned long long* trace) {
+                                                   int* __restrict__ statcnt, LT L, unsigned long long* trace) {
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp0_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const unsigned long long t_entry = trace ? wall_clock64() : 0;
@@ -445,6 +448,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1))
     if (!xcd_tile_map(MT, active_tiles(L) / TPW, rt, ct)) return;
     ct = global_tile(L, ct * TPW) / TPW;   // windows and segments are multiples of 128 columns
     const int c0 = ct * T::BN, ld = L.ld;
+    if (tile_dead(L, c0)) return;
     const float* A = W0 + (size_t)rt * T::BM * 512;
     const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) % T::WAVES_MN;   // (K-split tiles: wave within its group)
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
@@ -539,9 +543,9 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1))
 // TW: columns per partial -- MLP0_BN (64) from the channel-major mlp.0 kernels, 32 from mlp0_sp's transposed epilogue (one per wave strip).
 // A block = ROWS channels x PARTS tile ranges; with twice the partials (TW = 32) it takes half the channels and twice the ranges, so that a
 // range is still one batch of <= 8 loads at the headline shape (the first form kept 64 x 16 and paid a second dependent round trip: +1 us).
-template <int TW>
+template <int TW, class LT = ColLayout>
 __global__ __launch_bounds__(1024) void stat_final_kernel(const float* __restrict__ statpart, float* __restrict__ stats,
-                                                          ColLayout L) {
+                                                          LT L) {
     constexpr int ROWS = TW == 32 ? 32 : 64, PARTS = 1024 / ROWS;
     __shared__ double red[2][PARTS][ROWS];
     const int rl = threadIdx.x % ROWS, part = threadIdx.x / ROWS;
@@ -549,8 +553,8 @@ __global__ __launch_bounds__(1024) void stat_final_kernel(const float* __restric
     const int frame = seg >> 1, side = seg & 1;
     if (!((L.side_mask >> side) & 1)) return;
     const int t0 = (frame * L.np + (side ? L.n1p : 0)) / TW;
-    const int nt = (side ? L.n2p : L.n1p) / TW;
-    const int n = side ? L.n2 : L.n1;
+    const int nt = (side ? L.n2p : q_np(L, frame)) / TW;
+    const int n = side ? L.n2 : q_n(L, frame);
     const int per = (nt + PARTS - 1) / PARTS;
     const int tb = part * per, te = min(nt, tb + per);
     double S = 0.0, QP = 0.0;
@@ -602,12 +606,12 @@ using Mlp3TileTallW8 = GemmTile<128, 64, 4, 2, false>;   // both arithmetics: 12
 using Mlp3TileS = GemmTile<64, 64, 2, 2, false, false, 2>;   // fp32, launches that leave CUs empty: 64x64, two K groups of 4 waves
 
 // DS: the output tile leaves straight from the accumulators (store_tile_regs; plain 128 x 64 / 64 x 64 tiles, not the K-split one)
-template <class T, int PREC = 0, int DS = 0>
+template <class T, int PREC = 0, int DS = 0, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void mlp3_kernel(const float* __restrict__ W3, const float* __restrict__ b3,
                                                    const unsigned short* __restrict__ Whi, const unsigned short* __restrict__ Wlo,
                                                    const unsigned short* __restrict__ Wl2,
                                                    const float* __restrict__ U, const float* __restrict__ stats,
-                                                   float* __restrict__ Z, ColLayout L) {
+                                                   float* __restrict__ Z, LT L) {
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp3_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
@@ -616,6 +620,7 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void mlp3_ker
     if (!xcd_tile_map(MT, active_tiles(L) / TPW, rt, ct)) return;
     ct = global_tile(L, ct * TPW) / TPW;
     const int c0 = ct * T::BN, ld = L.ld;
+    if (tile_dead(L, c0)) return;
     const TileSeg ts = tile_seg(L, c0, T::BN);  // segments start on multiples of 128: a tile never straddles two
     const float* mean = stats + ((size_t)ts.seg * 2 + 0) * 512;
     const float* rstd = stats + ((size_t)ts.seg * 2 + 1) * 512;
@@ -678,16 +683,18 @@ using FinalTile = GemmTile<256, 32, 8, 1, false>;   // 8 waves x one 32x32 tile 
 
 // planes_prec: 0, or the arithmetic (BF16X6 / FP16X4) whose 16-bit planes of the query descriptors (MDTp, slab-major over all b * n1p
 // rows; fp16: of 2^SCORE_SPLIT_SCALE_LOG2 x) the split score contraction reads as its A operand
+template <class LT = ColLayout>
 __global__ __launch_bounds__(FinalTile::THREADS) void final_proj_norm_kernel(const float* __restrict__ Wf, const float* __restrict__ bf,
                                                               const float* __restrict__ Z, float* __restrict__ MD,
                                                               float* __restrict__ MDT, unsigned short* __restrict__ MDTp,
-                                                              int planes_prec, ColLayout L) {
+                                                              int planes_prec, LT L) {
     using T = FinalTile;
     if (planes_prec >= FP16X3) fp16_saturate_mode();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ float npart[T::WM][32];
     const int ct = blockIdx.x;
     const int c0 = ct * T::BN, ld = L.ld;
+    if (tile_dead(L, c0)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
     float bias[T::TM][16];   // requested before the main loop
@@ -771,15 +778,18 @@ using ScoreTileW8 = GemmTile<SC_BM, SC_BN, 4, 2, false>;        // default: 128x
 // Both one-round shapes measured SLOWER than 1.7 rounds of 128x64: 128x128 48.4 vs 45.3 us (event-timed), 256x64 (90 KB of LDS,
 // one workgroup per CU) 52.7 vs 46.4 us; three 128x64 workgroups per CU (80 VGPRs) unchanged.
 
-template <class T, bool RAW>
+template <class T, bool RAW, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS) void score_exp_kernel(const float* __restrict__ MDT, const float* __restrict__ MD,
                                                                float* __restrict__ conf, float* __restrict__ rowpart,
-                                                               float* __restrict__ colpart, ColLayout L, float scale) {
+                                                               float* __restrict__ colpart, LT L, float scale) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int nrt = (L.n1p + T::BM - 1) / T::BM, nct = L.n2p / T::BN;   // a last row tile may hang over n1p (rows masked below)
     int rt, ct;
     const int frame = blockIdx.y;
     if (!xcd_tile_map(nrt, nct, rt, ct)) return;
+    if constexpr (is_frames<LT>) {
+        if (rt * T::BM >= q_np(L, frame)) return;   // a row tile past the frame's own
+    }
     const int ld = L.ld;
     const float* Ap = MDT + ((size_t)frame * L.n1p + rt * T::BM) * D;     // [M][K], row stride 256
     const float* Bp = MD + (size_t)frame * L.np + L.n1p + ct * T::BN;
@@ -931,9 +941,12 @@ template <class T, int PREC, int BT = 0, int DS = 0, int QF = 0>
 static void launch_qkv_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const int NT = active_tiles(w.L);
     const WPlanes p = a.qkv_planes();
-    allow_big_lds<qkv_kv_kernel<T, PREC, BT, DS, QF>>();
-    GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_kernel<T, PREC, BT, DS, QF>), dim3(xcd_grid(6, NT)), dim3(T::THREADS), (smem_bytes<T, PREC>() + 512 * BT), s,
-                   a.WQKV(), a.BQKV(), p.hi, p.lo, p.lo2, w.Z, w.Q, w.kvpart, w.L);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<qkv_kv_kernel<T, PREC, BT, DS, QF, LT>>();
+        GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_kernel<T, PREC, BT, DS, QF, LT>), dim3(xcd_grid(6, NT)), dim3(T::THREADS), (smem_bytes<T, PREC>() + 512 * BT), s,
+                       a.WQKV(), a.BQKV(), p.hi, p.lo, p.lo2, w.Z, w.Q, w.kvpart, L);
+    });
 }
 
 // The fp16 modes run on the LDS-DMA loop (their planes carry the pack-time scale that only those kernels undo); the bf16 modes stay on the
@@ -952,8 +965,10 @@ void launch_kv_final(const AttnLayer& a, const Workspace& w, int cross, const fl
     // 11.4 -> 10.5 us event-timed, +0.7 ... +1.6 % frames/s in flight at the three shapes, bit-identical results; the two-row-part form is removed).
     // (round 6: the projection split in two launches so that kv_final runs beside the Q tiles -- 1264 vs 1266 frames/s in flight,
     //  profiles/r06e_*, r06f_* -- and a narrow 512-thread form -- 11.85 vs 11.22 us, profiles/r06c_ab_live_kvf_narrow_*.txt -- both removed)
-    GATSSPG_LAUNCH(hk, KID_KV_FINAL, s, kv_final_kernel<1>, dim3(17, w.nseg * H), dim3(1024), 0, s, w.kvpart, kv_src, w.kvfin, a.W0(), w.Mop, w.Mpl,
-                   w.ksumT, w.zsc, w.statcnt, a.SC(), w.L, cross, (int)w.prec, 0);
+    with_layout(w, [&](const auto& L) {
+        GATSSPG_LAUNCH(hk, KID_KV_FINAL, s, (kv_final_kernel<1, std::decay_t<decltype(L)>>), dim3(17, w.nseg * H), dim3(1024), 0, s, w.kvpart, kv_src, w.kvfin,
+                       a.W0(), w.Mop, w.Mpl, w.ksumT, w.zsc, w.statcnt, a.SC(), L, cross, (int)w.prec, 0);
+    });
 }
 
 // SF: the fused InstanceNorm reducer (stat_last_block) compiled in as a branch that never runs (statcnt = nullptr).  The split-bf16
@@ -964,19 +979,25 @@ template <class T, int PREC, int BT = 0, int QF = 0>
 static void launch_mlp0_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     constexpr int SF = PREC != FP32;
     const WPlanes p = a.w0_planes();
-    allow_big_lds<mlp0_kernel<T, PREC, BT, QF, SF>>();
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
-    GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, PREC, BT, QF, SF>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS),
-                   (smem_bytes<T, PREC>() + sizeof(float) * AttnFoldHooks::ZP_FLOATS + 512 * BT), s, a.W0(), a.B0(), p.hi, p.lo, p.lo2, w.Z, w.Q,
-                   w.Mop, w.Mpl, w.ksumT, w.U, w.statpart, w.stats, nullptr, w.L, g_trace);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<mlp0_kernel<T, PREC, BT, QF, SF, LT>>();
+        GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, PREC, BT, QF, SF, LT>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS),
+                       (smem_bytes<T, PREC>() + sizeof(float) * AttnFoldHooks::ZP_FLOATS + 512 * BT), s, a.W0(), a.B0(), p.hi, p.lo, p.lo2, w.Z, w.Q,
+                       w.Mop, w.Mpl, w.ksumT, w.U, w.statpart, w.stats, nullptr, L, g_trace);
+    });
 }
 template <class T, int PREC, int DS = 0>
 static void launch_mlp3_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const WPlanes p = a.w3_planes();
-    allow_big_lds<mlp3_kernel<T, PREC, DS>>();
     const int NT = active_tiles(w.L) / (T::BN / 64);
-    GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, PREC, DS>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS),
-                   (smem_bytes<T, PREC>()), s, a.W3(), a.B3(), p.hi, p.lo, p.lo2, w.U, w.stats, w.Z, w.L);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<mlp3_kernel<T, PREC, DS, LT>>();
+        GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, PREC, DS, LT>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS),
+                       (smem_bytes<T, PREC>()), s, a.W3(), a.B3(), p.hi, p.lo, p.lo2, w.U, w.stats, w.Z, L);
+    });
 }
 
 void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
@@ -989,18 +1010,25 @@ void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHo
     else if (active_tiles(w.L) > diet_min_tiles()) launch_mlp0_t<Mlp0TileW8, FP32, 1, 1>(a, w, s, hk);   // quarter fragments + bias table (94 VGPRs)
     else launch_mlp0_t<Mlp0TileW8, FP32>(a, w, s, hk);   // small launches: the two-half fragment loop (126 VGPRs)
     // the InstanceNorm reducer is a launch of its own (see launch_mlp0_t)
-    GATSSPG_LAUNCH(hk, KID_STAT_FINAL, s, stat_final_kernel<MLP0_BN>, dim3(w.nseg, 8), dim3(1024), 0, s, w.statpart, w.stats, w.L);
+    with_layout(w, [&](const auto& L) {
+        GATSSPG_LAUNCH(hk, KID_STAT_FINAL, s, (stat_final_kernel<MLP0_BN, std::decay_t<decltype(L)>>), dim3(w.nseg, 8), dim3(1024), 0, s, w.statpart, w.stats, L);
+    });
     if (is_fp16(w.prec)) launch_mlp3_sp(a, w, s, hk);
     else if (w.prec == BF16X3) launch_mlp3_t<Mlp3TileTallW8, BF16X3>(a, w, s, hk);
     else if (w.prec == BF16X6) launch_mlp3_t<Mlp3TileTallW8, BF16X6>(a, w, s, hk);
-    else if (active_tiles(w.L) <= small_nt3) launch_mlp3_t<Mlp3TileS, FP32>(a, w, s, hk);
-    else launch_mlp3_t<Mlp3TileTallW8, FP32, 1>(a, w, s, hk);
+    else   // the K-split tile adds its two halves last: every frame of a frames layout takes the tile it takes alone
+        launch_by_form(
+            w, [&](int tiles) { return tiles <= small_nt3; }, [&](const Workspace& v) { launch_mlp3_t<Mlp3TileS, FP32>(a, v, s, hk); },
+            [&](const Workspace& v) { launch_mlp3_t<Mlp3TileTallW8, FP32, 1>(a, v, s, hk); });
 }
 
 void launch_final_proj_norm(const float* Wf, const float* bf, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    allow_big_lds<final_proj_norm_kernel>();
-    GATSSPG_LAUNCH(hk, KID_FINAL_PROJ, s, final_proj_norm_kernel, dim3(w.L.ld / FinalTile::BN), dim3(FinalTile::THREADS),
-                   (smem_bytes<FinalTile>()), s, Wf, bf, w.Z, w.MD, w.MDT, w.MDTp, score_on_split_loop(w.prec, 0) ? (int)w.prec : 0, w.L);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<final_proj_norm_kernel<LT>>();
+        GATSSPG_LAUNCH(hk, KID_FINAL_PROJ, s, final_proj_norm_kernel<LT>, dim3(w.L.ld / FinalTile::BN), dim3(FinalTile::THREADS),
+                       (smem_bytes<FinalTile>()), s, Wf, bf, w.Z, w.MD, w.MDT, w.MDTp, score_on_split_loop(w.prec, 0) ? (int)w.prec : 0, L);
+    });
 }
 
 int score_tile_rows() { return SC_BM; }
@@ -1008,10 +1036,13 @@ int score_tile_cols() { return ScoreTileW8::BN; }
 
 template <class T, bool RAW>
 static void launch_score_t(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk) {
-    allow_big_lds<score_exp_kernel<T, RAW>>();
     const int nrt = (w.L.n1p + T::BM - 1) / T::BM;
-    GATSSPG_LAUNCH(hk, KID_SCORE_EXP, s, (score_exp_kernel<T, RAW>), dim3(xcd_grid(nrt, w.L.n2p / T::BN), w.L.b), dim3(T::THREADS),
-                   (smem_bytes<T>()), s, w.MDT, w.MD, conf, w.rowpart, w.colpart, w.L, scale);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<score_exp_kernel<T, RAW, LT>>();
+        GATSSPG_LAUNCH(hk, KID_SCORE_EXP, s, (score_exp_kernel<T, RAW, LT>), dim3(xcd_grid(nrt, w.L.n2p / T::BN), w.L.b), dim3(T::THREADS),
+                       (smem_bytes<T>()), s, w.MDT, w.MD, conf, w.rowpart, w.colpart, L, scale);
+    });
 }
 
 // The fp32-class split modes (bf16x6: operands split exactly; fp16x4: the exact product of 22-bit operands) also run the score

@@ -6,6 +6,8 @@
 #include "gatsspg_epilogue.h"
 #include "gatsspg_launch.h"
 
+#include <type_traits>
+
 namespace gatsspg {
 
 #ifndef GATSSPG_PROFILING_BUILD
@@ -38,11 +40,11 @@ template <int MODE>
 using QkvSpTile = SpTile<128, 2, 2, 2, MODE>;
 
 // fp16 modes on the slot schedule (SCHED 4); the bias through an LDS table, the Q tiles stored straight from the accumulators
-template <class T>
+template <class T, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS, 3) void qkv_kv_sp_kernel(const float* __restrict__ sc, const float* __restrict__ bqkv,
                                                                 const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                                 const unsigned short* __restrict__ P2, const float* __restrict__ Z,
-                                                                float* __restrict__ Qbuf, float* __restrict__ kvpart, ColLayout L) {
+                                                                float* __restrict__ Qbuf, float* __restrict__ kvpart, LT L) {
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     float* smem = reinterpret_cast<float*>(smem_c);
     if constexpr (T::F16) fp16_saturate_mode();
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(T::THREADS, 3) void qkv_kv_sp_kernel(const float* _
     if (!xcd_tile_map_g(6, active_tiles(L), L.xgs, rt, ct)) return;
     ct = global_tile(L, ct);
     const int c0 = ct * T::BN, ld = L.ld;
+    if (tile_dead(L, c0)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
     static_assert(T::BM == 128, "one half piece of bias values");
@@ -218,14 +221,14 @@ template <int MODE>
 using Mlp0SpTileN = SpTile<128, 2, 2, 3, MODE>;   // 128 x 64 on 4 waves: twice the workgroups (small shapes), two per CU
 
 // fp16 modes on the slot schedule (SCHED 4); the bias through an LDS table
-template <class T>
+template <class T, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS, (T::TM == 4 ? 1 : (T::WAVES == 4 && T::NST == 2) ? 3 : 2)) void mlp0_sp_kernel(const float* __restrict__ sc, const float* __restrict__ b0,
                                                               const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                               const unsigned short* __restrict__ P2, const float* __restrict__ Z,
                                                               const float* __restrict__ Qbuf, const unsigned short* __restrict__ Mpl,
                                                               const float* __restrict__ ksumT, const float* __restrict__ zsc,
                                                               float* __restrict__ U, float* __restrict__ statpart, float* __restrict__ stats,
-                                                              int* __restrict__ statcnt, ColLayout L, unsigned long long* trace) {
+                                                              int* __restrict__ statcnt, LT L, unsigned long long* trace) {
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     float* smem = reinterpret_cast<float*>(smem_c);
     if constexpr (T::F16) fp16_saturate_mode();
@@ -238,6 +241,7 @@ __global__ __launch_bounds__(T::THREADS, (T::TM == 4 ? 1 : (T::WAVES == 4 && T::
     if (!xcd_tile_map(MT, active_tiles(L) / TPW, rt, ct)) return;
     ct = global_tile(L, ct * TPW) / TPW;   // windows and segments are multiples of 128 columns
     const int c0 = ct * T::BN, ld = L.ld;
+    if (tile_dead(L, c0)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
     const TileSeg ts = tile_seg(L, c0, T::BN);
@@ -350,11 +354,11 @@ struct InstNormBx {
 };
 
 // fp16 modes on the slot schedule (SCHED 4); the tile stored straight from the accumulators
-template <class T>
+template <class T, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS, (T::NST == 2 ? 3 : 2)) void mlp3_sp_kernel(const float* __restrict__ sc, const float* __restrict__ b3,
                                                               const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                               const unsigned short* __restrict__ P2, const float* __restrict__ U,
-                                                              const float* __restrict__ stats, float* __restrict__ Z, ColLayout L) {
+                                                              const float* __restrict__ stats, float* __restrict__ Z, LT L) {
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     float* smem = reinterpret_cast<float*>(smem_c);
     if constexpr (T::F16) fp16_saturate_mode();
@@ -364,6 +368,7 @@ __global__ __launch_bounds__(T::THREADS, (T::NST == 2 ? 3 : 2)) void mlp3_sp_ker
     if (!xcd_tile_map_g(MT, active_tiles(L) / TPW, L.xgs, rt, ct)) return;
     ct = global_tile(L, ct * TPW) / TPW;
     const int c0 = ct * T::BN, ld = L.ld;
+    if (tile_dead(L, c0)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / T::WN, wn = wave % T::WN, half = lane >> 5, l31 = lane & 31;
     const TileSeg ts = tile_seg(L, c0, T::BN);
@@ -409,10 +414,10 @@ __global__ __launch_bounds__(T::THREADS, (T::NST == 2 ? 3 : 2)) void mlp3_sp_ker
 template <int MODE>
 using ScoreSpTile = SpTile<SC_BM, 2, 2, 2, MODE, SCORE_SPLIT_SCALE_LOG2>;
 
-template <class T>
+template <class T, class LT = ColLayout>
 __global__ __launch_bounds__(T::THREADS, 3) void score_exp_sp_kernel(const unsigned short* __restrict__ MDTp, const float* __restrict__ MD,
                                                                    float* __restrict__ conf, float* __restrict__ rowpart,
-                                                                   float* __restrict__ colpart, ColLayout L, float scale) {
+                                                                   float* __restrict__ colpart, LT L, float scale) {
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     float* smem = reinterpret_cast<float*>(smem_c);
     static_assert(T::BN == SC_BN && T::BM == SC_BM, "partial sums are per 128 x 64 tile");
@@ -421,6 +426,9 @@ __global__ __launch_bounds__(T::THREADS, 3) void score_exp_sp_kernel(const unsig
     int rt, ct;
     const int frame = blockIdx.y;
     if (!xcd_tile_map(nrt, nct, rt, ct)) return;
+    if constexpr (is_frames<LT>) {
+        if (rt * T::BM >= q_np(L, frame)) return;   // a row tile past the frame's own
+    }
     const int ld = L.ld;
     const size_t R = (size_t)L.b * L.n1p;
     const size_t m0 = (size_t)frame * L.n1p + (size_t)rt * T::BM;
@@ -445,9 +453,12 @@ __global__ __launch_bounds__(T::THREADS, 3) void score_exp_sp_kernel(const unsig
 template <int MODE>
 static void launch_score_sp_t(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk) {
     using T = ScoreSpTile<MODE>;
-    allow_big_lds<score_exp_sp_kernel<T>>();
-    GATSSPG_LAUNCH(hk, KID_SCORE_EXP, s, (score_exp_sp_kernel<T>), dim3(xcd_grid(w.L.n1p / T::BM, w.L.n2p / T::BN), w.L.b), dim3(T::THREADS),
-                   (size_t)T::RING_BYTES, s, w.MDTp, w.MD, conf, w.rowpart, w.colpart, w.L, scale);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<score_exp_sp_kernel<T, LT>>();
+        GATSSPG_LAUNCH(hk, KID_SCORE_EXP, s, (score_exp_sp_kernel<T, LT>), dim3(xcd_grid(w.L.n1p / T::BM, w.L.n2p / T::BN), w.L.b), dim3(T::THREADS),
+                       (size_t)T::RING_BYTES, s, w.MDTp, w.MD, conf, w.rowpart, w.colpart, L, scale);
+    });
 }
 void launch_score_exp_sp(const Workspace& w, float* conf, float scale, hipStream_t s, ProfileHook* hk) {
     if (w.prec == BF16X6) launch_score_sp_t<BF16X6>(w, conf, scale, s, hk);
@@ -467,9 +478,9 @@ void launch_score_exp_sp(const Workspace& w, float* conf, float scale, hipStream
 // 64-column tile (4 waves, two workgroups per CU, twice as many) fills the chip better, with more than one round its co-resident pairs overlap
 // one workgroup's store tail with the other's loop (fp16x4, 8 frames per step: 173 vs 185 us per launch)
 constexpr int SP_MLP0_WIDE_MIN = 48, SP_MLP0_WIDE_MAX = 64;
-static bool mlp0_sp_wide(const ColLayout& L) {
+static bool mlp0_sp_wide(int tiles) {   // tiles: 64-column tiles of the launch (of the frame alone, on a frames layout)
     const int wide_min = tuning_knob("SP_MLP0_WIDE_MIN", SP_MLP0_WIDE_MIN), wide_max = tuning_knob("SP_MLP0_WIDE_MAX", SP_MLP0_WIDE_MAX);
-    return active_tiles(L) / 2 >= wide_min && active_tiles(L) / 2 <= wide_max;
+    return tiles / 2 >= wide_min && tiles / 2 <= wide_max;
 }
 // (mlp.0 leaving U point-major from transposed accumulators, read by mlp.3 as a transposed B operand: 1908 vs 1925 frames/s in flight, 237-243
 //  registers instead of 192; and XCD-paired column tiles beside the 128-column mlp0 tile: no effect, 1912 vs 1908.  profiles/r05c_ab_live_ut_xcd_direct.txt;
@@ -479,9 +490,12 @@ template <int MODE>
 static void launch_qkv_sp_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     using T = QkvSpTile<MODE>;
     const WPlanes p = a.qkv_planes();
-    allow_big_lds<qkv_kv_sp_kernel<T>>();
-    GATSSPG_LAUNCH(hk, KID_QKV_KV, s, qkv_kv_sp_kernel<T>, dim3(xcd_grid(6, active_tiles(w.L))), dim3(T::THREADS), (size_t)T::RING_BYTES + 1024, s,
-                   a.SC(), a.BQKV(), p.h16, p.l16, p.l16, w.Z, w.Q, w.kvpart, w.L);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<qkv_kv_sp_kernel<T, LT>>();
+        GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_sp_kernel<T, LT>), dim3(xcd_grid(6, active_tiles(w.L))), dim3(T::THREADS), (size_t)T::RING_BYTES + 1024, s,
+                       a.SC(), a.BQKV(), p.h16, p.l16, p.l16, w.Z, w.Q, w.kvpart, L);
+    });
 }
 void launch_qkv_kv_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     if (w.prec == FP16X3) launch_qkv_sp_t<FP16X3>(a, w, s, hk);
@@ -492,14 +506,19 @@ template <class T>
 static void launch_mlp0_sp_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const WPlanes p = a.w0_planes();
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
-    allow_big_lds<mlp0_sp_kernel<T>>();
-    GATSSPG_LAUNCH(hk, KID_MLP0, s, mlp0_sp_kernel<T>, dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 2048, s, a.SC(), a.B0(),
-                   p.h16, p.l16, p.l16, w.Z, w.Q, w.Mpl, w.ksumT, w.zsc, w.U, w.statpart, w.stats, nullptr, w.L, g_trace);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<mlp0_sp_kernel<T, LT>>();
+        GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_sp_kernel<T, LT>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 2048, s, a.SC(), a.B0(),
+                       p.h16, p.l16, p.l16, w.Z, w.Q, w.Mpl, w.ksumT, w.zsc, w.U, w.statpart, w.stats, nullptr, L, g_trace);
+    });
 }
 template <int MODE>
 static void launch_mlp0_sp_m(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    if (mlp0_sp_wide(w.L)) launch_mlp0_sp_t<Mlp0SpTileW<MODE>>(a, w, s, hk);
-    else launch_mlp0_sp_t<Mlp0SpTileN<MODE>>(a, w, s, hk);
+    // (the two tiles walk the columns of a statistics partial from different starts: every frame of a frames layout takes the tile it takes alone)
+    launch_by_form(
+        w, [](int tiles) { return mlp0_sp_wide(tiles); }, [&](const Workspace& v) { launch_mlp0_sp_t<Mlp0SpTileW<MODE>>(a, v, s, hk); },
+        [&](const Workspace& v) { launch_mlp0_sp_t<Mlp0SpTileN<MODE>>(a, v, s, hk); });
 }
 void launch_mlp0_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     if (w.prec == FP16X3) launch_mlp0_sp_m<FP16X3>(a, w, s, hk);
@@ -509,9 +528,12 @@ void launch_mlp0_sp(const AttnLayer& a, const Workspace& w, hipStream_t s, Profi
 template <class T>
 static void launch_mlp3_sp_v(const AttnLayer& a, int NT, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const WPlanes p = a.w3_planes();
-    allow_big_lds<mlp3_sp_kernel<T>>();
-    GATSSPG_LAUNCH(hk, KID_MLP3, s, mlp3_sp_kernel<T>, dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s, a.SC(), a.B3(),
-                   p.h16, p.l16, p.l16, w.U, w.stats, w.Z, w.L);
+    with_layout(w, [&](const auto& L) {
+        using LT = std::decay_t<decltype(L)>;
+        allow_big_lds<mlp3_sp_kernel<T, LT>>();
+        GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_sp_kernel<T, LT>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS), (size_t)T::RING_BYTES + 4096, s, a.SC(), a.B3(),
+                       p.h16, p.l16, p.l16, w.U, w.stats, w.Z, L);
+    });
 }
 template <int MODE>
 static void launch_mlp3_sp_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {

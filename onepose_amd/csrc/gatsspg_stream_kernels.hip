@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/gatsspg.h"
 #include "gatsspg_launch.h"
 
@@ -27,21 +29,22 @@ __device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : expm1f(x)
 // ------------------------------------------------------------------------------------------------------
 // state load / store    (GATs_SuperGlue.py:192-193: the .float() descriptors become the GNN state)
 // ------------------------------------------------------------------------------------------------------
+template <class LT = ColLayout>
 __global__ __launch_bounds__(256) void load_state_kernel(const float* __restrict__ dq, const float* __restrict__ d3,
-                                                         float* __restrict__ Z, ColLayout L, int zero_missing) {
+                                                         float* __restrict__ Z, LT L, int zero_missing) {
     // one workgroup per (frame, channel) row; float4 stores (np is a multiple of 128), float4 loads when the
     // source rows are 16-byte aligned (n1, n2 multiples of 4).  A null source leaves its side untouched
     // (zero_missing = 0) or zero-fills it (zero_missing = 1).
     const int ch = blockIdx.x, f = blockIdx.y;
     float* zr = Z + (size_t)ch * L.ld + (size_t)f * L.np;
     const float* q = dq ? dq + ((size_t)f * D + ch) * L.n1 : nullptr;
-    const float* y = d3 ? d3 + ((size_t)f * D + ch) * L.n2 : nullptr;
+    const float* y = d3 ? d3 + ((size_t)db_frame(L, f) * D + ch) * L.n2 : nullptr;
     const bool vec = ((L.n1 | L.n2) & 3) == 0;
     for (int i = threadIdx.x * 4; i < L.np; i += 1024) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool side = i >= L.n1p;
         const int j = side ? i - L.n1p : i;
-        const int n = side ? L.n2 : L.n1;
+        const int n = side ? L.n2 : q_n(L, f);
         const float* src = side ? y : q;
         if (!src) {
             if (!zero_missing) continue;
@@ -72,10 +75,14 @@ __global__ __launch_bounds__(256) void store_state_kernel(const float* __restric
 }
 
 void launch_load_state(const float* dq, const float* d3, const Workspace& w, hipStream_t s, ProfileHook* hk) {
-    GATSSPG_LAUNCH(hk, KID_LOAD_STATE, s, load_state_kernel, dim3(D, w.L.b), dim3(256), 0, s, dq, d3, w.Z, w.L, 1);
+    with_layout(w, [&](const auto& L) {
+        GATSSPG_LAUNCH(hk, KID_LOAD_STATE, s, load_state_kernel<std::decay_t<decltype(L)>>, dim3(D, w.L.b), dim3(256), 0, s, dq, d3, w.Z, L, 1);
+    });
 }
 void launch_load_columns(const float* c2, const float* c3, float* dst, const Workspace& w, hipStream_t s) {
-    hipLaunchKernelGGL(load_state_kernel, dim3(D, w.L.b), dim3(256), 0, s, c2, c3, dst, w.L, 0);
+    with_layout(w, [&](const auto& L) {
+        hipLaunchKernelGGL(load_state_kernel<std::decay_t<decltype(L)>>, dim3(D, w.L.b), dim3(256), 0, s, c2, c3, dst, L, 0);
+    });
 }
 void launch_store_state(const float* src, float* out2d, float* out3d, const Workspace& w, hipStream_t s, ProfileHook*) {
     hipLaunchKernelGGL(store_state_kernel, dim3(D, w.L.b), dim3(256), 0, s, src, out2d, out3d, w.L);
@@ -103,6 +110,7 @@ __device__ __forceinline__ float lrelu02(float x) { return x > 0.f ? x : 0.2f * 
 // query descriptors dq [b,256,n1] into the 2D side of the state (pads zeroed) and zero the 3D-side pad columns --
 // what load_state_kernel would have done in a launch of its own.
 constexpr int GATS_COPY_BLOCKS = 64;   // 4 channel rows each
+constexpr int GATS_SHARED_GROUP = 4;   // frames per workgroup of the shared-leaf form (gats_leaf8x4_shared_kernel)
 
 // leaf logits of one lane: its 4 leaves x its 8 channel rows, then over the 8 row lanes (lane bits 3..5) with two halving
 // exchanges and one butterfly step: afterwards a lane holds leaf ((lane >> 3) & 1) * 2 + ((lane >> 4) & 1) of its 16-byte
@@ -127,10 +135,10 @@ __device__ __forceinline__ int leaf_logit_slot(int lane) { return (lane & 7) * 4
 
 // CACHED_LOGITS: the leaf logits come from the per-object cache `cl` ([tiles][32] floats of this frame and layer) instead of
 // being recomputed from the leaves (amortised mode)
-template <bool FUSED_LOAD, bool CACHED_LOGITS>
+template <bool FUSED_LOAD, bool CACHED_LOGITS, class LT = ColLayout>
 __global__ __launch_bounds__(256, 7) void gats_leaf8x4_kernel(const float* __restrict__ u1, const float* __restrict__ u2,
                                                            const float* __restrict__ leaves, const float* Z, float* dst,
-                                                           ColLayout L, int flags, int raw_out, int ntiles,
+                                                           LT L, int flags, int raw_out, int ntiles,
                                                            const float* __restrict__ h3, const float* __restrict__ dq,
                                                            const float* __restrict__ cl) {
     __shared__ __attribute__((aligned(16))) float hs[D * 4];
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(256, 7) void gats_leaf8x4_kernel(const float* __res
     const int n0 = tile * 4;
     const int pv = min(4, L.n2 - n0);
     const size_t lrow = (size_t)L.n2 * 8;
-    const float* Lf = leaves + (size_t)f * D * lrow + (size_t)n0 * 8;
+    const float* Lf = leaves + (size_t)db_frame(L, f) * D * lrow + (size_t)n0 * 8;
     const size_t ycol = (size_t)f * L.np + L.n1p + n0;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r = lane >> 3, c4 = lane & 7;
@@ -193,7 +201,7 @@ __global__ __launch_bounds__(256, 7) void gats_leaf8x4_kernel(const float* __res
     }
     const float u2v = u2[tid];
     float clv = 0.f;
-    if (CACHED_LOGITS && tid < 32) clv = cl[((size_t)f * ntiles + tile) * 32 + tid];
+    if (CACHED_LOGITS && tid < 32) clv = cl[((size_t)db_frame(L, f) * ntiles + tile) * 32 + tid];
     // UNCONDITIONAL loads: lanes of points beyond n2 (last tile only) re-read point 0 of the tile -- finite values whose
     // results are never stored.  (A `valid ? load : 0` form compiles to exec-masked branches with an s_waitcnt vmcnt(0)
     // in the middle of the sequence: the 8 loads of a lane were in flight 3 + 5 instead of 8 at a time.)
@@ -288,6 +296,130 @@ __global__ __launch_bounds__(256, 7) void gats_leaf8x4_kernel(const float* __res
     }
 }
 
+// Shared-leaf form for a frames layout (gatsspg_forward_frames: every frame runs against the SAME leaves): one workgroup reads its 4-point
+// leaf tile ONCE -- the 8 float4 of a lane stay in registers, the leaf logits (cached, or computed once: they do not depend on the frame)
+// stay in LDS -- and loops over a group of G frames: per frame it loads h, forms s3, the softmax over the 1 + 8 logits and the
+// coefficients, and writes the frame's columns.  Tile, lane mapping, reduction order and every expression are those of
+// gats_leaf8x4_kernel, so a frame's columns are bit for bit what that kernel writes.  num_leaf == 8 without the linear transform only.
+// The h tiles of the whole group are requested up front (G float4 per thread), in front of the leaves.
+template <int G, bool CACHED_LOGITS>
+__global__ __launch_bounds__(256, 6) void gats_leaf8x4_shared_kernel(const float* __restrict__ u1, const float* __restrict__ u2,
+                                                                   const float* __restrict__ leaves, const float* Z, float* dst,
+                                                                   ColLayout L, int flags, int ntiles, const float* __restrict__ cl) {
+    __shared__ __attribute__((aligned(16))) float hs[D * 4];
+    __shared__ __attribute__((aligned(16))) float pre[D * 4];
+    __shared__ float red3[4][4];
+    __shared__ float redl[4][32];
+    __shared__ float coef[4][9];
+    const int f0 = blockIdx.y * G;
+    const int nf = min(G, L.b - f0);
+    int tile;
+    {
+        const int g = blockIdx.x, xcd = g & 7, q = ntiles >> 3, r = ntiles & 7;
+        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (g >> 3);
+    }
+    const int n0 = tile * 4;
+    const int pv = min(4, L.n2 - n0);
+    const size_t lrow = (size_t)L.n2 * 8;
+    const float* Lf = leaves + (size_t)n0 * 8;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = lane >> 3, c4 = lane & 7;
+    const int pt = c4 >> 1, lh = c4 & 1;
+    const bool valid = pt < pv;
+    float4 a[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {   // (frames past the group's end re-read its first frame: in bounds, never used)
+        const size_t ycol = (size_t)(g < nf ? f0 + g : f0) * L.np + L.n1p + n0;
+        a[g] = *reinterpret_cast<const float4*>(Z + (size_t)tid * L.ld + ycol);
+    }
+    const float u2v = u2[tid];
+    float clv = 0.f;
+    if (CACHED_LOGITS && tid < 32) clv = cl[(size_t)tile * 32 + tid];
+    const int c4l = valid ? c4 : (c4 & 1);
+    float4 v[8];
+    float u1r[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const int ch = p * 32 + w * 8 + r;
+        v[p] = *reinterpret_cast<const float4*>(Lf + (size_t)ch * lrow + 4 * c4l);
+        u1r[p] = CACHED_LOGITS ? 0.f : u1[ch];
+    }
+    if (CACHED_LOGITS) {
+        if (tid < 32) redl[0][tid] = clv;
+    } else {
+        const float s = leaf_logit_wave_partial(v, u1r, lane);
+        if (lane < 32) redl[w][leaf_logit_slot(lane)] = s;
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (g >= nf) break;   // block-uniform
+        const size_t ycol = (size_t)(f0 + g) * L.np + L.n1p + n0;
+        {
+            *reinterpret_cast<float4*>(hs + tid * 4) = a[g];
+            const float p0 = a[g].x * u2v, p1 = a[g].y * u2v, p2 = a[g].z * u2v, p3 = a[g].w * u2v;
+            const bool b0 = lane & 1, b1 = lane & 2;
+            float k0 = b0 ? p2 : p0, k1 = b0 ? p3 : p1;
+            k0 += __shfl_xor(b0 ? p0 : p2, 1);
+            k1 += __shfl_xor(b0 ? p1 : p3, 1);
+            float s = b1 ? k1 : k0;
+            s += __shfl_xor(b1 ? k0 : k1, 2);
+#pragma unroll
+            for (int o = 4; o <= 32; o <<= 1) s += __shfl_xor(s, o);
+            if (lane < 4) red3[w][(lane & 1) * 2 + (lane >> 1)] = s;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            const int include_self = flags & GATSSPG_FLAG_INCLUDE_SELF;
+            const int p4 = lane >> 4, j = lane & 15;
+            const bool in = j < 9 && (j > 0 || include_self);
+            const float s3 = (red3[0][p4] + red3[1][p4]) + (red3[2][p4] + red3[3][p4]);
+            const int c = p4 * 8 + min(max(j - 1, 0), 7);
+            const float ll = CACHED_LOGITS ? redl[0][c] : (redl[0][c] + redl[1][c]) + (redl[2][c] + redl[3][c]);
+            const float e = lrelu02(s3 + (j == 0 ? s3 : ll));
+            float m = in ? e : -3.0e38f;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+            const float ex = in ? expf(e - m) : 0.f;
+            float sum = 0.f;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) sum += __shfl(ex, (lane & 48) + k);
+            if (j < 9) {
+                float cf;
+                if (include_self) cf = ex / sum + (j == 0 && (flags & GATSSPG_FLAG_ADDITIONAL) ? 1.f : 0.f);
+                else cf = j == 0 ? 1.f : (ex / sum) / 2.f;
+                coef[p4][j] = cf;
+            }
+        }
+        __syncthreads();
+        const float cj0 = coef[pt][1 + lh * 4 + 0], cj1 = coef[pt][1 + lh * 4 + 1];
+        const float cj2 = coef[pt][1 + lh * 4 + 2], cj3 = coef[pt][1 + lh * 4 + 3];
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int ch = p * 32 + w * 8 + r;
+            float part = ((cj0 * v[p].x + cj1 * v[p].y) + (cj2 * v[p].z + cj3 * v[p].w));
+            part += __shfl_xor(part, 1);
+            if (lh == 0) pre[ch * 4 + pt] = part;
+        }
+        __syncthreads();
+        {
+            const float4 pr = *reinterpret_cast<const float4*>(pre + tid * 4);
+            const float4 h4 = *reinterpret_cast<const float4*>(hs + tid * 4);
+            float o0 = coef[0][0] * h4.x + pr.x, o1 = coef[1][0] * h4.y + pr.y, o2 = coef[2][0] * h4.z + pr.z, o3 = coef[3][0] * h4.w + pr.w;
+            o0 = elu_f(o0); o1 = elu_f(o1); o2 = elu_f(o2); o3 = elu_f(o3);
+            float* o = dst + (size_t)tid * L.ld + ycol;
+            if (pv == 4) {
+                *reinterpret_cast<float4*>(o) = make_float4(o0, o1, o2, o3);
+            } else {
+                o[0] = o0;
+                if (pv > 1) o[1] = o1;
+                if (pv > 2) o[2] = o2;
+            }
+        }
+        // (the next frame overwrites hs / red3 in front of its first barrier, coef and pre behind it: hs is read by its own writer only,
+        //  red3's readers are two barriers back)
+    }
+}
+
 // Per-object leaf-logit cache: the logits leaf . u1 of GATs layers `first_layer` .. `first_layer + nlayers - 1` depend only
 // on the database (the leaves never change, GATs_SuperGlue.py:53-54), so gatsspg_prepare_database computes them once with
 // the layer kernel's own thread mapping and reduction order.  cl: [nlayers][b][tiles][32] floats.
@@ -332,16 +464,17 @@ __device__ __forceinline__ float block_sum_256(float x, float* scratch) {
     return (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
 }
 
+template <class LT = ColLayout>
 __global__ __launch_bounds__(256) void gats_generic_kernel(const float* __restrict__ u1, const float* __restrict__ u2,
                                                            const float* __restrict__ leaves, const float* Z,
-                                                           float* dst, ColLayout L, int nl, int flags,
+                                                           float* dst, LT L, int nl, int flags,
                                                            int raw_out) {
     __shared__ float scratch[4];
     __shared__ float sl[GATS_MAXL];
     __shared__ float coef[GATS_MAXL + 1];
     const int f = blockIdx.y, ch = threadIdx.x;
     const size_t lrow = (size_t)L.n2 * nl;
-    const float* Lr = leaves + ((size_t)f * D + ch) * lrow;
+    const float* Lr = leaves + ((size_t)db_frame(L, f) * D + ch) * lrow;
     const float u1v = u1[ch], u2v = u2[ch];
     const int include_self = flags & GATSSPG_FLAG_INCLUDE_SELF;
     for (int pt = 0; pt < 4; ++pt) {
@@ -407,22 +540,34 @@ void launch_gats(const GatsLayer& g, const float* leaves, int num_leaf, int flag
                  ProfileHook* hk, const float* h3, const float* dq, const float* cl) {
     const float *u1 = g.U1(), *u2 = g.U2();
     const int raw_out = (flags & GATSSPG_FLAG_WITH_LINEAR_TRANSFORM) ? 1 : 0;
-    if (num_leaf == 8) {
+    if (num_leaf == 8 && w.frames && w.shared_leaf && !raw_out && !h3) {
+        const int nt = (w.L.n2 + 3) / 4;
+        constexpr int G = GATS_SHARED_GROUP;
+        const dim3 grid(nt, (w.L.b + G - 1) / G);
+        if (cl) GATSSPG_LAUNCH(hk, KID_GATS, s, (gats_leaf8x4_shared_kernel<G, true>), grid, dim3(256), 0, s, u1, u2, leaves, w.Z, dst, w.L, flags, nt, cl);
+        else GATSSPG_LAUNCH(hk, KID_GATS, s, (gats_leaf8x4_shared_kernel<G, false>), grid, dim3(256), 0, s, u1, u2, leaves, w.Z, dst, w.L, flags, nt, cl);
+    } else if (num_leaf == 8) {
         const int nt = (w.L.n2 + 3) / 4;
         const int extra = h3 ? GATS_COPY_BLOCKS : 0;
         // (capping the residency -- fewer, staggered rounds of workgroups -- was measured: no gain at 4-5 per CU, worse below)
-        if (h3)
+        if (h3)   // (never on a frames layout: the cached chain loads the state itself)
             GATSSPG_LAUNCH(hk, KID_GATS, s, (gats_leaf8x4_kernel<true, false>), dim3(nt + extra, w.L.b), dim3(256), 0, s, u1, u2,
                            leaves, w.Z, dst, w.L, flags, raw_out, nt, h3, dq, cl);
         else if (cl)
-            GATSSPG_LAUNCH(hk, KID_GATS, s, (gats_leaf8x4_kernel<false, true>), dim3(nt, w.L.b), dim3(256), 0, s, u1, u2, leaves,
-                           w.Z, dst, w.L, flags, raw_out, nt, h3, dq, cl);
+            with_layout(w, [&](const auto& L) {
+                GATSSPG_LAUNCH(hk, KID_GATS, s, (gats_leaf8x4_kernel<false, true, std::decay_t<decltype(L)>>), dim3(nt, w.L.b), dim3(256), 0, s, u1, u2,
+                               leaves, w.Z, dst, L, flags, raw_out, nt, h3, dq, cl);
+            });
         else
-            GATSSPG_LAUNCH(hk, KID_GATS, s, (gats_leaf8x4_kernel<false, false>), dim3(nt, w.L.b), dim3(256), 0, s, u1, u2, leaves,
-                           w.Z, dst, w.L, flags, raw_out, nt, h3, dq, cl);
+            with_layout(w, [&](const auto& L) {
+                GATSSPG_LAUNCH(hk, KID_GATS, s, (gats_leaf8x4_kernel<false, false, std::decay_t<decltype(L)>>), dim3(nt, w.L.b), dim3(256), 0, s, u1, u2,
+                               leaves, w.Z, dst, L, flags, raw_out, nt, h3, dq, cl);
+            });
     } else {
-        GATSSPG_LAUNCH(hk, KID_GATS, s, gats_generic_kernel, dim3((w.L.n2 + 3) / 4, w.L.b), dim3(256), 0, s, u1, u2, leaves,
-                       w.Z, dst, w.L, num_leaf, flags, raw_out);
+        with_layout(w, [&](const auto& L) {
+            GATSSPG_LAUNCH(hk, KID_GATS, s, gats_generic_kernel<std::decay_t<decltype(L)>>, dim3((w.L.n2 + 3) / 4, w.L.b), dim3(256), 0, s, u1, u2,
+                           leaves, w.Z, dst, L, num_leaf, flags, raw_out);
+        });
     }
 }
 
@@ -452,13 +597,13 @@ constexpr int CF_NQ = CF_COLS / 256;
 // SMALL: at most 8 row partials per range (nct <= 128, i.e. n2 <= 8192) and one column partial per range (nrt <= 16, n1 <=
 // 2048): the prologue is then straight-line code whose loads are all issued up front.  Larger problems take the looped
 // prologue (hipcc drains every outstanding load -- the rows too -- in front of a loop that contains loads).
-template <bool VEC, bool SHIFTED, bool SMALL>
+template <bool VEC, bool SHIFTED, bool SMALL, class LT = ColLayout>
 __global__ __launch_bounds__(256) void conf_finalize_kernel(float* __restrict__ conf, const float* __restrict__ rowpart,
                                                             const float* __restrict__ colpart, const float* __restrict__ rs_g,
                                                             const float* __restrict__ cs_g, const float* __restrict__ rshift,
                                                             const float* __restrict__ cshift, float* __restrict__ rmax_v,
                                                             int* __restrict__ rmax_i, float* __restrict__ cmax_v,
-                                                            int* __restrict__ cmax_i, ColLayout L, int nct, int nrt, int nch,
+                                                            int* __restrict__ cmax_i, LT L, int nct, int nrt, int nch,
                                                             int nst) {
     __shared__ __attribute__((aligned(16))) float cs_s[CF_COLS];
     __shared__ __attribute__((aligned(16))) float csh_s[SHIFTED ? CF_COLS : 4];
@@ -469,7 +614,16 @@ __global__ __launch_bounds__(256) void conf_finalize_kernel(float* __restrict__ 
     const int chk = blockIdx.x, st = blockIdx.y, f = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i0 = st * CF_ROWS, j0 = chk * CF_COLS;
-    const int nrows = min(CF_ROWS, L.n1 - i0);
+    // frames layout: the frame's own rows and its own count of column partials (what it has alone); nrt stays their stride.  Set and read
+    // only under is_frames<LT>, and the choice is spelled out at each use ON PURPOSE: with one local in front of the prologue
+    // (nrt_own = frames ? nrtf : nrt) five of the uniform instantiations moved by 2-3 SGPRs against the parent (Resources).
+    int n1f, nrtf;
+    if constexpr (is_frames<LT>) {
+        n1f = L.cnt[f];
+        nrtf = round_up(n1f, CP) / SC_BM;
+        if (n1f <= i0) return;   // a strip past the frame's own rows: nothing to read, nothing to leave
+    }
+    const int nrows = min(CF_ROWS, (is_frames<LT> ? n1f : L.n1) - i0);
     float* cf = conf + (size_t)f * L.n1 * L.n2;
 
     // Load order = wait order (loads retire in order): first the partials of the normalisers into registers, then this wave's
@@ -482,7 +636,7 @@ __global__ __launch_bounds__(256) void conf_finalize_kernel(float* __restrict__ 
     const int pc_jl = 4 * tid, pc_j = j0 + pc_jl;                  // column partials: 4 consecutive columns per thread
     const bool pc_on = pc_jl < CF_COLS && pc_j < L.n2p;            // n2p is a multiple of 128: all four in bounds
     const float* pc_src = colpart + (size_t)f * nrt * L.n2p + pc_j;
-    const int pc_per = (nrt + 15) / 16;
+    const int pc_per = ((is_frames<LT> ? nrtf : nrt) + 15) / 16;
     float xr[8];
     float4 xc[16];
     if constexpr (!SHIFTED && SMALL) {
@@ -494,7 +648,7 @@ __global__ __launch_bounds__(256) void conf_finalize_kernel(float* __restrict__ 
         for (int u = 0; u < 8; ++u) xr[u] = pr_row[(size_t)min(pr_tb + u, nct - 1) * L.n1p];
         const float* pc_col = colpart + (size_t)f * nrt * L.n2p + min(pc_j, L.n2p - 4);
 #pragma unroll
-        for (int t = 0; t < 16; ++t) xc[t] = *reinterpret_cast<const float4*>(pc_col + (size_t)min(t, nrt - 1) * L.n2p);
+        for (int t = 0; t < 16; ++t) xc[t] = *reinterpret_cast<const float4*>(pc_col + (size_t)min(t, (is_frames<LT> ? nrtf : nrt) - 1) * L.n2p);
     }
     float e[4][CF_NQ][4];
 #pragma unroll
@@ -537,12 +691,12 @@ __global__ __launch_bounds__(256) void conf_finalize_kernel(float* __restrict__ 
                     c = xc[0];
 #pragma unroll
                     for (int t = 1; t < 16; ++t)
-                        if (t < nrt) { c.x += xc[t].x; c.y += xc[t].y; c.z += xc[t].z; c.w += xc[t].w; }
+                        if (t < (is_frames<LT> ? nrtf : nrt)) { c.x += xc[t].x; c.y += xc[t].y; c.z += xc[t].z; c.w += xc[t].w; }
                 }
             } else if (pc_on) {
                 {
                     for (int r = 0; r < 16; ++r) {
-                        const int tb = r * pc_per, te = min(nrt, tb + pc_per);
+                        const int tb = r * pc_per, te = min((is_frames<LT> ? nrtf : nrt), tb + pc_per);
                         float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
                         for (int t = tb; t < te; ++t) {
                             const float4 x = *reinterpret_cast<const float4*>(pc_src + (size_t)t * L.n2p);
@@ -675,11 +829,12 @@ __global__ __launch_bounds__(256) void conf_finalize_kernel(float* __restrict__ 
 // (ranges in order, combined in order), so the dependent-load chains are nst / 8 long.
 constexpr int MT_ITEMS = 32;
 
+template <class LT = ColLayout>
 __global__ __launch_bounds__(256) void match_tail_kernel(const float* __restrict__ rmax_v, const int* __restrict__ rmax_i,
                                                          const float* __restrict__ cmax_v, const int* __restrict__ cmax_i,
                                                          float thr, int64_t* __restrict__ matches0,
                                                          int64_t* __restrict__ matches1, float* __restrict__ ms0,
-                                                         float* __restrict__ ms1, ColLayout L, int nch, int nst) {
+                                                         float* __restrict__ ms1, LT L, int nch, int nst_launch) {
     __shared__ float pv[8][MT_ITEMS];
     __shared__ int pi[8][MT_ITEMS];
     __shared__ float rowv[MT_ITEMS];
@@ -690,8 +845,9 @@ __global__ __launch_bounds__(256) void match_tail_kernel(const float* __restrict
     const int base = (rows ? (int)blockIdx.x : (int)blockIdx.x - nrb) * MT_ITEMS;
     const float* rv = rmax_v + (size_t)f * nch * L.n1p;
     const int* ri = rmax_i + (size_t)f * nch * L.n1p;
-    const float* cv = cmax_v + (size_t)f * nst * L.n2p;
-    const int* ci = cmax_i + (size_t)f * nst * L.n2p;
+    const float* cv = cmax_v + (size_t)f * nst_launch * L.n2p;
+    const int* ci = cmax_i + (size_t)f * nst_launch * L.n2p;
+    const int nst = q_parts(L, f, CF_ROWS, nst_launch);   // strips that conf_finalize wrote for this frame
     // first maximum over partials [tb, te) spaced `stride` apart, 8 loads in flight at a time
     auto argpart = [&](const float* pvv, const int* pii, size_t stride, int tb, int te, float& v) {
         v = -INFINITY;
@@ -728,7 +884,14 @@ __global__ __launch_bounds__(256) void match_tail_kernel(const float* __restrict
     };
     if (rows) {
         const int i = base + it;
-        const bool live = i < L.n1;
+        const bool live = i < q_n(L, f);
+        if constexpr (is_frames<LT>) {   // rows between the frame's count and the capacity: no match
+            if (grp == 0 && !live && i < L.n1) {
+                matches0[(size_t)f * L.n1 + i] = (int64_t)-1;
+                ms0[(size_t)f * L.n1 + i] = 0.f;
+            }
+            if (base >= q_n(L, f)) return;   // block-uniform
+        }
         if (grp == 0) {
             float v = 0.f;
             const int j = live ? rowarg(i, v) : 0;
@@ -768,10 +931,14 @@ __global__ __launch_bounds__(256) void match_tail_kernel(const float* __restrict
 
 // ---- max-subtracting softmax statistics of the raw score matrix S (only when 1 / scale_factor > 80; off the benchmarked
 //      path, simple kernels): per row i  rshift = max_j S_ij, rs = sum_j exp(S_ij - rshift); per column likewise ----
+template <class LT = ColLayout>
 __global__ __launch_bounds__(256) void softmax_rowstat_kernel(const float* __restrict__ S, float* __restrict__ rshift,
-                                                              float* __restrict__ rs, ColLayout L) {
+                                                              float* __restrict__ rs, LT L) {
     __shared__ float red[256];
     const int i = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+    if constexpr (is_frames<LT>) {
+        if (i >= q_n(L, f)) return;
+    }
     const float* row = S + ((size_t)f * L.n1 + i) * L.n2;
     float m = -INFINITY;
     for (int j = tid; j < L.n2; j += 256) m = fmaxf(m, row[j]);
@@ -797,34 +964,36 @@ __global__ __launch_bounds__(256) void softmax_rowstat_kernel(const float* __res
     }
 }
 
+template <class LT = ColLayout>
 __global__ __launch_bounds__(256) void softmax_colstat_kernel(const float* __restrict__ S, float* __restrict__ cshift,
-                                                              float* __restrict__ cs, ColLayout L) {
+                                                              float* __restrict__ cs, LT L) {
     const int j = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
     if (j >= L.n2) return;
     const float* col = S + (size_t)f * L.n1 * L.n2 + j;
     float m = -INFINITY;
-    for (int i = 0; i < L.n1; ++i) m = fmaxf(m, col[(size_t)i * L.n2]);
+    const int n1 = q_n(L, f);
+    for (int i = 0; i < n1; ++i) m = fmaxf(m, col[(size_t)i * L.n2]);
     float s = 0.f;
-    for (int i = 0; i < L.n1; ++i) s += expf(col[(size_t)i * L.n2] - m);
+    for (int i = 0; i < n1; ++i) s += expf(col[(size_t)i * L.n2] - m);
     cshift[(size_t)f * L.n2p + j] = m;
     cs[(size_t)f * L.n2p + j] = s;
 }
 
-void launch_dual_softmax_match(const Workspace& w, const MatchOut& out, int shifted, float thr, hipStream_t s, ProfileHook* hk) {
-    const ColLayout& L = w.L;
+template <class LT>
+static void launch_dual_softmax_match_t(const Workspace& w, const LT& L, const MatchOut& out, int shifted, float thr, hipStream_t s, ProfileHook* hk) {
     float* conf = out.conf;
     const dim3 gf(w.cf_nch, w.cf_nst, L.b);
     const int nrt = (L.n1p + score_tile_rows() - 1) / score_tile_rows();
     const int nct = L.n2p / score_tile_cols();
     const bool vec = (L.n2 & 3) == 0 && (reinterpret_cast<uintptr_t>(conf) & 15) == 0;
     if (shifted) {
-        GATSSPG_LAUNCH(hk, KID_SOFTMAX_STATS, s, softmax_rowstat_kernel, dim3(L.n1, L.b), dim3(256), 0, s, conf, w.rshift, w.rs, L);
-        GATSSPG_LAUNCH(hk, KID_SOFTMAX_STATS, s, softmax_colstat_kernel, dim3((L.n2 + 255) / 256, L.b), dim3(256), 0, s, conf,
+        GATSSPG_LAUNCH(hk, KID_SOFTMAX_STATS, s, softmax_rowstat_kernel<LT>, dim3(L.n1, L.b), dim3(256), 0, s, conf, w.rshift, w.rs, L);
+        GATSSPG_LAUNCH(hk, KID_SOFTMAX_STATS, s, softmax_colstat_kernel<LT>, dim3((L.n2 + 255) / 256, L.b), dim3(256), 0, s, conf,
                        w.cshift, w.cs, L);
     }
     const bool small = nct <= 128 && nrt <= 16;
 #define GATSSPG_FINALIZE(VEC_, SH_, SM_)                                                                                     \
-    GATSSPG_LAUNCH(hk, KID_CONF_FINALIZE, s, (conf_finalize_kernel<VEC_, SH_, SM_>), gf, dim3(256), 0, s, conf, w.rowpart,    \
+    GATSSPG_LAUNCH(hk, KID_CONF_FINALIZE, s, (conf_finalize_kernel<VEC_, SH_, SM_, LT>), gf, dim3(256), 0, s, conf, w.rowpart,    \
                    w.colpart, w.rs, w.cs, w.rshift, w.cshift, w.rmax_v, w.rmax_i, w.cmax_v, w.cmax_i, L, nct, nrt,            \
                    w.cf_nch, w.cf_nst)
     if (vec && !shifted && small) GATSSPG_FINALIZE(true, false, true);
@@ -835,8 +1004,11 @@ void launch_dual_softmax_match(const Workspace& w, const MatchOut& out, int shif
     else GATSSPG_FINALIZE(false, true, true);
 #undef GATSSPG_FINALIZE
     const dim3 g1((L.n1p + L.n2p) / MT_ITEMS, L.b);
-    GATSSPG_LAUNCH(hk, KID_MATCH_TAIL, s, match_tail_kernel, g1, dim3(256), 0, s, w.rmax_v, w.rmax_i, w.cmax_v, w.cmax_i, thr,
+    GATSSPG_LAUNCH(hk, KID_MATCH_TAIL, s, match_tail_kernel<LT>, g1, dim3(256), 0, s, w.rmax_v, w.rmax_i, w.cmax_v, w.cmax_i, thr,
                    out.matches0, out.matches1, out.mscores0, out.mscores1, L, w.cf_nch, w.cf_nst);
+}
+void launch_dual_softmax_match(const Workspace& w, const MatchOut& out, int shifted, float thr, hipStream_t s, ProfileHook* hk) {
+    with_layout(w, [&](const auto& L) { launch_dual_softmax_match_t(w, L, out, shifted, thr, s, hk); });
 }
 
 // ------------------------------------------------------------------------------------------------------

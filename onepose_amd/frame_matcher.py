@@ -53,27 +53,65 @@ class FrameMatcher:
         pose, mask, info = pnp.ransac_pnp_from_matches(K_crop, kpts2d, self.db["keypoints3d"][0], pred["matches0"], scale=scale, seed=seed)
         return pose, mask, info, det
 
+    def _single(self, det):
+        """One frame through the matcher's single-frame path (pack_data :80-94, :146): (matches0, matching_scores0)."""
+        kpts2d = det["keypoints"][0]
+        inp = {"keypoints2d": kpts2d[None], "keypoints3d": self.db["keypoints3d"],
+               "descriptors2d_query": det["descriptors"][0][None].contiguous(), "descriptors3d_db": self.db["descriptors3d_db"],
+               "descriptors2d_db": self.db["descriptors2d_db"]}
+        pred, _ = self.matcher(inp, database=self.db_cache) if self.db_cache is not None else self.matcher(inp)
+        return pred["matches0"].reshape(-1), pred["matching_scores0"].reshape(-1)
+
+    def _match_dets(self, dets):
+        """(matches0, matching_scores0) per extractor output: the frames with at least 2 keypoints through ONE ragged matcher batch
+        against the resident database (``GATsSuperGlue.match_frames``: each frame bitwise its own single-frame forward), the others
+        stay out of the batch and are answered -- or refused -- by the single-frame path exactly as without it."""
+        if self.db_cache is None:
+            raise RuntimeError("the batched matcher needs the resident database cache (cache_database=True)")
+        out = [None] * len(dets)
+        batch = [i for i, d in enumerate(dets) if d["keypoints"][0].shape[0] >= 2]
+        preds = self.matcher.match_frames([dets[i]["descriptors"][0] for i in batch], self.db_cache) if batch else []
+        for i, p in zip(batch, preds):
+            out[i] = (p["matches0"], p["matching_scores0"])
+        for i, det in enumerate(dets):
+            if out[i] is None:
+                out[i] = self._single(det)
+        return out
+
     @torch.no_grad()
-    def solve_poses_device(self, images, K_crops, scale=1000, seeds=0):
+    def match_frames(self, images):
+        """A list (or [B,1,H,W] batch) of crops of this object -> one dict per frame, each what ``__call__`` returns for it.  The
+        extractor runs frame by frame, the matcher ONCE over all frames (``_match_dets``)."""
+        frames = [images[i:i + 1] for i in range(images.shape[0])] if isinstance(images, torch.Tensor) else list(images)
+        dets = [self.extractor(image) for image in frames]
+        out = []
+        for det, (matches, conf) in zip(dets, self._match_dets(dets)):
+            kpts2d = det["keypoints"][0]
+            valid = matches > -1
+            out.append({"mkpts2d": kpts2d[valid], "mkpts3d": self.db["keypoints3d"][0][matches[valid]], "mconf": conf[valid],
+                        "keypoints2d": kpts2d, "matches0": matches})
+        return out
+
+    @torch.no_grad()
+    def solve_poses_device(self, images, K_crops, scale=1000, seeds=0, batched_matcher=None):
         """A list (or [B,1,H,W] batch) of crops -> (poses [B,3,4] float64, masks [B,cap1] per query keypoint, infos [B,4],
-        detections), all left on the GPU.  Extractor and matcher run frame by frame exactly as in ``solve_pose_device`` (each frame
-        keeps its own keypoint count); their keypoints and matches go into padded [B, cap1] buffers, cap1 the largest count, and ONE
-        batched solve (``pnp_ransac_epnp_matches_batch``) answers all frames: frame i bitwise as ``solve_pose_device`` answers it with
-        ``K_crops[i]`` and ``seeds[i]``.  K_crops: [3,3] or B of them; seeds: an int or B ints."""
+        detections), all left on the GPU.  The extractor runs frame by frame exactly as in ``solve_pose_device`` (each frame
+        keeps its own keypoint count), the matcher once over all frames (below); the keypoints and matches go into padded [B, cap1]
+        buffers, cap1 the largest count, and ONE batched solve (``pnp_ransac_epnp_matches_batch``) answers all frames: frame i
+        bitwise as ``solve_pose_device`` answers it with ``K_crops[i]`` and ``seeds[i]``.  K_crops: [3,3] or B of them; seeds: an
+        int or B ints.
+        batched_matcher: True = the matcher runs ONCE over all frames (``_match_dets``: one ragged frame batch against the resident
+        database; needs the database cache), False = frame by frame as in ``solve_pose_device``; the outputs are the same bit for
+        bit.  Default (None): batched whenever the database cache exists -- from 4 frames on the batch is 1.2x to 2.9x the loop's
+        matcher throughput."""
         from . import pnp
         frames = [images[i:i + 1] for i in range(images.shape[0])] if isinstance(images, torch.Tensor) else list(images)
         if not frames:
             raise ValueError("solve_poses_device needs at least one image")
-        dets, matches = [], []
-        for image in frames:
-            det = self.extractor(image)
-            kpts2d = det["keypoints"][0]
-            inp = {"keypoints2d": kpts2d[None], "keypoints3d": self.db["keypoints3d"],
-                   "descriptors2d_query": det["descriptors"][0][None].contiguous(), "descriptors3d_db": self.db["descriptors3d_db"],
-                   "descriptors2d_db": self.db["descriptors2d_db"]}
-            pred, _ = self.matcher(inp, database=self.db_cache) if self.db_cache is not None else self.matcher(inp)
-            dets.append(det)
-            matches.append(pred["matches0"].reshape(-1))
+        if batched_matcher is None:
+            batched_matcher = self.db_cache is not None
+        dets = [self.extractor(image) for image in frames]
+        matches = [m for m, _ in (self._match_dets(dets) if batched_matcher else [self._single(det) for det in dets])]
         counts = [d["keypoints"][0].shape[0] for d in dets]
         dev = dets[0]["keypoints"][0].device
         cap1 = max(max(counts), 1)

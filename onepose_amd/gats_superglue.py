@@ -120,6 +120,32 @@ class KeypointEncoder(nn.Module):
         return out
 
 
+def pack_frames(queries, out=None):
+    """Per-frame descriptor tensors ([256, n_i] or [1, 256, n_i]) -> (dq [b, 256, cap1], counts): frame i in columns [0, n_i) of
+    its slab, cap1 the largest count.  The columns behind a count are left UNINITIALISED on purpose (``torch.empty``): the frame
+    forward never reads them.  ``out``: a [b, 256, >= cap1] buffer to fill instead."""
+    qs = [q[0] if q.dim() == 3 else q for q in queries]
+    if not qs:
+        raise ValueError("pack_frames needs at least one frame")
+    for q in qs:
+        if q.dim() != 2 or q.shape[0] != D:
+            raise ValueError(f"descriptors must be [256, n] or [1, 256, n] (got {list(q.shape)})")
+    counts = [int(q.shape[1]) for q in qs]
+    if out is None:
+        out = torch.empty(len(qs), D, max(counts), device=qs[0].device, dtype=torch.float32)
+    for i, q in enumerate(qs):
+        out[i, :, :counts[i]] = q
+    return out, counts
+
+
+def trim_frames(out, counts):
+    """The outputs of ``forward_frames`` per frame, trimmed to the counts: a list of dicts with ``conf`` [n_i, n2] (a VIEW of the batch
+    buffer), ``matches0`` / ``matching_scores0`` [n_i], ``matches1`` / ``matching_scores1`` [n2]."""
+    conf, m0, m1, s0, s1 = out
+    return [{"conf": conf[i, :n], "matches0": m0[i, :n], "matches1": m1[i], "matching_scores0": s0[i, :n], "matching_scores1": s1[i]}
+            for i, n in enumerate(counts)]
+
+
 _NO_CPU = ("onepose_amd.GATsSuperGlue runs only on a ROCm GPU (tensor '{}' is on {}); "
            "there is no CPU fallback -- move the module and its inputs to the GPU")
 
@@ -140,7 +166,12 @@ class Database:
         self.ready = torch.cuda.Event()
         self.ready.record(torch.cuda.current_stream(cache.device))
 
-    def check(self, engine, b, n2, num_leaf, device):
+    def check(self, engine, b, n2, num_leaf, device, frames=False):
+        """``frames``: the cache is consumed by ``b`` frames at once (``forward_frames``), which takes a ``b = 1`` cache."""
+        if frames and self.b != 1:
+            raise ValueError(f"a frame batch runs against ONE database: the cache must be prepared with b=1 (this one has b={self.b})")
+        if frames:
+            b = 1
         if (b, n2, num_leaf) != (self.b, self.n2, self.num_leaf) or self.cache.device != device:
             raise ValueError(f"database cache was built for b={self.b} n2={self.n2} num_leaf={self.num_leaf} on "
                              f"{self.cache.device}; got b={b} n2={n2} num_leaf={num_leaf} on {device}")
@@ -248,6 +279,26 @@ class GATsSPGEngine(Engine):
                       float(match_threshold), *out, ws, ws.numel())
         return out
 
+    def forward_frames(self, dq, counts, database, scale_factor, match_threshold, out=None):
+        """``b <= MAX_FRAMES`` frames with their own query counts against ONE database in one chain of launches
+        (``gatsspg_forward_frames``).  dq [b,256,cap1]: frame i in columns [0, counts[i]); counts: b host ints; database: a ``b = 1``
+        handle of prepare_database.  Returns (conf [b,cap1,n2], matches0 [b,cap1], matches1 [b,n2], mscores0, mscores1); frame i is
+        bitwise ``forward(dq[i:i+1, :, :counts[i]], ..., database)``, conf rows at or past counts[i] are not written.  ``out``: the
+        five output tensors to write into (default: fresh ones)."""
+        b, _, cap1 = dq.shape
+        counts = [int(c) for c in counts]
+        if len(counts) != b:
+            raise ValueError(f"{b} frames but {len(counts)} counts")
+        n2, num_leaf, dev = database.n2, database.num_leaf, dq.device
+        packed = self.packed_weights(dev)
+        database.check(self, b, n2, num_leaf, dev, frames=True)
+        ws = self.workspace(b, cap1, n2, num_leaf, dev)
+        out = self._outputs(b, cap1, n2, dev) if out is None else out
+        n1 = (ctypes.c_int32 * b)(*counts)
+        self.call("gatsspg_forward_frames", dev, packed, dq, n1, database.desc2d_db, database.cache, database.cache.numel() * 4,
+                  b, cap1, n2, num_leaf, self.flags(), float(scale_factor), float(match_threshold), *out, ws, ws.numel())
+        return out
+
     def prepare_database(self, d3, d2db):
         """Query-independent part of the first three GNN layers for a resident 3D database (amortised mode)."""
         b, _, n2 = d3.shape
@@ -279,6 +330,13 @@ class GATsSPGEngine(Engine):
         ws = self.workspace(*dims)
         self.call("gatsspg_gats_layer", dims[4], self.packed_weights(dims[4]), layer, d2db, *dims[:4],
                   self.flags() if flags is None else flags, ws, ws.numel())
+
+    def gats_layer_frames(self, dims, layer, d2db, leaf_logits=None, shared_leaf=True):
+        """One GATs layer of a frame batch on the state of ``dims``: the b frames against ONE database's leaves ``d2db`` [1,256,n2*L];
+        shared_leaf: the kernel that reads each leaf tile once per group of frames, or the per-frame kernel at database stride 0."""
+        ws = self.workspace(*dims)
+        self.call("gatsspg_gats_layer_frames", dims[4], self.packed_weights(dims[4]), layer, d2db, leaf_logits, *dims[:4], self.flags(),
+                  int(shared_leaf), ws, ws.numel())
 
     def attn_layer(self, dims, layer, kind):
         ws = self.workspace(*dims)
@@ -388,6 +446,36 @@ class GATsSuperGlue(nn.Module):
         with torch.no_grad():
             return self.engine.forward(dq, d3, d2db, self.hparams["scale_factor"], self.hparams["match_threshold"],
                                        database)
+
+    def match_frames(self, queries, database, max_frames=_native.MAX_FRAMES):
+        """Many frames of ONE object (not part of the reference API): ``queries`` is a list of per-frame descriptor tensors
+        ([256, n_i] or [1, 256, n_i], n_i >= 2, each frame its own count), ``database`` a handle of prepare_database() made with
+        ONE database (b = 1) or, to prepare one here, the data dict with ``descriptors3d_db`` / ``descriptors2d_db``.  Runs
+        ``max_frames`` (<= 32) frames per chain of launches and returns one dict per frame -- ``matches0``, ``matching_scores0``,
+        ``matches1``, ``matching_scores1`` trimmed to the frame's count and ``conf`` [n_i, n2] as a view of the batch buffer -- each
+        bitwise what ``forward(..., database=database)`` gives for that frame alone."""
+        if self.match_type != "softmax":
+            raise NotImplementedError
+        if not 1 <= max_frames <= _native.MAX_FRAMES:
+            raise ValueError(f"max_frames must be in [1, {_native.MAX_FRAMES}] (got {max_frames})")
+        if not isinstance(database, Database):
+            database = self.prepare_database(database)
+        if database.b != 1:
+            raise ValueError(f"a frame batch runs against ONE database: the cache must be prepared with b=1 (this one has b={database.b})")
+        queries = [_gpu(q, "descriptors2d_query") for q in queries]
+        queries = [q[0] if q.dim() == 3 and q.shape[0] == 1 else q for q in queries]
+        for q in queries:
+            if q.dim() != 2 or q.shape[0] != D:
+                raise ValueError(f"descriptors must have 256 channels, [256, n] or [1, 256, n] (got {list(q.shape)})")
+            if q.shape[1] < 2:   # an empty frame has no matcher call in the reference (:195); one point is what InstanceNorm1d refuses (:126)
+                raise ValueError(f"Expected more than 1 spatial element when training, got input size {[1, 512, q.shape[1]]}")
+        res = []
+        with torch.no_grad():
+            for i in range(0, len(queries), max_frames):
+                dq, counts = pack_frames(queries[i:i + max_frames])
+                out = self.engine.forward_frames(dq, counts, database, self.hparams["scale_factor"], self.hparams["match_threshold"])
+                res += trim_frames(out, counts)
+        return res
 
     def forward(self, data, database=None):
         """Keys of ``data`` as in the reference docstring (:181-189); extra keys are ignored.  ``database``:
