@@ -42,7 +42,8 @@ LIBRARIES = (
     Library("spp", ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"],
             ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", "wg_primitives.h", _include("superpoint.h")], tuning=True),
     Library("pnp", ["pnp_kernels.hip"], ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("pnp.h"), _include("pnp_batch.h")]),
-    Library("superglue", [os.path.join("superglue", "superglue.hip")], ["capi_common.h", _include("superglue", "superglue.h")]),
+    Library("superglue", [os.path.join("superglue", "superglue.hip"), os.path.join("superglue", "nn_matcher.hip")],
+            ["capi_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", _include("superglue", "superglue.h"), _include("superglue", "nn_matcher.h")]),
     Library("det", [os.path.join("detector", "detector.hip")],
             ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h")]),
     Library("map", [os.path.join("mapping", "mapping.hip")],

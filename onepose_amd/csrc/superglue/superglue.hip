@@ -847,7 +847,7 @@ int run_attention(const float* q, const float* kv, int b, int capN, int capM, co
 
 extern "C" {
 
-int sg_version(void) { return 2; }
+int sg_version(void) { return 3; }   // 3: the nearest-neighbour matcher (nn_matcher.h, nn_matcher.hip)
 const char* sg_last_error(void) { return g_err; }
 
 size_t sg_packed_weights_bytes(int n_layers) {

@@ -24,6 +24,7 @@ import torch
 
 from . import _native_det, _native_sg
 from ._binding import NativeError, WorkspaceCache, gpu_tensor, k_array  # noqa: F401
+from .nearest_neighbour import NearestNeighbour
 from .superglue import SuperGlue
 
 REPROJ_THRESHOLD = 6.0     # local_feature_2D_detector.py:105
@@ -117,7 +118,7 @@ def _write_gray(path, img_u8):
 
 class LocalFeatureObjectDetector:
     """extractor: onepose_amd.SuperPoint; matcher: onepose_amd.SuperGlue (its engine is driven directly, the V forwards
-    enqueued back to back) or any callable with SuperGlue's ``forward(data)`` contract on GPU tensors (called once per view).
+    enqueued back to back), onepose_amd.NearestNeighbour (one ragged call over the views, which share the query plane) or any callable with SuperGlue's ``forward(data)`` contract on GPU tensors (called once per view).
 
     ``ref_images``: list of [1,1,H,W] GPU tensors in [0, 1] -- the reference views, no file reader needed.  ``sfm_ws_dir``
     keeps the reference's meaning: image names from the COLMAP model there, sampled like the reference.
@@ -227,6 +228,8 @@ class LocalFeatureObjectDetector:
         native = isinstance(self.matcher, SuperGlue)
         if native and self.ragged and len(self.live) > 1:
             return self._match_views_ragged(kpts1, scores1, desc1, query_hw)
+        if isinstance(self.matcher, NearestNeighbour) and self.ragged and len(self.live) > 1:
+            return self._match_views_nn(desc1)
         if native:
             m1 = torch.empty(1, n1, device=dev, dtype=torch.int64)
             s1 = torch.empty(1, n1, device=dev, dtype=torch.float32)
@@ -269,6 +272,25 @@ class LocalFeatureObjectDetector:
             engine.forward_ragged(self.kpts0[sel], self.view_scores[sel], self.view_desc[sel], kpts1[None].expand(b, -1, -1),
                                   scores1[None].expand(b, -1), desc1[None].expand(b, -1, -1), [self.n0_host[i] for i in live],
                                   [n1] * b, [self.hw0_host[i] for i in live], [qhw] * b, out=(m0, m1, s0, s1))
+            if not whole:
+                self.matches0[sel] = m0
+                self.scores0[sel] = s0
+
+    def _match_views_nn(self, desc1):
+        """The views that have keypoints as ragged batches of the nearest-neighbour matcher (bitwise the loop's results): every
+        view reads the ONE query plane; with no empty view the outputs land straight in matches0 / scores0."""
+        n1, dev = int(desc1.shape[1]), desc1.device
+        engine, step = self.matcher.engine, _native_sg.NNM_MAX_ITEMS
+        for k in range(0, len(self.live), step):
+            live = self.live[k:k + step]
+            b = len(live)
+            whole = b == self.V
+            sel = slice(None) if whole else torch.tensor(live, device=dev)
+            m0 = self.matches0 if whole else torch.empty(b, self.cap0, device=dev, dtype=torch.int64)
+            s0 = self.scores0 if whole else torch.empty(b, self.cap0, device=dev, dtype=torch.float32)
+            m1 = torch.empty(b, n1, device=dev, dtype=torch.int64)
+            s1 = torch.empty(b, n1, device=dev, dtype=torch.float32)
+            engine.match_ragged(self.view_desc[sel], desc1, [self.n0_host[i] for i in live], [n1] * b, out=(m0, m1, s0, s1))
             if not whole:
                 self.matches0[sel] = m0
                 self.scores0[sel] = s0

@@ -29,6 +29,7 @@ import torch
 
 from . import _native_map, _native_sg
 from ._binding import NativeError
+from .nearest_neighbour import NearestNeighbour
 from .superglue import SuperGlue
 
 THRESHOLDS = dict(max_epipolar_error=4.0, min_pair_inliers=15, max_reproj_error=4.0, min_tri_angle=1.5, max_hypotheses=120,
@@ -292,7 +293,7 @@ class ObjectMapper:
 
     ``extractor``: a ``SuperPoint`` (max_keypoints 4096 in the reference), ``matcher``: a ``SuperGlue`` (match threshold 0.7);
     both may be None when only ``build_from_features`` / ``build_from_matches`` are used.  ``pair_batch``: image pairs per
-    ragged batch of the native matcher (``SuperGlue.match_pairs``; the matches are bitwise those of one forward per pair);
+    ragged batch of a native matcher (``SuperGlue.match_pairs`` / ``NearestNeighbour.match_pairs``; the matches are bitwise those of one forward per pair);
     1, or any other matcher, runs one forward per pair.  ``thresholds``: any of THRESHOLDS.
     Every entry point returns the dict ``load_object_database`` returns and, with ``out_dir``, writes the three annotation
     files it reads; ``self.last`` keeps the intermediate results of the latest build (numpy)."""
@@ -338,7 +339,7 @@ class ObjectMapper:
 
         todo = list(unique_pairs(pairs))
         pair_matches = []
-        if isinstance(self.matcher, SuperGlue) and self.pair_batch > 1:
+        if isinstance(self.matcher, (SuperGlue, NearestNeighbour)) and self.pair_batch > 1:
             step = min(self.pair_batch, _native_sg.MAX_ITEMS)
             for k in range(0, len(todo), step):      # one batch of pairs in memory at a time
                 chunk = todo[k:k + step]
