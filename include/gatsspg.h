@@ -141,8 +141,20 @@ int gatsspg_forward_profiled(const float* packed, const float* desc2d_query, con
  * The 3D database (desc3d_db + its leaves desc2d_db) is constant per object (inference.py:113-130) while the
  * reference recomputes -- and re-uploads, inference.py:86-90 -- everything per frame.  gnn.layers.0 (GATs),
  * the 3D side of gnn.layers.1 (self), the 3D-side projections / KV sums of gnn.layers.2 (cross) and the leaf logits
- * of the later GATs layers (num_leaf == 8, no linear transform) do not depend on the query frame; gatsspg_prepare_database computes them once, gatsspg_forward_cached skips them.  Results are
- * bit-identical to gatsspg_forward (same kernels, same fixed-order reductions) WHEN THE CACHE WAS PREPARED UNDER THE SAME `flags` AND
+ * of the later GATs layers (num_leaf == 8, no linear transform) do not depend on the query frame; gatsspg_prepare_database computes them once, gatsspg_forward_cached skips them.
+ * Those stages run on ONE-SIDE WINDOWS of the frame (the 3D columns when the cache is prepared, the query columns in the cached forward), and a
+ * stage with two kernel forms picks its form by the 64-column tiles of its own launch: b * round_up(n, 128) / 64 for a window,
+ * b * (round_up(n1, 128) + round_up(n2, 128)) / 64 for the plain forward.  Results are bit-identical to gatsspg_forward (same kernels, same
+ * fixed-order reductions) when every windowed launch takes the form the whole-frame launch takes; two thresholds separate forms that associate
+ * their sums differently: the fp32 mlp.3 tile (up to 64 tiles: the 64x64 tile that splits K over two wave groups and adds the halves last;
+ * above: the tall tile) and the fp16x3 / fp16x4 mlp.0 tile (tiles / 2 in [48, 64]: the 128-column tile; otherwise the 64-column tile, which
+ * walks the columns of an InstanceNorm partial from another start).  The other launch-size thresholds (register-diet forms of the fp32 qkv_kv /
+ * mlp.0, two- / three-stage ring of the fp16 mlp.3) separate forms that issue the same MFMAs in the same order.  bf16x3 / bf16x6 have one form
+ * per stage and are always bit-identical.
+ * Otherwise (the fp32 headline shape: 1000 x 7000 is 126 tiles, its query window 16) the two differ by the re-association noise of those sums
+ * and give the same matches: measured max |d conf| 3.5e-8 (fp32, 100 x 4000) and 1.1e-8 (fp16x4, 100 x 6000) on conf entries up to 5e-3,
+ * asserted below 2e-5 with identical matches0 / matches1 (tests/test_gats_stage_edges.py::test_database_cache_at_form_edges).
+ * All of this WHEN THE CACHE WAS PREPARED UNDER THE SAME `flags` AND
  * PACKED WEIGHTS as the call that consumes it.  The library does not record them in the cache (the Python wrapper does, and refuses a
  * mismatch); a C caller that mixes arithmetics gets a well-defined result -- the cached stages in the arithmetic of the prepare call, the
  * rest in the arithmetic of the forward call -- within the two arithmetics' difference of the plain forward: since round 6 the KV sums of

@@ -420,7 +420,9 @@ class GATsSuperGlue(nn.Module):
         """Amortised mode (not part of the reference API): keep the object's 3D database resident and precompute
         what the first three GNN layers derive from it alone.  ``data`` needs ``descriptors3d_db`` and
         ``descriptors2d_db``; pass the returned handle as ``database=`` to forward()/forward_batched() together
-        with the same database tensors.  Results are bit-identical to the plain forward."""
+        with the same database tensors.  Results are bit-identical to the plain forward when every one-side window of the cached
+        stages takes the kernel form the whole frame takes, otherwise within re-association noise of it with the same matches
+        (include/gatsspg.h, amortised mode)."""
         d3, d2db = _gpu(data["descriptors3d_db"], "descriptors3d_db"), _gpu(data["descriptors2d_db"], "descriptors2d_db")
         if d3.shape[2] < 2 or d2db.shape[2] % d3.shape[2] != 0:
             raise ValueError("database needs >= 2 points and a whole number of leaves per point")

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import TIE_GAP, TRAINED_CASES, argmax_flips, case_inputs, check_bench_golden, load_golden
+from gats_stage_reference import attention_propagation as attention_propagation_f64   # float64 by default: the yardstick of the scale tests
 from oracle import gatsspg_oracle as orc
 from onepose_amd import GATsSuperGlue, synthetic, _native
 
@@ -757,27 +758,6 @@ def test_fp16_terms_saturate_instead_of_overflowing(precision):
     rel = max(float(np.abs(o2 - r2).max() / np.abs(r2).max()), float(np.abs(o3 - r3).max() / np.abs(r3).max()))
     print(f"{precision}: relative deviation from the fp32 arithmetic at operand magnitude ~5e3: {rel:.2e}")
     assert rel < 1e-3
-
-
-def attention_propagation_f64(sd, p, x, s):
-    """AttentionPropagation (GATs_SuperGlue.py:69-128) in float64 numpy: the yardstick that separates an arithmetic's own error
-    from the fp32 noise every fp32 evaluation (the reference's included) has at unusual operand scales."""
-    f = lambda k: sd[f"{p}.{k}"].astype(np.float64)                                  # noqa: E731
-    conv = lambda w, b, t: np.einsum("oc,bcn->bon", w[..., 0], t) + b[None, :, None]   # noqa: E731
-    elu1 = lambda t: np.where(t > 0, t, np.expm1(np.minimum(t, 0))) + 1.0            # noqa: E731
-    x, s = x.astype(np.float64), s.astype(np.float64)
-    b, ns = x.shape[0], s.shape[2]
-    q = conv(f("attn.proj.0.weight"), f("attn.proj.0.bias"), x).reshape(b, 64, 4, -1)
-    k = conv(f("attn.proj.1.weight"), f("attn.proj.1.bias"), s).reshape(b, 64, 4, -1)
-    v = conv(f("attn.proj.2.weight"), f("attn.proj.2.bias"), s).reshape(b, 64, 4, -1)
-    Q, K, V = elu1(q), elu1(k), v / ns
-    KV = np.einsum("bdhm,bqhm->bqdh", K, V)
-    Z = 1.0 / (np.einsum("bdhn,bdh->bhn", Q, K.sum(axis=3)) + 1e-6)
-    msg = (np.einsum("bdhn,bqdh,bhn->bqhn", Q, KV, Z) * ns).reshape(b, 256, -1)
-    msg = conv(f("attn.merge.weight"), f("attn.merge.bias"), msg)
-    u = conv(f("mlp.0.weight"), f("mlp.0.bias"), np.concatenate([x, msg], axis=1))
-    u = (u - u.mean(axis=2, keepdims=True)) / np.sqrt(u.var(axis=2, keepdims=True) + 1e-5)
-    return conv(f("mlp.3.weight"), f("mlp.3.bias"), np.maximum(u, 0.0))
 
 
 def test_f64_yardstick_agrees_with_the_oracle():
