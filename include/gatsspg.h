@@ -74,6 +74,9 @@ extern "C" {
  *     The four precision bits are exclusive. */
 #define GATSSPG_FLAG_PREC_FP16X3 0x400
 #define GATSSPG_FLAG_PREC_FP16X4 0x800
+/* gatsspg_forward only: always enqueue the plain chain, never look at or write the workspace's reuse area (see gatsspg_forward).  Not set by
+ * default.  Same results, bit for bit; a caller whose database changes on every call saves the comparison pass with it. */
+#define GATSSPG_FLAG_NO_DB_REUSE 0x1000 /* not a GraphAttentionLayer or arithmetic flag: which chain gatsspg_forward enqueues */
 /* layer kinds for gatsspg_attn_layer (GATs_SuperGlue.py:55-64) */
 #define GATSSPG_LAYER_SELF 0
 #define GATSSPG_LAYER_CROSS 1
@@ -120,6 +123,35 @@ int gatsspg_pack_weights(const gatsspg_raw_weights* raw, float* packed, void* st
  *   desc2d_query [b,256,n1]  desc3d_db [b,256,n2]  desc2d_db [b,256,n2*num_leaf]
  *   conf [b,n1,n2]; matches0 [b,n1] int64; matches1 [b,n2] int64; mscores0 [b,n1]; mscores1 [b,n2]
  * n1 >= 2 and n2 >= 2 (the reference raises for a single point, and returns early for 0). */
+/* DATABASE REUSE.  The 3D database is one per object and a caller of the reference's forward(data) passes the same tensors for every frame of
+ * a sequence, so on shapes of more than 64 column tiles -- b * (round_up(n1, 128) + round_up(n2, 128)) / 64 > 64; smaller frames are bound by
+ * launches and run the plain chain -- gatsspg_forward keeps, in a reuse area at the END of the workspace, what the first three GNN layers
+ * derive from the database and the weights alone (the cache of the amortised mode below), together with a bitwise snapshot of desc3d_db,
+ * desc2d_db and the packed-weight ranges that work depends on (GATs layer 0, attention layers 0 and 1).  Every call first compares the
+ * caller's tensors with the snapshot, ALL of them, word for word, on the device (one pass, 168 MB of reads at 1000 x 7000 x 8 leaves, 28 us); if
+ * they are equal it skips that work (about 12 % of the frame's matrix flops and one pass over the leaves), otherwise it redoes it from this
+ * call's inputs.  There is no host synchronisation and the launch sequence is the same either way (graph-capture safe): the kernels of the
+ * skipped part are launched and return at once.  A snapshot is taken (a copy of the database) when a call misses on a database whose
+ * fingerprint -- a sum over 8 KB of it -- the previous call had too: a constant database misses twice and hits from the third call on, a
+ * database that changes on every call never pays the copy.  The fingerprint never decides a hit.
+ *   - Results are BIT FOR BIT those of the plain chain (GATSSPG_FLAG_NO_DB_REUSE): the windowed launches take the whole frame's kernel forms.
+ *   - The workspace therefore carries state between calls of gatsspg_forward.  One workspace serves one stream at a time, as before.
+ *     Overwriting it is harmless and costs the next two calls a miss: a hit reads nothing of the area that the comparison has not covered
+ *     -- the snapshot against the caller's tensors, the cache against a second copy of itself, the stamp of the state block (magic value,
+ *     b, round_up(n1, 128), n2, num_leaf, flags) -- so the same memory may serve calls of other shapes, flags or entry points in between.
+ *     Changing the database or the weights in place is detected (it is a mismatch like any other).
+ *   - The price where it never pays.  A call that misses redoes the database-side work on a 3D-side window and the rest on a query-side
+ *     window, each launch about as long as the whole frame's, on top of the comparison pass.  Measured at 1000 x 7000 x 8 leaves, fp32, with
+ *     two databases alternated call by call (never a hit, never a snapshot): 1062 against 1148 frames/s with 4 frames in flight (-7.5 %),
+ *     1.155 against 0.991 ms one frame at a time (+17 %).  A caller whose database changes on every call sets GATSSPG_FLAG_NO_DB_REUSE and
+ *     is where it was (1151 against 1148 frames/s, 0.996 against 0.991 ms); a caller with one database per sequence pays two such calls
+ *     per sequence.
+ * gatsspg_forward_profiled always runs the plain chain.
+ * The area's state block is the LAST 256 bytes of a workspace of such a shape, at gatsspg_workspace_bytes(b, n1, n2, num_leaf) - 256:
+ * sixteen int32 words, for a caller (or a test) that wants to know what the last call did, read after synchronising the stream: [0..5] the
+ * stamp (a magic value, b, round_up(n1, 128), n2, num_leaf, flags), [6] the fingerprint of the last call's database, [7] snapshot_valid,
+ * [8] miss (during a call: a difference was found; 0 again afterwards), [9] strike (its fingerprint was the previous call's), [10] hit (1: the
+ * last call reused the cache; 0: it redid the work).  A workspace of a smaller shape has no area and ends as it did before ABI 413. */
 int gatsspg_forward(const float* packed, const float* desc2d_query, const float* desc3d_db,
                     const float* desc2d_db, int b, int n1, int n2, int num_leaf, int flags,
                     float scale_factor, float match_threshold, float* conf, int64_t* matches0,

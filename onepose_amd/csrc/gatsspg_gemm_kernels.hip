@@ -49,6 +49,7 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void qkv_kv_k
                                                             const unsigned short* __restrict__ Wl2,
                                                             const float* __restrict__ Z, float* __restrict__ Qbuf,
                                                             float* __restrict__ kvpart, LT L) {
+    if (launch_is_off(L)) return;
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: qkv_kv_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
@@ -208,6 +209,7 @@ __global__ __launch_bounds__(1024) void kv_final_kernel(const float* __restrict_
                                                         float* __restrict__ Mop, unsigned short* __restrict__ Mpl,
                                                         float* __restrict__ ksumT, float* __restrict__ zsc, int* __restrict__ statcnt,
                                                         const float* __restrict__ sc, LT L, int cross, int prec, int abl) {
+    if (launch_is_off(L)) return;
     __shared__ float4 red[16][64];
     __shared__ float4 kvs[64];   // this block's final KV^T rows: [4 d][16 float4 of q]
     __shared__ float opsum[16];      // per wave: sum over its tiles of the tile's largest key-sum bound (bound data, slots 0..3)
@@ -438,6 +440,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1))
                                                    const float* __restrict__ ksumT,
                                                    float* __restrict__ U, float* __restrict__ statpart, float* __restrict__ stats,
                                                    int* __restrict__ statcnt, LT L, unsigned long long* trace) {
+    if (launch_is_off(L)) return;
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp0_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const unsigned long long t_entry = trace ? wall_clock64() : 0;
@@ -546,6 +549,7 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1))
 template <int TW, class LT = ColLayout>
 __global__ __launch_bounds__(1024) void stat_final_kernel(const float* __restrict__ statpart, float* __restrict__ stats,
                                                           LT L) {
+    if (launch_is_off(L)) return;
     constexpr int ROWS = TW == 32 ? 32 : 64, PARTS = 1024 / ROWS;
     __shared__ double red[2][PARTS][ROWS];
     const int rl = threadIdx.x % ROWS, part = threadIdx.x / ROWS;
@@ -612,6 +616,7 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void mlp3_ker
                                                    const unsigned short* __restrict__ Wl2,
                                                    const float* __restrict__ U, const float* __restrict__ stats,
                                                    float* __restrict__ Z, LT L) {
+    if (launch_is_off(L)) return;
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp3_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
@@ -810,6 +815,7 @@ using WltTile = GemmTile<64, 64, 2, 2, true>;
 
 __global__ __launch_bounds__(256) void gats_wlt_kernel(const float* __restrict__ W, const float* __restrict__ P,
                                                        float* __restrict__ Z, ColLayout L, int add_h) {
+    if (launch_is_off(L)) return;
     using T = WltTile;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
@@ -932,6 +938,20 @@ constexpr int DIET_MIN_TILES = 64;
 // chain, not by the matrix pipes: up to SMALL_NT3 64-column tiles take the 64x64 tile with the K loop split over two wave groups.
 constexpr int SMALL_NT3 = 64;
 static int diet_min_tiles() { return tuning_knob("DIET_MIN_TILES", DIET_MIN_TILES); }
+static int small_nt3() { static const int v = tuning_knob("SMALL_NT3", SMALL_NT3); return v; }
+// Where gatsspg_forward reuses the first-three-layer work of an unchanged database (gatsspg_capi.hip).  That path runs gnn.layers.1
+// and the projections of gnn.layers.2 on one-side windows of the frame, and must give the plain chain's bits.  Two shape thresholds separate
+// forms that associate their sums differently -- the fp32 mlp.3 tile here, the fp16 mlp.0 tile in gatsspg_split_kernels.hip -- and both are
+// taken through launch_by_form, which the reusing path hands the WHOLE frame's tile count (Workspace::form_tiles): every window runs the
+// form the plain forward's whole-frame launch runs, at every shape (left to its own 16 tiles, the headline's query window would take
+// Mlp3TileS against the frame's Mlp3TileTallW8).  The other thresholds (register diet, two- / three-stage ring) choose between forms that
+// issue the same MFMAs in the same order.  What the predicate leaves out is the small-launch regime of those very thresholds: a frame of
+// at most SMALL_NT3 / DIET_MIN_TILES tiles leaves CUs empty and is bound by launches, not by flops, so the comparison pass and a dozen
+// empty launches are not paid for by the columns they save; such a shape runs the plain chain and its workspace carries no reuse area.
+bool db_reuse_shape(int b, int n1, int n2) {
+    const int whole = b * (round_up(n1, CP) + round_up(n2, CP)) / 64;
+    return whole > small_nt3() && whole > diet_min_tiles();
+}
 // (removed alternatives of the fp32 kernels, each measured and lost: the Q / mlp3 tiles staged through LDS instead of stored from the
 //  accumulators, -0.5 % per frame; the bias table without quarter fragments, -0.2 % in flight; quarter fragments without the table; mlp3's
 //  quarter-fragment form, 2 % slower one frame at a time (profiles/r06b_*, r06c_*); the fp32 arithmetic on the LDS-DMA loop, 8 % slower
@@ -1003,7 +1023,6 @@ static void launch_mlp3_t(const AttnLayer& a, const Workspace& w, hipStream_t s,
 void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     // (profiling ablations of the fp32 main loop -- no global loads, no LDS writes, cache-hot panels, L1-hot loads, the loop cut to its
     //  fixed cost -- were timed in round 5, profiles/r05d_trace_mlp0_*; removed)
-    static const int small_nt3 = tuning_knob("SMALL_NT3", SMALL_NT3);
     if (is_fp16(w.prec)) launch_mlp0_sp(a, w, s, hk);
     else if (w.prec == BF16X3) launch_mlp0_t<Mlp0TileW8, BF16X3>(a, w, s, hk);
     else if (w.prec == BF16X6) launch_mlp0_t<Mlp0TileW8, BF16X6>(a, w, s, hk);
@@ -1018,7 +1037,7 @@ void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHo
     else if (w.prec == BF16X6) launch_mlp3_t<Mlp3TileTallW8, BF16X6>(a, w, s, hk);
     else   // the K-split tile adds its two halves last: every frame of a frames layout takes the tile it takes alone
         launch_by_form(
-            w, [&](int tiles) { return tiles <= small_nt3; }, [&](const Workspace& v) { launch_mlp3_t<Mlp3TileS, FP32>(a, v, s, hk); },
+            w, [&](int tiles) { return tiles <= small_nt3(); }, [&](const Workspace& v) { launch_mlp3_t<Mlp3TileS, FP32>(a, v, s, hk); },
             [&](const Workspace& v) { launch_mlp3_t<Mlp3TileTallW8, FP32, 1>(a, v, s, hk); });
 }
 

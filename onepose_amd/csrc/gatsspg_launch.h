@@ -86,6 +86,17 @@ void launch_load_state(const float* dq, const float* d3, const Workspace& w, hip
 // copies compact [b,256,n] columns of one or both sides into `dst` ([256][ld]); a null side is left untouched
 void launch_load_columns(const float* c2, const float* c3, float* dst, const Workspace& w, hipStream_t s);
 void launch_store_state(const float* src, float* out2d, float* out3d, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
+// the final KV sums of the 3D-side segments (w.kvfin, written by launch_kv_final) into a database cache's kvY [b][4][KVP]
+void launch_store_kv_sums(float* kvY, const Workspace& w, hipStream_t s);
+// The plain forward's database reuse.  launch_db_verify: st->miss (left 0 by the previous call) becomes 1 unless every
+// 16-byte word of the pieces equals its snapshot, the snapshot is valid and was taken under `stamp`; also st->strike (the database's
+// fingerprint, a sum over a strided sample of d3 [n3 words] and d2db [n2 words], equals the previous call's) and the new fingerprint and stamp.
+// launch_db_settle, the last launch of the prepare chain (one workgroup, never gated): on a miss launch_store_kv_sums' work; st->hit = !miss,
+// st->copy = miss with a strike, st->snapshot_valid set by such a miss and cleared by any other; st->miss cleared for the next call.
+// launch_db_snapshot: copies the pieces into the snapshot where st->copy says so.
+void launch_db_settle(float* kvY, const Workspace& w, ReuseState* st, hipStream_t s);
+void launch_db_verify(const DbPieces& P, ReuseState* st, const ReuseStamp& stamp, const float* d3, size_t n3, const float* d2db, size_t n2, hipStream_t s);
+void launch_db_snapshot(const DbPieces& P, ReuseState* st, hipStream_t s);
 // h3: where the layer reads the 3D-point descriptors from: nullptr = the state Z; otherwise the caller's compact
 // [b,256,n2] tensor (first layer of a forward: the state load is fused, `dq` is copied into the 2D side by spare workgroups)
 void launch_gats(const GatsLayer& g, const float* leaves, int num_leaf, int flags, float* dst, const Workspace& w, hipStream_t s,

@@ -45,6 +45,7 @@ __global__ __launch_bounds__(T::THREADS, 3) void qkv_kv_sp_kernel(const float* _
                                                                 const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                                 const unsigned short* __restrict__ P2, const float* __restrict__ Z,
                                                                 float* __restrict__ Qbuf, float* __restrict__ kvpart, LT L) {
+    if (launch_is_off(L)) return;
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     float* smem = reinterpret_cast<float*>(smem_c);
     if constexpr (T::F16) fp16_saturate_mode();
@@ -229,6 +230,7 @@ __global__ __launch_bounds__(T::THREADS, (T::TM == 4 ? 1 : (T::WAVES == 4 && T::
                                                               const float* __restrict__ ksumT, const float* __restrict__ zsc,
                                                               float* __restrict__ U, float* __restrict__ statpart, float* __restrict__ stats,
                                                               int* __restrict__ statcnt, LT L, unsigned long long* trace) {
+    if (launch_is_off(L)) return;
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     float* smem = reinterpret_cast<float*>(smem_c);
     if constexpr (T::F16) fp16_saturate_mode();
@@ -359,6 +361,7 @@ __global__ __launch_bounds__(T::THREADS, (T::NST == 2 ? 3 : 2)) void mlp3_sp_ker
                                                               const unsigned short* __restrict__ P0, const unsigned short* __restrict__ P1,
                                                               const unsigned short* __restrict__ P2, const float* __restrict__ U,
                                                               const float* __restrict__ stats, float* __restrict__ Z, LT L) {
+    if (launch_is_off(L)) return;
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     float* smem = reinterpret_cast<float*>(smem_c);
     if constexpr (T::F16) fp16_saturate_mode();

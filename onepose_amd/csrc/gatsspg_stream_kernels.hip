@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256) void load_state_kernel(const float* __restrict
     // one workgroup per (frame, channel) row; float4 stores (np is a multiple of 128), float4 loads when the
     // source rows are 16-byte aligned (n1, n2 multiples of 4).  A null source leaves its side untouched
     // (zero_missing = 0) or zero-fills it (zero_missing = 1).
+    if (launch_is_off(L)) return;
     const int ch = blockIdx.x, f = blockIdx.y;
     float* zr = Z + (size_t)ch * L.ld + (size_t)f * L.np;
     const float* q = dq ? dq + ((size_t)f * D + ch) * L.n1 : nullptr;
@@ -62,6 +63,7 @@ __global__ __launch_bounds__(256) void load_state_kernel(const float* __restrict
 
 __global__ __launch_bounds__(256) void store_state_kernel(const float* __restrict__ S, float* __restrict__ o2,
                                                           float* __restrict__ o3, ColLayout L) {
+    if (launch_is_off(L)) return;
     const int ch = blockIdx.x, f = blockIdx.y;
     const float* zr = S + (size_t)ch * L.ld + (size_t)f * L.np;
     if (o2) {
@@ -86,6 +88,117 @@ void launch_load_columns(const float* c2, const float* c3, float* dst, const Wor
 }
 void launch_store_state(const float* src, float* out2d, float* out3d, const Workspace& w, hipStream_t s, ProfileHook*) {
     hipLaunchKernelGGL(store_state_kernel, dim3(D, w.L.b), dim3(256), 0, s, src, out2d, out3d, w.L);
+}
+
+// the final KV sums of the 3D-side segments (segment 2 f + 1 of kvfin) into a database cache: one workgroup per frame
+__global__ __launch_bounds__(256) void store_kv_sums_kernel(const float* __restrict__ kvfin, float* __restrict__ kvY, ColLayout L) {
+    if (launch_is_off(L)) return;
+    const float4* src = reinterpret_cast<const float4*>(kvfin + (size_t)(2 * blockIdx.x + 1) * H * KVP);
+    float4* dst = reinterpret_cast<float4*>(kvY + (size_t)blockIdx.x * H * KVP);
+    for (int i = threadIdx.x; i < H * KVP / 4; i += 256) dst[i] = src[i];
+}
+void launch_store_kv_sums(float* kvY, const Workspace& w, hipStream_t s) {
+    static_assert((H * KVP) % 4 == 0, "the KV sums of a segment are copied as float4");
+    hipLaunchKernelGGL(store_kv_sums_kernel, dim3(w.L.b), dim3(256), 0, s, w.kvfin, kvY, w.L);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// database reuse of the plain forward: full bitwise comparison of the caller's database and weight ranges with the
+// snapshot in the workspace, and the snapshot copy.  Both walk every piece in 16-byte words, grid-strided, blockIdx.y = piece.
+// ------------------------------------------------------------------------------------------------------
+constexpr int DBV_BLOCKS = 1024, DBV_UNROLL = 4;   // workgroups per piece (blockIdx.y = piece); 4 x 2 independent 16-byte loads per thread and trip
+constexpr int DBS_BLOCKS = 128;                    // workgroups per piece of the snapshot copy
+constexpr int DBV_SAMPLES = 1024;                  // fingerprint: this many words of each database tensor (8 KB in all)
+__global__ __launch_bounds__(256) void db_verify_kernel(DbPieces P, ReuseState* st, ReuseStamp stamp, const unsigned* __restrict__ d3,
+                                                        unsigned long long n3, const unsigned* __restrict__ d2db, unsigned long long n2) {
+    const uint4* __restrict__ cur = P.cur[blockIdx.y];
+    const uint4* __restrict__ snap = P.snap[blockIdx.y];
+    const bool owner = blockIdx.x == 0 && blockIdx.y == 0;   // workgroup (0, 0) also owns the state block
+    __shared__ int same_stamp;
+    if (owner && threadIdx.x == 0) {
+        // a snapshot that is not valid, or was taken under another stamp, is a miss before anything is compared
+        const ReuseStamp o = st->stamp;
+        same_stamp = o.magic == stamp.magic && o.b == stamp.b && o.n1p == stamp.n1p && o.n2 == stamp.n2 && o.num_leaf == stamp.num_leaf && o.flags == stamp.flags;
+        if (!same_stamp || st->snapshot_valid != 1) {
+            st->snapshot_valid = 0;
+            atomicOr(&st->miss, 1);
+        }
+    }
+    // A word that already reads non-zero cannot change the outcome any more: the workgroups that start after the first difference was
+    // recorded skip their share (a miss costs a fraction of the pass), and no wave adds an atomic to a word that is set (when nearly
+    // every wave differs -- no valid snapshot -- 28 k atomics on one address took 200 us).  Which workgroups skip depends on their order;
+    // whether the word ends non-zero does not.
+    const unsigned long long total = __hip_atomic_load(&st->miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0ull : P.n[blockIdx.y];
+    const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+    unsigned diff = 0;
+    for (unsigned long long i0 = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i0 < total; i0 += stride * DBV_UNROLL) {
+        uint4 a[DBV_UNROLL], c[DBV_UNROLL];
+#pragma unroll
+        for (int j = 0; j < DBV_UNROLL; ++j) {
+            const unsigned long long i = i0 + j * stride;
+            a[j] = c[j] = make_uint4(0, 0, 0, 0);
+            if (i < total) {
+                a[j] = cur[i];
+                c[j] = snap[i];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DBV_UNROLL; ++j) diff |= (a[j].x ^ c[j].x) | (a[j].y ^ c[j].y) | (a[j].z ^ c[j].z) | (a[j].w ^ c[j].w);
+    }
+    // one plain atomic per wave that saw a difference: the word's value does not depend on who comes first
+    if (__any(diff != 0) && (threadIdx.x & 63) == 0 && !__hip_atomic_load(&st->miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(&st->miss, 1);
+    if (!owner) return;
+    // fingerprint of this call's database, and the new stamp
+    __shared__ unsigned fp;
+    if (threadIdx.x == 0) fp = 0;
+    __syncthreads();
+    unsigned h = 0;
+    for (int k = threadIdx.x; k < DBV_SAMPLES; k += 256)   // word k * n / SAMPLES of each tensor, weighted by its (odd) position
+        h += d3[(unsigned long long)k * n3 / DBV_SAMPLES] * (2u * k + 1u) + d2db[(unsigned long long)k * n2 / DBV_SAMPLES] * (2u * (k + DBV_SAMPLES) + 1u);
+    atomicAdd(&fp, h);   // (integer sum: the same value in every order)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        st->strike = same_stamp && st->fingerprint == fp ? 1 : 0;
+        st->fingerprint = fp;
+        st->stamp = stamp;
+    }
+}
+// The last launch of the gated prepare chain, ONE workgroup, never gated itself: on a miss the KV sums of the 3D-side segments into the
+// cache (store_kv_sums_kernel's work); then the call's verdict -- hit, whether db_snapshot_kernel copies, the snapshot's validity -- and the
+// miss word cleared for the next call's db_verify_kernel (this workgroup is its last reader: no memset in front of every call).
+__global__ __launch_bounds__(1024) void db_settle_kernel(const float* __restrict__ kvfin, float* __restrict__ kvY, int b, ReuseState* st) {
+    const int miss = st->miss, strike = st->strike;
+    if (miss) {
+        for (int f = 0; f < b; ++f) {
+            const float4* src = reinterpret_cast<const float4*>(kvfin + (size_t)(2 * f + 1) * H * KVP);
+            float4* dst = reinterpret_cast<float4*>(kvY + (size_t)f * H * KVP);
+            for (int i = threadIdx.x; i < H * KVP / 4; i += 1024) dst[i] = src[i];
+        }
+    }
+    __syncthreads();   // every thread has read st->miss
+    if (threadIdx.x == 0) {
+        st->hit = miss ? 0 : 1;
+        st->copy = miss && strike ? 1 : 0;
+        if (miss) st->snapshot_valid = strike ? 1 : 0;   // (with the copy that the next launch makes)
+        st->miss = 0;
+    }
+}
+__global__ __launch_bounds__(256) void db_snapshot_kernel(DbPieces P, const ReuseState* st) {
+    if (!st->copy) return;
+    const uint4* __restrict__ cur = P.cur[blockIdx.y];
+    uint4* __restrict__ snap = P.snap[blockIdx.y];
+    const unsigned long long total = P.n[blockIdx.y], stride = (unsigned long long)gridDim.x * 256;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) snap[i] = cur[i];
+}
+void launch_db_verify(const DbPieces& P, ReuseState* st, const ReuseStamp& stamp, const float* d3, size_t n3, const float* d2db, size_t n2, hipStream_t s) {
+    hipLaunchKernelGGL(db_verify_kernel, dim3(DBV_BLOCKS, DB_PIECES), dim3(256), 0, s, P, st, stamp, reinterpret_cast<const unsigned*>(d3), (unsigned long long)n3,
+                       reinterpret_cast<const unsigned*>(d2db), (unsigned long long)n2);
+}
+void launch_db_settle(float* kvY, const Workspace& w, ReuseState* st, hipStream_t s) {
+    hipLaunchKernelGGL(db_settle_kernel, dim3(1), dim3(1024), 0, s, w.kvfin, kvY, w.L.b, st);
+}
+void launch_db_snapshot(const DbPieces& P, ReuseState* st, hipStream_t s) {
+    hipLaunchKernelGGL(db_snapshot_kernel, dim3(DBS_BLOCKS, DB_PIECES), dim3(256), 0, s, P, st);   // (a hit pays for this grid's start)
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -146,6 +259,7 @@ __global__ __launch_bounds__(256, 7) void gats_leaf8x4_kernel(const float* __res
     __shared__ float red3[4][4];
     __shared__ float redl[4][32];
     __shared__ float coef[4][9];
+    if (launch_is_off(L)) return;
     const int f = blockIdx.y;
     if (FUSED_LOAD && (int)blockIdx.x >= ntiles) {   // state-load role
         const int ch = ((int)blockIdx.x - ntiles) * 4 + (threadIdx.x >> 6), ln = threadIdx.x & 63;
@@ -472,6 +586,7 @@ __global__ __launch_bounds__(256) void gats_generic_kernel(const float* __restri
     __shared__ float scratch[4];
     __shared__ float sl[GATS_MAXL];
     __shared__ float coef[GATS_MAXL + 1];
+    if (launch_is_off(L)) return;
     const int f = blockIdx.y, ch = threadIdx.x;
     const size_t lrow = (size_t)L.n2 * nl;
     const float* Lr = leaves + ((size_t)db_frame(L, f) * D + ch) * lrow;

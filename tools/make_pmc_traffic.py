@@ -2,7 +2,7 @@
 """profiles/pmc_traffic.json from two rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE, each in its own run: MI355X_MICROARCH.md, HBM section)
 summarised by tools/rocpd_pmc.py:
 
-    python tools/make_pmc_traffic.py fetch.txt write.txt [--git HEAD_SHA] > profiles/pmc_traffic.json
+    python tools/make_pmc_traffic.py fetch.txt write.txt [--git HEAD_SHA] [--command "how the passes were taken"] > profiles/pmc_traffic.json
 
 Keeps the entries of the existing file that the passes do not cover (the extractor's).  Records the hash of the sources the passes were taken
 on (onepose_amd.build_ext.source_hash): bench.py compares it with the sources it runs and reports a stale file as stale."""
@@ -40,6 +40,7 @@ def parse(path, counter):
 def main():
     fetch, write = parse(sys.argv[1], "FETCH_SIZE"), parse(sys.argv[2], "WRITE_SIZE")
     git = sys.argv[sys.argv.index("--git") + 1] if "--git" in sys.argv else None
+    command = sys.argv[sys.argv.index("--command") + 1] if "--command" in sys.argv else None   # how the passes were taken, if not as below
     path = sys.argv[sys.argv.index("--file") + 1] if "--file" in sys.argv else os.path.join(ROOT, "profiles", "pmc_traffic.json")
     old = json.load(open(path)) if os.path.exists(path) else {}
     if "--config" in sys.argv:
@@ -58,7 +59,7 @@ def main():
                        "(MI355X_MICROARCH.md, HBM section); write bytes = WRITE_SIZE * 1024.  bench.py quotes these as static numbers and checks "
                        "_source.csrc_sha against the sources it runs (roofline.traffic_source).",
            "_source": {"csrc_sha": build_ext.source_hash(), "git_head": git, "passes": [os.path.basename(sys.argv[1]), os.path.basename(sys.argv[2])],
-                       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python bench.py --steps 6 --warmup 2 --reps 1 --min-timed-seconds 0 --streams 1 (tools/r06_collect.sh)"}}
+                       "command": command or "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python bench.py --steps 6 --warmup 2 --reps 1 --min-timed-seconds 0 --streams 1 (tools/r06_collect.sh)"}}
     for k in sorted(set(fetch) & set(write)):
         out[k] = {"FETCH_SIZE_KB": fetch[k], "WRITE_SIZE_KB": write[k], "bytes": int(round((2 * fetch[k] + write[k]) * 1024))}
     for k, v in old.items():
