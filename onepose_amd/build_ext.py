@@ -46,8 +46,8 @@ LIBRARIES = (
             ["capi_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", _include("superglue", "superglue.h"), _include("superglue", "nn_matcher.h")]),
     Library("det", [os.path.join("detector", "detector.hip")],
             ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h")]),
-    Library("map", [os.path.join("mapping", "mapping.hip")],
-            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h")]),
+    Library("map", [os.path.join("mapping", "mapping.hip"), os.path.join("mapping", "bundle_adjust.hip")],
+            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h"), _include("mapping", "bundle_adjust.h")]),
 )
 # views of the table under the names other modules use
 LIB_PATH, SPP_LIB_PATH, PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH, MAP_LIB_PATH = (lib.path for lib in LIBRARIES)
