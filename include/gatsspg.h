@@ -127,8 +127,9 @@ int gatsspg_pack_weights(const gatsspg_raw_weights* raw, float* packed, void* st
  * a sequence, so on shapes of more than 64 column tiles -- b * (round_up(n1, 128) + round_up(n2, 128)) / 64 > 64; smaller frames are bound by
  * launches and run the plain chain -- gatsspg_forward keeps, in a reuse area at the END of the workspace, what the first three GNN layers
  * derive from the database and the weights alone (the cache of the amortised mode below), together with a bitwise snapshot of desc3d_db,
- * desc2d_db and the packed-weight ranges that work depends on (GATs layer 0, attention layers 0 and 1).  Every call first compares the
- * caller's tensors with the snapshot, ALL of them, word for word, on the device (one pass, 168 MB of reads at 1000 x 7000 x 8 leaves, 28 us); if
+ * desc2d_db and the packed-weight ranges that work depends on (GATs layer 0, attention layers 0 and 1).  Every call compares the
+ * caller's tensors with the snapshot, ALL of them, word for word, on the device (168 MB of reads at 1000 x 7000 x 8 leaves, under the call's
+ * first launches, which work on the query alone: about 5 us of the 28 us the pass takes alone, fp32; a launch of its own otherwise); if
  * they are equal it skips that work (about 12 % of the frame's matrix flops and one pass over the leaves), otherwise it redoes it from this
  * call's inputs.  There is no host synchronisation and the launch sequence is the same either way (graph-capture safe): the kernels of the
  * skipped part are launched and return at once.  A snapshot is taken (a copy of the database) when a call misses on a database whose
@@ -142,10 +143,9 @@ int gatsspg_pack_weights(const gatsspg_raw_weights* raw, float* packed, void* st
  *     Changing the database or the weights in place is detected (it is a mismatch like any other).
  *   - The price where it never pays.  A call that misses redoes the database-side work on a 3D-side window and the rest on a query-side
  *     window, each launch about as long as the whole frame's, on top of the comparison pass.  Measured at 1000 x 7000 x 8 leaves, fp32, with
- *     two databases alternated call by call (never a hit, never a snapshot): 1062 against 1148 frames/s with 4 frames in flight (-7.5 %),
- *     1.155 against 0.991 ms one frame at a time (+17 %).  A caller whose database changes on every call sets GATSSPG_FLAG_NO_DB_REUSE and
- *     is where it was (1151 against 1148 frames/s, 0.996 against 0.991 ms); a caller with one database per sequence pays two such calls
- *     per sequence.
+ *     two databases alternated call by call (never a hit, never a snapshot): 1065 against 1140 frames/s with 4 frames in flight (-7 %),
+ *     1.134 against 1.014 ms one frame at a time (+12 %).  A caller whose database changes on every call sets GATSSPG_FLAG_NO_DB_REUSE and
+ *     is where it was; a caller with one database per sequence pays two such calls per sequence.
  * gatsspg_forward_profiled always runs the plain chain.
  * The area's state block is the LAST 256 bytes of a workspace of such a shape, at gatsspg_workspace_bytes(b, n1, n2, num_leaf) - 256:
  * sixteen int32 words, for a caller (or a test) that wants to know what the last call did, read after synchronising the stream: [0..5] the

@@ -98,13 +98,17 @@ Workspace windowed(const Workspace& w, int side) {
 }
 
 // The prepare chain: everything of the first three GNN layers that depends on the database and the weights alone, into the cache `c`.
-// w: a workspace carved with 2 dummy (zero) query columns.  Every launch takes w.L.gate (the reusing path of gatsspg_forward: the chain
-// does nothing while the gate word reads 0).  ll: also the leaf logits of the three GATs layers still to come (DbCache::LL).
+// w: a workspace carved with 2 dummy (zero) query columns (gatsspg_prepare_database), or -- with `settle` -- the workspace of a reusing
+// forward itself: the chain then runs on the 3D-side columns of the call's own layout and leaves alone what the call's part A wrote (query
+// columns of state and Q, their KV partials; the per-segment sums, statistics and operators of the query side it does overwrite are
+// consumed by then or written again by part B).  Every launch takes w.L.gate (the reusing path of gatsspg_forward: the chain does nothing
+// while the gate word reads 0).  ll: also the leaf logits of the three GATs layers still to come (DbCache::LL).
 // settle: the reusing path's state block, whose verdict the last launch then settles (launch_db_settle), or null.
 void enqueue_prepare(const float* packed, const float* desc3d_db, const float* desc2d_db, int num_leaf, int flags, const Workspace& w,
                      const DbCache& c, bool ll, ReuseState* settle, hipStream_t s) {
     const Workspace wy = windowed(w, 1);
-    launch_load_state(nullptr, desc3d_db, w, s);
+    if (settle) launch_load_columns(nullptr, desc3d_db, w.Z, w, s);         // the query columns stay
+    else launch_load_state(nullptr, desc3d_db, w, s);
     enqueue_gats(packed, 0, desc2d_db, num_leaf, flags, w, s);              // gnn.layers.0 (3D side only by nature)
     enqueue_attn(packed, 0, GATSSPG_LAYER_SELF, wy, s);                     // gnn.layers.1, 3D side
     const AttnLayer a1 = attn_layer(packed, 1);
@@ -117,22 +121,34 @@ void enqueue_prepare(const float* packed, const float* desc3d_db, const float* d
     if (ll) launch_gats_leaf_logits(gats_layer(packed, 1), 3, desc2d_db, c.LL, w, s);   // leaf . u1 of the three GATs layers still to come
 }
 
-// The cached chain: the forward from a cache of the prepare chain.  w: the call's workspace, or its frames form (gatsspg_forward_frames).
-void enqueue_cached(const float* packed, const float* desc2d_query, const float* desc2d_db, const DbCache& c, bool ll, int num_leaf, int flags,
-                    float scale_factor, float match_threshold, const MatchOut& out, const Workspace& w, hipStream_t s) {
-    const Workspace wx = windowed(w, 0);
-    launch_load_state(desc2d_query, c.Y2, w, s);                            // state = [X0 (of every frame) | cached Y2]
+// The cached chain: the forward from a cache of the prepare chain, in two halves split at the first use of the cache.
+// w: the call's workspace, or its frames form (gatsspg_forward_frames).
+// Part A, the query side: nothing here reads the cache, the database or (reusing path) the verdict.  With w.rider the three GEMM launches
+// of gnn.layers.1 carry the database comparison.  (The projection of gnn.layers.2 as a fourth riding launch: no difference)
+void enqueue_cached_query(const float* packed, const float* desc2d_query, const Workspace& w, hipStream_t s) {
+    Workspace wx = windowed(w, 0);
+    launch_load_columns(desc2d_query, nullptr, w.Z, w, s);                  // state = [X0 (of every frame) | ...]
     enqueue_attn(packed, 0, GATSSPG_LAYER_SELF, wx, s);                     // gnn.layers.1, query side only
+    wx.rider = nullptr;
+    launch_qkv_kv(attn_layer(packed, 1), wx, s);                            // gnn.layers.2: query-side Q, KV, ksum
+}
+// Part B: everything from the cache on.
+void enqueue_cached_rest(const float* packed, const float* desc2d_db, const DbCache& c, bool ll, int num_leaf, int flags, float scale_factor,
+                         float match_threshold, const MatchOut& out, const Workspace& w, hipStream_t s) {
     const AttnLayer a1 = attn_layer(packed, 1);
-    launch_qkv_kv(a1, wx, s);                                               // gnn.layers.2: query-side Q, KV, ksum
-    launch_load_columns(nullptr, c.QY, w.Q, w, s);                          // 3D-side Q from the cache
+    launch_load_db_columns(c.Y2, w.Z, c.QY, w.Q, w, s);                     // state = [... | cached Y2], 3D-side Q from the cache
     launch_kv_final(a1, w, 1, c.kvY, s);                                    // query-side sums from the partials, 3D-side sums from the cache
     launch_mlp(a1, w, s);
     enqueue_rounds(packed, 1, desc2d_db, num_leaf, flags, w, s, nullptr, nullptr, nullptr, ll ? c.LL : nullptr, c.ll_layer);
     enqueue_tail(packed, w, scale_factor, match_threshold, out, s, nullptr);
 }
+void enqueue_cached(const float* packed, const float* desc2d_query, const float* desc2d_db, const DbCache& c, bool ll, int num_leaf, int flags,
+                    float scale_factor, float match_threshold, const MatchOut& out, const Workspace& w, hipStream_t s) {
+    enqueue_cached_query(packed, desc2d_query, w, s);
+    enqueue_cached_rest(packed, desc2d_db, c, ll, num_leaf, flags, scale_factor, match_threshold, out, w, s);
+}
 
-// The tensors db_verify_kernel compares and db_snapshot_kernel copies: the database, and the packed-weight ranges the cache is computed
+// The tensors the comparison reads and db_snapshot_kernel copies: the database, and the packed-weight ranges the cache is computed
 // from -- GATs layer 0, attention layers 0 and 1; their 16-bit planes only under the arithmetics that read them -- and the cache against its copy.
 DbPieces db_pieces(const float* packed, const float* desc3d_db, const float* desc2d_db, const Workspace& w, int num_leaf) {
     const AttnLayer a0 = attn_layer(packed, 0), a1 = attn_layer(packed, 1);
@@ -146,29 +162,50 @@ DbPieces db_pieces(const float* packed, const float* desc3d_db, const float* des
     return P;
 }
 
-// The plain forward on a shape of db_reuse_shape: ONE fixed sequence of launches, the device chooses which of them work.  db_verify
-// compares the caller's database and weights with the workspace's snapshot, word for word; the prepare chain is gated on its verdict (a hit:
-// a dozen empty launches; a miss: the cache is rebuilt from this call's inputs), its last launch settles the verdict; db_snapshot keeps the
-// inputs for the next call when this one missed on a database whose fingerprint the previous call had too; the cached chain always runs.
+// The plain forward on a shape of db_reuse_shape: ONE fixed sequence of launches, the device chooses which of them work.
+//   1. Part A of the cached chain, the query side.  Its three GEMM launches of gnn.layers.1 carry the comparison of the caller's database
+//      and weights with the workspace's snapshot, word for word, as extra workgroups (db_rider_share decides which launch compares which
+//      words of which piece; rider 0 of the first launch owns stamp and fingerprint).  A frame whose part A does not take the riding
+//      instantiations (the split arithmetics, a query window of more than DIET_MIN_TILES tiles) runs the same comparison as one launch behind A.
+//   2. The prepare chain on the 3D-side columns of the same layout, gated on the verdict (a hit: a dozen empty launches; a miss: the cache
+//      is rebuilt from this call's inputs, what part A wrote stays); its last launch settles the verdict.
+//   3. db_snapshot keeps the inputs for the next call when this one missed on a database whose fingerprint the previous call had too.
+//   4. Part B of the cached chain, always.
 // No host synchronisation, no memset: the state block is only ever written by these kernels.
 int forward_reusing(const float* packed, const float* desc2d_query, const float* desc3d_db, const float* desc2d_db, int num_leaf, int flags,
-                    float scale_factor, float match_threshold, const MatchOut& out, void* ws, Workspace& w, hipStream_t s) {
+                    float scale_factor, float match_threshold, const MatchOut& out, Workspace& w, hipStream_t s) {
     const ColLayout& L = w.L;
     ReuseState* st = w.R.state;
-    const DbPieces P = db_pieces(packed, desc3d_db, desc2d_db, w, num_leaf);
-    const ReuseStamp stamp = {REUSE_MAGIC, L.b, L.n1p, L.n2, num_leaf, flags};
     const size_t words3 = (size_t)L.b * D * L.n2;
-    launch_db_verify(P, st, stamp, desc3d_db, words3, desc2d_db, words3 * num_leaf, s);
-    // the prepare chain in its own carve-up of the same memory (2 dummy query columns: it ends in front of the reuse area), in the whole
-    // frame's kernel forms
-    Workspace wp = carve_workspace(ws, L.b, 2, L.n2);
-    wp.prec = w.prec;
+    // what every launch of the comparison takes; then per riding launch its share of each piece, its rider count, and the owner role
+    DbRider all = {};
+    all.P = db_pieces(packed, desc3d_db, desc2d_db, w, num_leaf);
+    all.st = st;
+    all.stamp = {REUSE_MAGIC, L.b, L.n1p, L.n2, num_leaf, flags};
+    all.d3 = reinterpret_cast<const unsigned*>(desc3d_db);
+    all.d2db = reinterpret_cast<const unsigned*>(desc2d_db);
+    all.n3 = words3;
+    all.n2 = words3 * num_leaf;
+    DbRider r[DB_RIDER_LAUNCHES];
+    for (int k = 0; k < DB_RIDER_LAUNCHES; ++k) {
+        r[k] = all;
+        r[k].owner = k == 0;
+        r[k].blocks = DB_RIDER_BLOCKS[k];
+        for (int p = 0; p < DB_PIECES; ++p) db_rider_share(all.P.n[p], k, &r[k].lo[p], &r[k].hi[p]);
+    }
+    // every window in the whole frame's kernel forms
+    w.form_tiles = active_tiles(L);
+    const bool rides = db_rider_rides(windowed(w, 0));
+    w.rider = rides ? r : nullptr;
+    enqueue_cached_query(packed, desc2d_query, w, s);
+    w.rider = nullptr;
+    if (!rides) launch_db_verify(all, s);
+    Workspace wp = w;
     wp.L.gate = &st->miss;
-    wp.form_tiles = w.form_tiles = active_tiles(L);
     enqueue_prepare(packed, desc3d_db, desc2d_db, num_leaf, flags, wp, w.R.cache, false, st, s);
-    launch_db_snapshot(P, st, s);
+    launch_db_snapshot(all.P, st, s);
     // (the leaf-logit table stays out of this path: DbCache::LL is carved and never written here)
-    enqueue_cached(packed, desc2d_query, desc2d_db, w.R.cache, false, num_leaf, flags, scale_factor, match_threshold, out, w, s);
+    enqueue_cached_rest(packed, desc2d_db, w.R.cache, false, num_leaf, flags, scale_factor, match_threshold, out, w, s);
     return check_launch(1, "forward");
 }
 
@@ -185,7 +222,7 @@ int forward_impl(const float* packed, const float* desc2d_query, const float* de
     // (The comparison reads 16-byte words: tensors that break the header's alignment rule are simply not compared.)
     const bool aligned = !((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(desc3d_db) | reinterpret_cast<uintptr_t>(desc2d_db)) & 15);
     if (!hk && w.R.present && aligned && !(flags & GATSSPG_FLAG_NO_DB_REUSE))
-        return forward_reusing(packed, desc2d_query, desc3d_db, desc2d_db, num_leaf, flags, scale_factor, match_threshold, out, ws, w, s);
+        return forward_reusing(packed, desc2d_query, desc3d_db, desc2d_db, num_leaf, flags, scale_factor, match_threshold, out, w, s);
     // the state load is fused into the first GATs launch where that kernel supports it (num_leaf == 8, no linear transform)
     const bool fused_load = gats_fuses_state_load(num_leaf, flags, w);
     if (!fused_load) launch_load_state(desc2d_query, desc3d_db, w, s, hk);

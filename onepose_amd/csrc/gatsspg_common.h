@@ -40,7 +40,7 @@ struct ColLayout {
     int side_mask;   // bit 0: 2D-side segments active, bit 1: 3D-side segments (segment-level reduction kernels)
     int xgs;         // XCD granule of the split kernels' tile map, log2 of column tiles (xcd_tile_map_g); always 0
     // nullptr, or a device word written earlier on the stream: while it reads 0 the launch does nothing (launch_is_off).  The plain
-    // forward's database reuse points its prepare chain at the "database or weights changed" word of db_verify_kernel.
+    // forward's database reuse points its prepare chain at the "database or weights changed" word of the comparison (db_verify_share).
     const int* gate;
 };
 
@@ -229,15 +229,16 @@ inline DbCache carve_cache(void* base, int b, int n2) {
 // ---- reuse area of the plain forward (gatsspg_forward): the last piece of a workspace, state that one call leaves for
 //      the next.  A DbCache of the database the workspace saw last, a bitwise snapshot of that database and of the packed-weight
 //      ranges the cache depends on (GATs layer 0, attention layers 0 and 1), a second copy of the cache, and the words below.
-//      db_verify_kernel compares the caller's tensors with the snapshot and the cache with its copy, word for word, at the head of every
-//      call; only a call that finds them all equal reads the cache.  Order: cache | snapshot pieces 0..6 | cache copy | state.
+//      Every call compares the caller's tensors with the snapshot and the cache with its copy, word for word (db_verify_share: as extra
+//      workgroups of the call's first GEMM launches, which touch query columns only, or as the db_verify_kernel launch behind them); only a
+//      call that finds them all equal reads the cache.  Order: cache | snapshot pieces 0..6 | cache copy | state.
 constexpr int REUSE_MAGIC = 0x67447265;
 struct ReuseStamp { int magic, b, n1p, n2, num_leaf, flags; };   // what a snapshot was taken under; n1p: the area's offset and the kernel forms go by it
 struct ReuseState {
     ReuseStamp stamp;
     unsigned fingerprint;   // of the previous call's database (a sum over a strided sample): decides whether a snapshot is worth taking, never a hit
     int snapshot_valid;     // 1: snapshot and cache are those of one database, taken under `stamp`
-    int miss;               // this call: OR-ed to 1 by every mismatch db_verify_kernel finds; the gate of the prepare chain; db_settle_kernel
+    int miss;               // this call: OR-ed to 1 by every mismatch the comparison finds; the gate of the prepare chain; db_settle_kernel
                             // clears it again and leaves the verdict in `hit` (a word of garbage here costs one miss)
     int strike;             // this call: its fingerprint is the previous call's (same stamp)
     int hit;                // this call's outcome, for the caller to read back: 1 = the cache was reused
@@ -272,6 +273,113 @@ inline size_t db_piece_bytes(int p, int b, int n2, int num_leaf) {
 // Where gatsspg_forward takes the reusing path, by shape (gatsspg_gemm_kernels.hip, next to the launch thresholds it goes by)
 bool db_reuse_shape(int b, int n1, int n2);
 
+// The comparison rides on the three GEMM launches of attention layer 0 on the query window -- qkv_kv, mlp0, mlp3, the first launches of a
+// reusing forward, which read neither cache nor database and leave most of the machine idle: extra workgroups behind the GEMM
+// grid of each compare that launch's share of every piece.  Shares in proportion to the launches' measured times at the headline shape
+// (16-tile query window: 13.9 / 21.3 / 19.5 us).  DB_RIDER_BLOCKS: rider workgroups per launch (of the GEMM kernel's 512 threads each);
+// both from the sweep in DESIGN 10d, which is flat around these values.
+constexpr int DB_RIDER_LAUNCHES = 3;
+constexpr int DB_RIDER_WEIGHT[DB_RIDER_LAUNCHES] = {14, 21, 19};
+constexpr int DB_RIDER_BLOCKS[DB_RIDER_LAUNCHES] = {128, 128, 128};
+// words [*lo, *hi) of a piece of n 16-byte words that riding launch k compares: the shares tile [0, n) in order, without gap or overlap
+inline void db_rider_share(unsigned long long n, int k, unsigned long long* lo, unsigned long long* hi) {
+    unsigned long long before = 0, total = 0;
+    for (int i = 0; i < DB_RIDER_LAUNCHES; ++i) {
+        total += DB_RIDER_WEIGHT[i];
+        if (i < k) before += DB_RIDER_WEIGHT[i];
+    }
+    *lo = n * before / total;                          // (n < 2^58: the products stay inside 64 bits)
+    *hi = n * (before + DB_RIDER_WEIGHT[k]) / total;   // k = last: n * total / total = n
+}
+// What a launch that carries the comparison takes: the pieces, its share of each, and what the owner -- rider workgroup 0 of the first
+// riding launch of a call (`owner`), or workgroup 0 of the stand-alone db_verify_kernel -- needs for the stamp and the fingerprint.
+struct DbRider {
+    DbPieces P;
+    unsigned long long lo[DB_PIECES], hi[DB_PIECES];   // this launch compares words [lo, hi) of piece p
+    ReuseState* st;
+    int first_block, blocks;   // workgroups [first_block, first_block + blocks) of the grid are the riders
+    int owner;
+    ReuseStamp stamp;
+    const unsigned *d3, *d2db;      // the database tensors as 4-byte words (fingerprint), n3 / n2 of them
+    unsigned long long n3, n2;
+};
+// the layout of a GEMM launch that carries riders: the kernels take the role from the type (is_rider), so that only the riding launches
+// instantiate it and the whole-frame kernels stay what they are
+struct RiderLayout : ColLayout {
+    DbRider rider;
+};
+template <class LT> inline constexpr bool is_rider = false;
+template <> inline constexpr bool is_rider<RiderLayout> = true;
+
+#if defined(__HIPCC__)
+constexpr int DBV_UNROLL = 4;      // 4 x 2 independent 16-byte loads per thread and trip
+constexpr int DBV_SAMPLES = 1024;  // fingerprint: this many 4-byte words of each database tensor (8 KB in all)
+// words [lo + first, end) of one piece, every stride-th batch: the OR of all differences this thread saw
+__device__ __forceinline__ unsigned db_compare_words(const uint4* __restrict__ cur, const uint4* __restrict__ snap, unsigned long long lo,
+                                                     unsigned long long end, unsigned long long first, unsigned long long stride) {
+    unsigned diff = 0;
+    for (unsigned long long i0 = lo + first; i0 < end; i0 += stride * DBV_UNROLL) {
+        uint4 a[DBV_UNROLL], c[DBV_UNROLL];
+#pragma unroll
+        for (int j = 0; j < DBV_UNROLL; ++j) {
+            const unsigned long long i = i0 + j * stride;
+            a[j] = c[j] = make_uint4(0, 0, 0, 0);
+            if (i < end) {
+                a[j] = cur[i];
+                c[j] = snap[i];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DBV_UNROLL; ++j) diff |= (a[j].x ^ c[j].x) | (a[j].y ^ c[j].y) | (a[j].z ^ c[j].z) | (a[j].w ^ c[j].w);
+    }
+    return diff;
+}
+// The comparison of one workgroup (`rider` of r.blocks, any block size) with its owner duties: every 16-byte word of its launch's share of
+// every piece against the snapshot, as integers; one plain atomicOr per wave that saw a difference, none once the word is set.
+// Nothing waits: the first reader of st->miss is a later launch on the stream.  The owner also checks stamp and snapshot_valid, computes
+// the fingerprint, compares it with the stored one (strike) and stores fingerprint and stamp: exactly once per call.
+__device__ __forceinline__ void db_verify_share(const DbRider& r, int rider) {
+    ReuseState* st = r.st;
+    const bool owner = r.owner && rider == 0;
+    int same_stamp = 0;   // (thread 0 of the owner)
+    if (owner && threadIdx.x == 0) {
+        // a snapshot that is not valid, or was taken under another stamp, is a miss before anything is compared
+        const ReuseStamp o = st->stamp, n = r.stamp;
+        same_stamp = o.magic == n.magic && o.b == n.b && o.n1p == n.n1p && o.n2 == n.n2 && o.num_leaf == n.num_leaf && o.flags == n.flags;
+        if (!same_stamp || st->snapshot_valid != 1) {
+            st->snapshot_valid = 0;
+            atomicOr(&st->miss, 1);
+        }
+    }
+    // A word that already reads non-zero cannot change the outcome any more: the workgroups that start after the first difference was
+    // recorded skip their share (a miss costs a fraction of the pass), and no wave adds an atomic to a word that is set (when nearly
+    // every wave differs -- no valid snapshot -- 28 k atomics on one address took 200 us).  Which workgroups skip depends on their order;
+    // whether the word ends non-zero does not.
+    const bool skip = __hip_atomic_load(&st->miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    const unsigned long long stride = (unsigned long long)r.blocks * blockDim.x, first = (unsigned long long)rider * blockDim.x + threadIdx.x;
+    unsigned diff = 0;
+#pragma unroll 1   // (a real loop: unrolled, the 8 x 4 piece arguments live at once spill scalar registers in the GEMM kernels)
+    for (int p = 0; p < DB_PIECES; ++p) diff |= db_compare_words(r.P.cur[p], r.P.snap[p], r.lo[p], skip ? 0ull : r.hi[p], first, stride);
+    // one plain atomic per wave that saw a difference: the word's value does not depend on who comes first
+    if (__any(diff != 0) && (threadIdx.x & 63) == 0 && !__hip_atomic_load(&st->miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(&st->miss, 1);
+    if (!owner) return;
+    // fingerprint of this call's database, and the new stamp
+    __shared__ unsigned fp;
+    if (threadIdx.x == 0) fp = 0;
+    __syncthreads();
+    unsigned h = 0;
+    for (int k = threadIdx.x; k < DBV_SAMPLES; k += blockDim.x)   // word k * n / SAMPLES of each tensor, weighted by its (odd) position
+        h += r.d3[(unsigned long long)k * r.n3 / DBV_SAMPLES] * (2u * k + 1u) + r.d2db[(unsigned long long)k * r.n2 / DBV_SAMPLES] * (2u * (k + DBV_SAMPLES) + 1u);
+    atomicAdd(&fp, h);   // (integer sum: the same value in every order)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        st->strike = same_stamp && st->fingerprint == fp ? 1 : 0;
+        st->fingerprint = fp;
+        st->stamp = r.stamp;
+    }
+}
+#endif
+
 // ---- workspace carve-up ---------------------------------------------------------------------------
 struct Workspace {
     ColLayout L;
@@ -304,8 +412,19 @@ struct Workspace {
     // 0, or the 64-column tiles of the WHOLE frame this windowed launch is a part of: launch_by_form then goes by them, so that a one-side
     // window takes the kernel form the plain forward's whole-frame launch takes (the reusing path of gatsspg_forward: bit-identical to it)
     int form_tiles;
+    // nullptr, or the DB_RIDER_LAUNCHES rider arguments of a reusing forward's part A (host side only): the fp32 qkv_kv / mlp0 / mlp3
+    // launchers then take the riding instantiation with rider[0 / 1 / 2] (rider_layout)
+    const DbRider* rider;
     ReuseArea R;
 };
+// the layout a riding launch hands its kernel: rider k of the call, behind a GEMM grid of `grid` workgroups
+inline RiderLayout rider_layout(const Workspace& w, int k, int grid) {
+    RiderLayout R;
+    static_cast<ColLayout&>(R) = w.L;
+    R.rider = w.rider[k];
+    R.rider.first_block = grid;
+    return R;
+}
 inline FramesLayout frames_layout(const Workspace& w) {
     FramesLayout F;
     static_cast<ColLayout&>(F) = w.L;
@@ -354,6 +473,7 @@ __host__ __device__ inline const float* mop_seg(const float* Mop, int seg) {
 inline Workspace carve_workspace(void* base, int b, int n1, int n2, int num_leaf = 0) {
     Workspace w;
     w.form_tiles = 0;
+    w.rider = nullptr;
     w.L = make_layout(b, n1, n2);
     w.prec = FP32;
     w.frames = false; w.skip = 0; w.shared_leaf = false;

@@ -50,6 +50,14 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void qkv_kv_k
                                                             const float* __restrict__ Z, float* __restrict__ Qbuf,
                                                             float* __restrict__ kvpart, LT L) {
     if (launch_is_off(L)) return;
+    // the rider role (is_rider<LT>: only the riding launches of a reusing forward instantiate it): workgroups behind the GEMM grid run their
+    // share of the database comparison and return, before any LDS use or barrier of the GEMM
+    if constexpr (is_rider<LT>) {
+        if ((int)blockIdx.x >= L.rider.first_block) {
+            db_verify_share(L.rider, (int)blockIdx.x - L.rider.first_block);
+            return;
+        }
+    }
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: qkv_kv_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
@@ -441,6 +449,14 @@ __global__ __launch_bounds__(T::THREADS, (QF >= 2 ? 5 : PREC >= BF16X6 ? 4 : 1))
                                                    float* __restrict__ U, float* __restrict__ statpart, float* __restrict__ stats,
                                                    int* __restrict__ statcnt, LT L, unsigned long long* trace) {
     if (launch_is_off(L)) return;
+    // the rider role (is_rider<LT>: only the riding launches of a reusing forward instantiate it): workgroups behind the GEMM grid run their
+    // share of the database comparison and return, before any LDS use or barrier of the GEMM
+    if constexpr (is_rider<LT>) {
+        if ((int)blockIdx.x >= L.rider.first_block) {
+            db_verify_share(L.rider, (int)blockIdx.x - L.rider.first_block);
+            return;
+        }
+    }
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp0_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const unsigned long long t_entry = trace ? wall_clock64() : 0;
@@ -617,6 +633,14 @@ __global__ __launch_bounds__(T::THREADS, (PREC >= BF16X6 ? 4 : 1)) void mlp3_ker
                                                    const float* __restrict__ U, const float* __restrict__ stats,
                                                    float* __restrict__ Z, LT L) {
     if (launch_is_off(L)) return;
+    // the rider role (is_rider<LT>: only the riding launches of a reusing forward instantiate it): workgroups behind the GEMM grid run their
+    // share of the database comparison and return, before any LDS use or barrier of the GEMM
+    if constexpr (is_rider<LT>) {
+        if ((int)blockIdx.x >= L.rider.first_block) {
+            db_verify_share(L.rider, (int)blockIdx.x - L.rider.first_block);
+            return;
+        }
+    }
     static_assert(PREC >= FP32 && PREC <= BF16X6, "fp32, bf16x3 or bf16x6 (the fp16 modes: mlp3_sp_kernel)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int rt, ct;
@@ -957,16 +981,26 @@ bool db_reuse_shape(int b, int n1, int n2) {
 //  quarter-fragment form, 2 % slower one frame at a time (profiles/r06b_*, r06c_*); the fp32 arithmetic on the LDS-DMA loop, 8 % slower
 //  per frame (profiles/r04_ab_live_fp32_dma.txt))
 
-template <class T, int PREC, int BT = 0, int DS = 0, int QF = 0>
+// RIDE (the three launchers below): the launch carries rider w.rider[k] of the database comparison -- the kernel on a RiderLayout, the
+// rider's workgroups behind the GEMM grid
+template <class T, int PREC, int BT = 0, int DS = 0, int QF = 0, bool RIDE = false>
 static void launch_qkv_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const int NT = active_tiles(w.L);
     const WPlanes p = a.qkv_planes();
-    with_layout(w, [&](const auto& L) {
+    const int grid = xcd_grid(6, NT);
+    auto go = [&](const auto& L, int riders) {
         using LT = std::decay_t<decltype(L)>;
         allow_big_lds<qkv_kv_kernel<T, PREC, BT, DS, QF, LT>>();
-        GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_kernel<T, PREC, BT, DS, QF, LT>), dim3(xcd_grid(6, NT)), dim3(T::THREADS), (smem_bytes<T, PREC>() + 512 * BT), s,
+        GATSSPG_LAUNCH(hk, KID_QKV_KV, s, (qkv_kv_kernel<T, PREC, BT, DS, QF, LT>), dim3(grid + riders), dim3(T::THREADS), (smem_bytes<T, PREC>() + 512 * BT), s,
                        a.WQKV(), a.BQKV(), p.hi, p.lo, p.lo2, w.Z, w.Q, w.kvpart, L);
-    });
+    };
+    if constexpr (RIDE) go(rider_layout(w, 0, grid), w.rider[0].blocks);
+    else with_layout(w, [&](const auto& L) { go(L, 0); });
+}
+// Whether part A of a reusing forward (wx: its query window) carries the comparison: the fp32 arithmetic on the small-launch forms of
+// qkv_kv / mlp0 and the whole frame's tall mlp3 tile -- the only riding instantiations.  Every other frame keeps the stand-alone launch.
+bool db_rider_rides(const Workspace& wx) {
+    return wx.prec == FP32 && !wx.frames && active_tiles(wx.L) <= diet_min_tiles() && (wx.form_tiles ? wx.form_tiles : active_tiles(wx.L)) > small_nt3();
 }
 
 // The fp16 modes run on the LDS-DMA loop (their planes carry the pack-time scale that only those kernels undo); the bf16 modes stay on the
@@ -977,6 +1011,7 @@ void launch_qkv_kv(const AttnLayer& a, const Workspace& w, hipStream_t s, Profil
     else if (w.prec == BF16X3) launch_qkv_t<QkvTileW8, BF16X3>(a, w, s, hk);
     else if (w.prec == BF16X6) launch_qkv_t<QkvTileW8, BF16X6>(a, w, s, hk);
     else if (active_tiles(w.L) > diet_min_tiles()) launch_qkv_t<QkvTileW8, FP32, 1, 1, 1>(a, w, s, hk);   // quarter fragments + bias table (80 VGPRs)
+    else if (w.rider) launch_qkv_t<QkvTileW8, FP32, 0, 1, 0, true>(a, w, s, hk);   // (db_rider_rides: a small launch)
     else launch_qkv_t<QkvTileW8, FP32, 0, 1>(a, w, s, hk);   // small launches: the two-half fragment loop
 }
 
@@ -995,29 +1030,35 @@ void launch_kv_final(const AttnLayer& a, const Workspace& w, int cross, const fl
 // instantiations keep it: their register allocation sits at the 128 cap, and without the dead branch the six-term kernel picked up a
 // 12-byte spill -- they stay exactly the round-5 kernels.  (Finishing the statistics in the last workgroups instead of the stat_final launch:
 // 1231 vs 1232 frames/s in flight, 5.3 us longer mlp0 for the 4.8 us launch it saves, profiles/r04_stat_fused_ab.txt; removed.)
-template <class T, int PREC, int BT = 0, int QF = 0>
+template <class T, int PREC, int BT = 0, int QF = 0, bool RIDE = false>
 static void launch_mlp0_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     constexpr int SF = PREC != FP32;
     const WPlanes p = a.w0_planes();
     const int NT = active_tiles(w.L) / (T::BN / MLP0_BN);
-    with_layout(w, [&](const auto& L) {
+    const int grid = xcd_grid(512 / T::BM, NT);
+    auto go = [&](const auto& L, int riders) {
         using LT = std::decay_t<decltype(L)>;
         allow_big_lds<mlp0_kernel<T, PREC, BT, QF, SF, LT>>();
-        GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, PREC, BT, QF, SF, LT>), dim3(xcd_grid(512 / T::BM, NT)), dim3(T::THREADS),
+        GATSSPG_LAUNCH(hk, KID_MLP0, s, (mlp0_kernel<T, PREC, BT, QF, SF, LT>), dim3(grid + riders), dim3(T::THREADS),
                        (smem_bytes<T, PREC>() + sizeof(float) * AttnFoldHooks::ZP_FLOATS + 512 * BT), s, a.W0(), a.B0(), p.hi, p.lo, p.lo2, w.Z, w.Q,
                        w.Mop, w.Mpl, w.ksumT, w.U, w.statpart, w.stats, nullptr, L, g_trace);
-    });
+    };
+    if constexpr (RIDE) go(rider_layout(w, 1, grid), w.rider[1].blocks);
+    else with_layout(w, [&](const auto& L) { go(L, 0); });
 }
-template <class T, int PREC, int DS = 0>
+template <class T, int PREC, int DS = 0, bool RIDE = false>
 static void launch_mlp3_t(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
     const WPlanes p = a.w3_planes();
     const int NT = active_tiles(w.L) / (T::BN / 64);
-    with_layout(w, [&](const auto& L) {
+    const int grid = xcd_grid(256 / T::BM, NT);
+    auto go = [&](const auto& L, int riders) {
         using LT = std::decay_t<decltype(L)>;
         allow_big_lds<mlp3_kernel<T, PREC, DS, LT>>();
-        GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, PREC, DS, LT>), dim3(xcd_grid(256 / T::BM, NT)), dim3(T::THREADS),
+        GATSSPG_LAUNCH(hk, KID_MLP3, s, (mlp3_kernel<T, PREC, DS, LT>), dim3(grid + riders), dim3(T::THREADS),
                        (smem_bytes<T, PREC>()), s, a.W3(), a.B3(), p.hi, p.lo, p.lo2, w.U, w.stats, w.Z, L);
-    });
+    };
+    if constexpr (RIDE) go(rider_layout(w, 2, grid), w.rider[2].blocks);
+    else with_layout(w, [&](const auto& L) { go(L, 0); });
 }
 
 void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHook* hk) {
@@ -1027,6 +1068,7 @@ void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHo
     else if (w.prec == BF16X3) launch_mlp0_t<Mlp0TileW8, BF16X3>(a, w, s, hk);
     else if (w.prec == BF16X6) launch_mlp0_t<Mlp0TileW8, BF16X6>(a, w, s, hk);
     else if (active_tiles(w.L) > diet_min_tiles()) launch_mlp0_t<Mlp0TileW8, FP32, 1, 1>(a, w, s, hk);   // quarter fragments + bias table (94 VGPRs)
+    else if (w.rider) launch_mlp0_t<Mlp0TileW8, FP32, 0, 0, true>(a, w, s, hk);   // (db_rider_rides: a small launch)
     else launch_mlp0_t<Mlp0TileW8, FP32>(a, w, s, hk);   // small launches: the two-half fragment loop (126 VGPRs)
     // the InstanceNorm reducer is a launch of its own (see launch_mlp0_t)
     with_layout(w, [&](const auto& L) {
@@ -1035,6 +1077,7 @@ void launch_mlp(const AttnLayer& a, const Workspace& w, hipStream_t s, ProfileHo
     if (is_fp16(w.prec)) launch_mlp3_sp(a, w, s, hk);
     else if (w.prec == BF16X3) launch_mlp3_t<Mlp3TileTallW8, BF16X3>(a, w, s, hk);
     else if (w.prec == BF16X6) launch_mlp3_t<Mlp3TileTallW8, BF16X6>(a, w, s, hk);
+    else if (w.rider) launch_mlp3_t<Mlp3TileTallW8, FP32, 1, true>(a, w, s, hk);   // (db_rider_rides: the whole frame takes the tall tile)
     else   // the K-split tile adds its two halves last: every frame of a frames layout takes the tile it takes alone
         launch_by_form(
             w, [&](int tiles) { return tiles <= small_nt3(); }, [&](const Workspace& v) { launch_mlp3_t<Mlp3TileS, FP32>(a, v, s, hk); },

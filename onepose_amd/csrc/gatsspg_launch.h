@@ -88,14 +88,20 @@ void launch_load_columns(const float* c2, const float* c3, float* dst, const Wor
 void launch_store_state(const float* src, float* out2d, float* out3d, const Workspace& w, hipStream_t s, ProfileHook* hk = nullptr);
 // the final KV sums of the 3D-side segments (w.kvfin, written by launch_kv_final) into a database cache's kvY [b][4][KVP]
 void launch_store_kv_sums(float* kvY, const Workspace& w, hipStream_t s);
-// The plain forward's database reuse.  launch_db_verify: st->miss (left 0 by the previous call) becomes 1 unless every
-// 16-byte word of the pieces equals its snapshot, the snapshot is valid and was taken under `stamp`; also st->strike (the database's
-// fingerprint, a sum over a strided sample of d3 [n3 words] and d2db [n2 words], equals the previous call's) and the new fingerprint and stamp.
+// the cached chain's two copies in one launch: compact [b,256,n2] tensors s0 / s1 into the 3D-side columns of d0 / d1 ([256][ld])
+void launch_load_db_columns(const float* s0, float* d0, const float* s1, float* d1, const Workspace& w, hipStream_t s);
+// The plain forward's database reuse.  The comparison (db_verify_share, gatsspg_common.h): st->miss (left 0 by the previous
+// call) becomes 1 unless every 16-byte word of the pieces equals its snapshot, the snapshot is valid and was taken under r.stamp; also
+// st->strike (the database's fingerprint, a sum over a strided sample of r.d3 [n3 words] and r.d2db [n2 words], equals the previous call's)
+// and the new fingerprint and stamp.  It rides on the fp32 GEMM launches of the query window where db_rider_rides says so (Workspace::rider;
+// launch_qkv_kv and launch_mlp then start r[k].blocks more workgroups); launch_db_verify is the same comparison as one launch of its own,
+// for every other frame (r: pieces, state, stamp and tensors; shares and roles are set here).
 // launch_db_settle, the last launch of the prepare chain (one workgroup, never gated): on a miss launch_store_kv_sums' work; st->hit = !miss,
 // st->copy = miss with a strike, st->snapshot_valid set by such a miss and cleared by any other; st->miss cleared for the next call.
 // launch_db_snapshot: copies the pieces into the snapshot where st->copy says so.
+bool db_rider_rides(const Workspace& wx);   // wx: the query window of the call (gatsspg_gemm_kernels.hip)
 void launch_db_settle(float* kvY, const Workspace& w, ReuseState* st, hipStream_t s);
-void launch_db_verify(const DbPieces& P, ReuseState* st, const ReuseStamp& stamp, const float* d3, size_t n3, const float* d2db, size_t n2, hipStream_t s);
+void launch_db_verify(DbRider r, hipStream_t s);
 void launch_db_snapshot(const DbPieces& P, ReuseState* st, hipStream_t s);
 // h3: where the layer reads the 3D-point descriptors from: nullptr = the state Z; otherwise the caller's compact
 // [b,256,n2] tensor (first layer of a forward: the state load is fused, `dq` is copied into the 2D side by spare workgroups)

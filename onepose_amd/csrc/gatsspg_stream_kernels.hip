@@ -86,6 +86,33 @@ void launch_load_columns(const float* c2, const float* c3, float* dst, const Wor
         hipLaunchKernelGGL(load_state_kernel<std::decay_t<decltype(L)>>, dim3(D, w.L.b), dim3(256), 0, s, c2, c3, dst, L, 0);
     });
 }
+// Two compact [b,256,n2] tensors into the 3D-side columns of two [256][ld] buffers in ONE launch (blockIdx.z = pair): the cached chain's
+// Y2 -> state and QY -> Q.  Per pair what load_state_kernel does for its 3D side (pads zeroed); the query side is not touched.
+template <class LT = ColLayout>
+__global__ __launch_bounds__(256) void load_db_columns_kernel(const float* __restrict__ s0, float* __restrict__ d0, const float* __restrict__ s1,
+                                                              float* __restrict__ d1, LT L) {
+    const int ch = blockIdx.x, f = blockIdx.y;
+    const float* y = (blockIdx.z ? s1 : s0) + ((size_t)db_frame(L, f) * D + ch) * L.n2;
+    float* zr = (blockIdx.z ? d1 : d0) + (size_t)ch * L.ld + (size_t)f * L.np + L.n1p;
+    const bool vec = (L.n2 & 3) == 0;
+    for (int j = threadIdx.x * 4; j < L.n2p; j += 1024) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (vec && j + 3 < L.n2) {
+            v = *reinterpret_cast<const float4*>(y + j);
+        } else {
+            if (j < L.n2) v.x = y[j];
+            if (j + 1 < L.n2) v.y = y[j + 1];
+            if (j + 2 < L.n2) v.z = y[j + 2];
+            if (j + 3 < L.n2) v.w = y[j + 3];
+        }
+        *reinterpret_cast<float4*>(zr + j) = v;
+    }
+}
+void launch_load_db_columns(const float* s0, float* d0, const float* s1, float* d1, const Workspace& w, hipStream_t s) {
+    with_layout(w, [&](const auto& L) {
+        hipLaunchKernelGGL(load_db_columns_kernel<std::decay_t<decltype(L)>>, dim3(D, w.L.b, 2), dim3(256), 0, s, s0, d0, s1, d1, L);
+    });
+}
 void launch_store_state(const float* src, float* out2d, float* out3d, const Workspace& w, hipStream_t s, ProfileHook*) {
     hipLaunchKernelGGL(store_state_kernel, dim3(D, w.L.b), dim3(256), 0, s, src, out2d, out3d, w.L);
 }
@@ -104,68 +131,17 @@ void launch_store_kv_sums(float* kvY, const Workspace& w, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------------------------
 // database reuse of the plain forward: full bitwise comparison of the caller's database and weight ranges with the
-// snapshot in the workspace, and the snapshot copy.  Both walk every piece in 16-byte words, grid-strided, blockIdx.y = piece.
+// snapshot in the workspace, and the snapshot copy.  The comparison itself is db_verify_share (gatsspg_common.h): on the fp32 path it
+// rides on the GEMM launches of the query window (gatsspg_gemm_kernels.hip); this is its stand-alone launch for every other frame.  Both
+// kernels here are ONE bounded one-dimensional grid whose workgroups walk all pieces in 16-byte words, grid-strided: no workgroup is
+// started for an empty piece.
 // ------------------------------------------------------------------------------------------------------
-constexpr int DBV_BLOCKS = 1024, DBV_UNROLL = 4;   // workgroups per piece (blockIdx.y = piece); 4 x 2 independent 16-byte loads per thread and trip
-constexpr int DBS_BLOCKS = 128;                    // workgroups per piece of the snapshot copy
-constexpr int DBV_SAMPLES = 1024;                  // fingerprint: this many words of each database tensor (8 KB in all)
-__global__ __launch_bounds__(256) void db_verify_kernel(DbPieces P, ReuseState* st, ReuseStamp stamp, const unsigned* __restrict__ d3,
-                                                        unsigned long long n3, const unsigned* __restrict__ d2db, unsigned long long n2) {
-    const uint4* __restrict__ cur = P.cur[blockIdx.y];
-    const uint4* __restrict__ snap = P.snap[blockIdx.y];
-    const bool owner = blockIdx.x == 0 && blockIdx.y == 0;   // workgroup (0, 0) also owns the state block
-    __shared__ int same_stamp;
-    if (owner && threadIdx.x == 0) {
-        // a snapshot that is not valid, or was taken under another stamp, is a miss before anything is compared
-        const ReuseStamp o = st->stamp;
-        same_stamp = o.magic == stamp.magic && o.b == stamp.b && o.n1p == stamp.n1p && o.n2 == stamp.n2 && o.num_leaf == stamp.num_leaf && o.flags == stamp.flags;
-        if (!same_stamp || st->snapshot_valid != 1) {
-            st->snapshot_valid = 0;
-            atomicOr(&st->miss, 1);
-        }
-    }
-    // A word that already reads non-zero cannot change the outcome any more: the workgroups that start after the first difference was
-    // recorded skip their share (a miss costs a fraction of the pass), and no wave adds an atomic to a word that is set (when nearly
-    // every wave differs -- no valid snapshot -- 28 k atomics on one address took 200 us).  Which workgroups skip depends on their order;
-    // whether the word ends non-zero does not.
-    const unsigned long long total = __hip_atomic_load(&st->miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0ull : P.n[blockIdx.y];
-    const unsigned long long stride = (unsigned long long)gridDim.x * 256;
-    unsigned diff = 0;
-    for (unsigned long long i0 = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i0 < total; i0 += stride * DBV_UNROLL) {
-        uint4 a[DBV_UNROLL], c[DBV_UNROLL];
-#pragma unroll
-        for (int j = 0; j < DBV_UNROLL; ++j) {
-            const unsigned long long i = i0 + j * stride;
-            a[j] = c[j] = make_uint4(0, 0, 0, 0);
-            if (i < total) {
-                a[j] = cur[i];
-                c[j] = snap[i];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < DBV_UNROLL; ++j) diff |= (a[j].x ^ c[j].x) | (a[j].y ^ c[j].y) | (a[j].z ^ c[j].z) | (a[j].w ^ c[j].w);
-    }
-    // one plain atomic per wave that saw a difference: the word's value does not depend on who comes first
-    if (__any(diff != 0) && (threadIdx.x & 63) == 0 && !__hip_atomic_load(&st->miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(&st->miss, 1);
-    if (!owner) return;
-    // fingerprint of this call's database, and the new stamp
-    __shared__ unsigned fp;
-    if (threadIdx.x == 0) fp = 0;
-    __syncthreads();
-    unsigned h = 0;
-    for (int k = threadIdx.x; k < DBV_SAMPLES; k += 256)   // word k * n / SAMPLES of each tensor, weighted by its (odd) position
-        h += d3[(unsigned long long)k * n3 / DBV_SAMPLES] * (2u * k + 1u) + d2db[(unsigned long long)k * n2 / DBV_SAMPLES] * (2u * (k + DBV_SAMPLES) + 1u);
-    atomicAdd(&fp, h);   // (integer sum: the same value in every order)
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        st->strike = same_stamp && st->fingerprint == fp ? 1 : 0;
-        st->fingerprint = fp;
-        st->stamp = stamp;
-    }
-}
+constexpr int DBV_BLOCKS = 2048;   // workgroups of the stand-alone comparison (256 threads: 4 x 2 independent 16-byte loads per thread and trip)
+constexpr int DBS_BLOCKS = 512;    // workgroups of the snapshot copy (a hit pays for this grid's start)
+__global__ __launch_bounds__(256) void db_verify_kernel(DbRider r) { db_verify_share(r, blockIdx.x); }
 // The last launch of the gated prepare chain, ONE workgroup, never gated itself: on a miss the KV sums of the 3D-side segments into the
 // cache (store_kv_sums_kernel's work); then the call's verdict -- hit, whether db_snapshot_kernel copies, the snapshot's validity -- and the
-// miss word cleared for the next call's db_verify_kernel (this workgroup is its last reader: no memset in front of every call).
+// miss word cleared for the next call's comparison (this workgroup is its last reader: no memset in front of every call).
 __global__ __launch_bounds__(1024) void db_settle_kernel(const float* __restrict__ kvfin, float* __restrict__ kvY, int b, ReuseState* st) {
     const int miss = st->miss, strike = st->strike;
     if (miss) {
@@ -185,20 +161,26 @@ __global__ __launch_bounds__(1024) void db_settle_kernel(const float* __restrict
 }
 __global__ __launch_bounds__(256) void db_snapshot_kernel(DbPieces P, const ReuseState* st) {
     if (!st->copy) return;
-    const uint4* __restrict__ cur = P.cur[blockIdx.y];
-    uint4* __restrict__ snap = P.snap[blockIdx.y];
-    const unsigned long long total = P.n[blockIdx.y], stride = (unsigned long long)gridDim.x * 256;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) snap[i] = cur[i];
+    const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+#pragma unroll
+    for (int p = 0; p < DB_PIECES; ++p) {
+        const uint4* __restrict__ cur = P.cur[p];
+        uint4* __restrict__ snap = P.snap[p];
+        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < P.n[p]; i += stride) snap[i] = cur[i];
+    }
 }
-void launch_db_verify(const DbPieces& P, ReuseState* st, const ReuseStamp& stamp, const float* d3, size_t n3, const float* d2db, size_t n2, hipStream_t s) {
-    hipLaunchKernelGGL(db_verify_kernel, dim3(DBV_BLOCKS, DB_PIECES), dim3(256), 0, s, P, st, stamp, reinterpret_cast<const unsigned*>(d3), (unsigned long long)n3,
-                       reinterpret_cast<const unsigned*>(d2db), (unsigned long long)n2);
+void launch_db_verify(DbRider r, hipStream_t s) {
+    for (int p = 0; p < DB_PIECES; ++p) { r.lo[p] = 0; r.hi[p] = r.P.n[p]; }   // every word of every piece, in this one launch
+    r.first_block = 0;
+    r.blocks = DBV_BLOCKS;
+    r.owner = 1;
+    hipLaunchKernelGGL(db_verify_kernel, dim3(DBV_BLOCKS), dim3(256), 0, s, r);
 }
 void launch_db_settle(float* kvY, const Workspace& w, ReuseState* st, hipStream_t s) {
     hipLaunchKernelGGL(db_settle_kernel, dim3(1), dim3(1024), 0, s, w.kvfin, kvY, w.L.b, st);
 }
 void launch_db_snapshot(const DbPieces& P, ReuseState* st, hipStream_t s) {
-    hipLaunchKernelGGL(db_snapshot_kernel, dim3(DBS_BLOCKS, DB_PIECES), dim3(256), 0, s, P, st);   // (a hit pays for this grid's start)
+    hipLaunchKernelGGL(db_snapshot_kernel, dim3(DBS_BLOCKS), dim3(256), 0, s, P, st);
 }
 
 // ------------------------------------------------------------------------------------------------------
