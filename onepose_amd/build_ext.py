@@ -44,8 +44,8 @@ LIBRARIES = (
     Library("pnp", ["pnp_kernels.hip"], ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("pnp.h"), _include("pnp_batch.h")]),
     Library("superglue", [os.path.join("superglue", "superglue.hip"), os.path.join("superglue", "nn_matcher.hip")],
             ["capi_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", _include("superglue", "superglue.h"), _include("superglue", "nn_matcher.h")]),
-    Library("det", [os.path.join("detector", "detector.hip")],
-            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h")]),
+    Library("det", [os.path.join("detector", "detector.hip"), os.path.join("detector", "flow.hip")],
+            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h"), _include("detector", "flow.h")]),
     Library("map", [os.path.join("mapping", "mapping.hip"), os.path.join("mapping", "bundle_adjust.hip")],
             ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h"), _include("mapping", "bundle_adjust.h")]),
 )

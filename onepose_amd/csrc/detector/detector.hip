@@ -366,7 +366,7 @@ int ransac(const float* kpts0, const int32_t* n0, const int64_t* matches0, const
 
 extern "C" {
 
-int det_version(void) { return 1; }
+int det_version(void) { return 2; }   // 2: the flow step (flow.hip, include/detector/flow.h) joined the library
 const char* det_last_error(void) { return g_err; }
 
 size_t det_workspace_bytes(int V, int cap0, int iterations) {
