@@ -46,8 +46,10 @@ LIBRARIES = (
             ["capi_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", _include("superglue", "superglue.h"), _include("superglue", "nn_matcher.h")]),
     Library("det", [os.path.join("detector", "detector.hip"), os.path.join("detector", "flow.hip")],
             ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h"), _include("detector", "flow.h")]),
-    Library("map", [os.path.join("mapping", "mapping.hip"), os.path.join("mapping", "bundle_adjust.hip")],
-            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h"), _include("mapping", "bundle_adjust.h")]),
+    Library("map", [os.path.join("mapping", "mapping.hip"), os.path.join("mapping", "bundle_adjust.hip"),
+                    os.path.join("mapping", "track_update.hip")],
+            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h"), _include("mapping", "bundle_adjust.h"),
+             _include("mapping", "track_update.h")]),
 )
 # views of the table under the names other modules use
 LIB_PATH, SPP_LIB_PATH, PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH, MAP_LIB_PATH = (lib.path for lib in LIBRARIES)

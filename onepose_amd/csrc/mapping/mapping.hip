@@ -560,7 +560,7 @@ constexpr int MAX_IMAGES = 1 << 16, MAX_PAIRS = 1 << 22, MAX_TRACKS = 1 << 24, M
 
 extern "C" {
 
-int map_version(void) { return 2; }
+int map_version(void) { return 3; }
 const char* map_last_error(void) { return g_err; }
 
 size_t map_workspace_bytes(int n_points) {

@@ -1,0 +1,418 @@
+"""numpy oracle of the tracker's map update step (include/mapping/track_update.h) and of the state machine around it.
+
+``update`` restates the header expression by expression: every product and sum is an elementwise numpy operation in the order
+the kernels use (no ``np.dot``: BLAS may reorder a sum), vectorised over the pairs only, which changes no value.  The HIP
+kernels are compared bit for bit against it.  ``Tracker`` is the keyframe tracker's state machine (the bookkeeping of
+``onepose_amd.tracker.BATracker``) with the numerical cores injected as callables.
+"""
+import collections
+
+import numpy as np
+
+MAX_KEYPOINTS = 8192
+SUMMARY_ENTRIES = 8
+JACOBI_SWEEPS = 16
+JACOBI_STOP = 1e-30
+
+Update = collections.namedtuple("Update", "pair_kf pair_q q_pt_ids pair_dist new_points unmatched_q median summary")
+
+
+def canonical(a):
+    """Every NaN as the one quiet NaN the ABI writes."""
+    a = np.array(a, dtype=np.float64)
+    a[np.isnan(a)] = np.nan
+    return a
+
+
+def tri4(i, j):
+    if i > j:
+        i, j = j, i
+    return i * 4 - i * (i - 1) // 2 + (j - i)
+
+
+def project(X, K, pose):
+    """tracking_utils.py:74-88 on X [n, 3]: Xc_r = (R_r0 X_0 + R_r1 X_1) + R_r2 X_2 + t_r, h = K Xc row by row, x = h_0 / h_2."""
+    X, K, pose = np.asarray(X, np.float64), np.asarray(K, np.float64), np.asarray(pose, np.float64)
+    with np.errstate(all="ignore"):
+        c = [((pose[r, 0] * X[:, 0] + pose[r, 1] * X[:, 1]) + pose[r, 2] * X[:, 2]) + pose[r, 3] for r in range(3)]
+        h = [(K[r, 0] * c[0] + K[r, 1] * c[1]) + K[r, 2] * c[2] for r in range(3)]
+        return np.stack([h[0] / h[2], h[1] / h[2]], axis=1)
+
+
+def reproj_dist(X, K, pose, xy):
+    xy = np.asarray(xy, np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        p = project(X, K, pose)
+        dx, dy = p[:, 0] - xy[:, 0], p[:, 1] - xy[:, 1]
+        return np.sqrt(dx * dx + dy * dy)
+
+
+def projection_matrix(K, pose):
+    """P = K pose[:3], row dots with the index ascending."""
+    K, pose = np.asarray(K, np.float64), np.asarray(pose, np.float64)
+    P = np.empty((3, 4))
+    for r in range(3):
+        for c in range(4):
+            P[r, c] = (K[r, 0] * pose[0, c] + K[r, 1] * pose[1, c]) + K[r, 2] * pose[2, c]
+    return P
+
+
+def jacobi4(S):
+    """Cyclic Jacobi on n packed symmetric 4 x 4 matrices (S: list of 10 arrays [n], upper triangle row by row), every element
+    taking exactly the rotations and the stopping decision the scalar loop of the kernel takes.  Returns (S, V[4][4])."""
+    n = S[0].shape[0]
+    S = [s.copy() for s in S]
+    V = [[np.ones(n) if i == j else np.zeros(n) for j in range(4)] for i in range(4)]
+    running = np.ones(n, dtype=bool)
+    with np.errstate(all="ignore"):
+        for _ in range(JACOBI_SWEEPS):
+            off, diag = np.zeros(n), np.zeros(n)
+            for p in range(4):
+                diag = diag + S[tri4(p, p)] * S[tri4(p, p)]
+                for q in range(p + 1, 4):
+                    off = off + S[tri4(p, q)] * S[tri4(p, q)]
+            running = running & (off > JACOBI_STOP * diag)
+            if not running.any():
+                break
+            for p in range(3):
+                for q in range(p + 1, 4):
+                    apq = S[tri4(p, q)]
+                    rot = running & (apq != 0.0)
+                    theta = (S[tri4(q, q)] - S[tri4(p, p)]) / (2.0 * apq)
+                    t = np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                    c = 1.0 / np.sqrt(t * t + 1.0)
+                    s = t * c
+                    for k in range(4):
+                        if k != p and k != q:
+                            akp, akq = S[tri4(k, p)], S[tri4(k, q)]
+                            S[tri4(k, p)] = np.where(rot, c * akp - s * akq, akp)
+                            S[tri4(k, q)] = np.where(rot, s * akp + c * akq, akq)
+                        vkp, vkq = V[k][p], V[k][q]
+                        V[k][p] = np.where(rot, c * vkp - s * vkq, vkp)
+                        V[k][q] = np.where(rot, s * vkp + c * vkq, vkq)
+                    S[tri4(p, p)] = np.where(rot, S[tri4(p, p)] - t * apq, S[tri4(p, p)])
+                    S[tri4(q, q)] = np.where(rot, S[tri4(q, q)] + t * apq, S[tri4(q, q)])
+                    S[tri4(p, q)] = np.where(rot, 0.0, apq)
+    return S, V
+
+
+def triangulate_raw(P1, P2, xy1, xy2):
+    """ba_tracker.py:251-265 on n pairs: the rows of A, M = A^T A summed over the rows in ascending order, the eigenvector of
+    the smallest eigenvalue (ties: lowest index), X = v[:3] / v[3].  NaN as it comes."""
+    P1, P2 = np.asarray(P1, np.float64).reshape(3, 4), np.asarray(P2, np.float64).reshape(3, 4)
+    a = np.asarray(xy1, np.float32).astype(np.float64).reshape(-1, 2)
+    b = np.asarray(xy2, np.float32).astype(np.float64).reshape(-1, 2)
+    n = a.shape[0]
+    if n == 0:
+        return np.zeros((0, 3))
+    with np.errstate(all="ignore"):
+        A = [[a[:, 0] * P1[2, c] - P1[0, c] for c in range(4)], [a[:, 1] * P1[2, c] - P1[1, c] for c in range(4)],
+             [b[:, 0] * P2[2, c] - P2[0, c] for c in range(4)], [b[:, 1] * P2[2, c] - P2[1, c] for c in range(4)]]
+        S = [None] * 10
+        for i in range(4):
+            for j in range(i, 4):
+                S[tri4(i, j)] = ((A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j]) + A[3][i] * A[3][j]
+        S, V = jacobi4(S)
+        best = S[tri4(0, 0)]
+        v = [V[k][0] for k in range(4)]
+        for i in range(1, 4):
+            better = S[tri4(i, i)] < best
+            best = np.where(better, S[tri4(i, i)], best)
+            v = [np.where(better, V[k][i], v[k]) for k in range(4)]
+        return np.stack([v[0] / v[3], v[1] / v[3], v[2] / v[3]], axis=1)
+
+
+def triangulate_pairs(P1, P2, xy1, xy2):
+    """What trk_triangulate_pairs writes."""
+    return canonical(triangulate_raw(P1, P2, xy1, xy2))
+
+
+def median(d):
+    """numpy's median, restated: the middle order statistic, (a + b) / 2 of the two middle ones for an even count, NaN when any
+    value is NaN or there is none."""
+    d = np.asarray(d, np.float64)
+    if d.size == 0 or np.isnan(d).any():
+        return np.float64(np.nan)
+    s = np.sort(d)
+    n = s.size
+    with np.errstate(all="ignore"):
+        return s[n // 2] if n % 2 else (s[n // 2 - 1] + s[n // 2]) / 2.0
+
+
+def gate_median(dist, factor):
+    """What trk_gate_median writes: (factor x median, keep [n] int32)."""
+    dist = np.asarray(dist, np.float64)
+    with np.errstate(all="ignore"):
+        med = canonical(factor * median(dist))[()]
+        return med, (dist < med).astype(np.int32)
+
+
+def update(matches0, kf_xy, q_xy, kf_pt_ids, points, K_kf, K_q, pose_kf, pose_q, gate_factor=1.2, max_reproj=20.0, max_z=0.15):
+    """The whole step, as the header of trk_update states it.  Arrays come back at the sizes the ABI writes them (pair_* and
+    q_pt_ids [n_kf], unmatched_q [n_q], padded as stated there) except new_points, which holds the kept rows only."""
+    matches0, kf_pt_ids = np.asarray(matches0).astype(np.int64).reshape(-1), np.asarray(kf_pt_ids).astype(np.int64).reshape(-1)
+    kf_xy, q_xy = np.asarray(kf_xy, np.float32).reshape(-1, 2), np.asarray(q_xy, np.float32).reshape(-1, 2)
+    points = np.asarray(points, np.float64).reshape(-1, 3)
+    n_kf, n_q, n_points = kf_xy.shape[0], q_xy.shape[0], points.shape[0]
+    assert matches0.shape == (n_kf,) and kf_pt_ids.shape == (n_kf,)
+
+    # 1. pairs
+    valid = (matches0 >= 0) & (matches0 < n_q)
+    ignored = int(((matches0 >= n_q) | (matches0 < -1)).sum())
+    i_of = np.where(valid)[0]
+    j_of = matches0[i_of]
+    m = i_of.size
+    # 2. classes
+    ids = kf_pt_ids[i_of]
+    known = (ids >= 0) & (ids < n_points)
+    cand = ids == -1
+    ignored += int((~known & ~cand).sum())
+
+    pair_kf, pair_q, q_pt_ids = (np.full(n_kf, -1, np.int32) for _ in range(3))
+    pair_dist = np.full((n_kf, 2), np.nan)
+    pair_kf[:m], pair_q[:m] = i_of, j_of
+
+    # 3. known pairs
+    kk = np.where(known)[0]
+    d = canonical(reproj_dist(points[ids[kk]], K_q, pose_q, q_xy[j_of[kk]]))
+    pair_dist[kk, 0] = d
+    med, keep = gate_median(d, gate_factor)
+    q_pt_ids[kk[keep == 1]] = ids[kk[keep == 1]]
+
+    # 4. candidates
+    cc = np.where(cand)[0]
+    X = triangulate_raw(projection_matrix(K_kf, pose_kf), projection_matrix(K_q, pose_q), kf_xy[i_of[cc]], q_xy[j_of[cc]])
+    rep_q = reproj_dist(X, K_q, pose_q, q_xy[j_of[cc]])
+    rep_kf = reproj_dist(X, K_kf, pose_kf, kf_xy[i_of[cc]])
+    finite = np.isfinite(X).all(axis=1) & np.isfinite(rep_q) & np.isfinite(rep_kf)
+    with np.errstate(all="ignore"):
+        kept = finite & ~((rep_q > max_reproj) | (rep_kf > max_reproj) | (X[:, 2] > max_z))
+    pair_dist[cc, 0], pair_dist[cc, 1] = canonical(rep_q), canonical(rep_kf)
+    # 5. ids
+    n_new = int(kept.sum())
+    q_pt_ids[cc[kept]] = n_points + np.arange(n_new)
+    new_points = X[kept]
+
+    # 6. unmatched
+    named = np.zeros(n_q, dtype=bool)
+    named[j_of] = True
+    free = np.where(~named)[0]
+    unmatched_q = np.full(n_q, -1, np.int32)
+    unmatched_q[:free.size] = free
+
+    summary = np.array([m, kk.size, int(keep.sum()), cc.size, n_new, int((~finite).sum()), ignored, free.size], np.int32)
+    return Update(pair_kf, pair_q, q_pt_ids, pair_dist, new_points, unmatched_q, np.array([med]), summary)
+
+
+class Tracker:
+    """The keyframe tracker's state machine, restated from the reference (ba_tracker.py:14-78, 128-235, 295-356, 468-802) line
+    by line, with the numerical cores injected:
+
+      match(desc_kf [256, n_kf], desc_q [256, n_q]) -> matches0 [n_kf]
+      flow_pnp(kf_frame_info, frame_info_dict) -> (pose [4, 4], kpt_dist, kpt_new [n, 2], valid_ids)
+      update(matches0, kf_xy, q_xy, kf_pt_ids, points, K_kf, K_q, pose_kf, pose_q) -> Update (numpy, as ``update`` above)
+      ba(kpt2ds, kpt2d3d_ids, kpt2d_fids, kpt3d_list, cams, win_size) -> (points, cams)
+
+    and the host helpers taken from onepose_amd.tracker (pinned on their own in test_track_helpers.py).  No printing, timers
+    or movie writer.  The four fixed reference defects are marked FIXED; index arrays are integer."""
+
+    def __init__(self, match, flow_pnp, update, ba, win_size=10, frame_interval=5):
+        self.match, self.flow_pnp, self.update, self.ba = match, flow_pnp, update, ba
+        self._defaults(win_size, frame_interval)
+
+    def _defaults(self, win_size, frame_interval):
+        self.kf_frames, self.query_frames = {}, {}
+        self.id, self.last_kf_id = 0, -1
+        self.pose_list = []
+        self.kpt2ds, self.kpt2d_available_list, self.kpt2d_descs, self.kpt2d_fids, self.cams = [], [], [], [], []
+        self.kf_kpt_index_dict = {}
+        self.db_3d_list, self.db_3d_index = np.array([]), np.array([], dtype=int)
+        self.kpt3d_list, self.kpt3d_sourceid, self.kpt2d3d_ids = [], [], []
+        self.update_th, self.frame_id, self.last_kf_info = 10, 0, None
+        self.win_size, self.frame_interval = win_size, frame_interval
+        self.init_cnt, self.use_motion_cnt = 3, 0
+
+    def reset(self):
+        self._defaults(20, 3)
+
+    def update_kf(self, kf):
+        from onepose_amd.tracker import cm_degree_5_metric
+        if self.last_kf_info is not None:
+            trans, rot = cm_degree_5_metric(kf['pose_pred'], self.pose_list[-1])
+            if trans > 10 or rot > 10:
+                return False
+            self.last_kf_info = kf
+            return True
+        self.last_kf_info = kf
+        return True
+
+    def add_kf(self, kf):
+        from onepose_amd.tracker import get_cam_param
+        self.kf_frames[self.id] = kf
+        self.pose_list.append(kf['pose_pred'])
+        kpts, desc = np.asarray(kf['kpt_pred']['keypoints']), np.asarray(kf['kpt_pred']['descriptors'])
+        n_kpt = kpts.shape[0]
+        mk3 = np.asarray(kf['mkpts3d'], np.float64)
+        valid_2d_id = np.asarray(kf['valid_query_id'], dtype=int)
+        kf_db_ids = np.asarray(kf['kpt3d_ids'])
+        if len(self.kpt2ds) == 0:
+            self.cams = np.array([get_cam_param(kf['K'], kf['pose_pred'])])
+            self.kpt2ds = kpts
+            self.kpt2d_match = np.zeros([n_kpt], dtype=int)
+            self.kpt2d_descs = desc.transpose()
+            self.kpt2d_fids = np.ones([n_kpt], dtype=int) * self.id
+            self.kf_kpt_index_dict[self.id] = (0, n_kpt - 1)
+            self.kpt3d_list = mk3
+            self.kpt3d_source_id = np.ones([len(mk3)], dtype=int) * self.id
+            self.kpt2d3d_ids = np.ones([n_kpt], dtype=int) * -1
+            self.kpt2d3d_ids[valid_2d_id] = np.arange(0, len(mk3))
+            self.db_3d_list = kf_db_ids
+            self.db_3d_index = np.arange(0, len(mk3))
+        else:
+            self.cams = np.concatenate([self.cams, np.array([get_cam_param(kf['K'], kf['pose_pred'])])], axis=0)
+            self.kpt2ds = np.concatenate([self.kpt2ds, kpts], axis=0)
+            self.kpt2d_match = np.concatenate([self.kpt2d_match, np.zeros([n_kpt], dtype=int)], axis=0)
+            self.kpt2d_descs = np.concatenate([self.kpt2d_descs, desc.transpose()], axis=0)
+            self.kpt2d_fids = np.concatenate([self.kpt2d_fids, np.ones([n_kpt], dtype=int) * self.id])
+            start_id = self.kf_kpt_index_dict[self.last_kf_id][-1] + 1
+            self.kf_kpt_index_dict[self.id] = (start_id, start_id + n_kpt - 1)
+            inter = np.intersect1d(self.db_3d_list, kf_db_ids)
+            kf_exist = np.isin(kf_db_ids, inter)
+            new3d = mk3[np.where(kf_exist == False)[0]]  # noqa: E712
+            ids = np.ones([n_kpt], dtype=int) * -1
+            # FIXED (:213-214): every known database point takes the 3D id recorded for its own database id
+            where = {int(d): int(k) for d, k in zip(self.db_3d_list, self.db_3d_index)}
+            ids[valid_2d_id[np.where(kf_exist == True)[0]]] = [where[int(d)] for d in kf_db_ids[kf_exist]]  # noqa: E712
+            start3d = len(self.kpt3d_list)
+            ids[valid_2d_id[np.where(kf_exist == False)[0]]] = np.arange(start3d, start3d + len(new3d))  # noqa: E712
+            self.kpt2d3d_ids = np.concatenate([self.kpt2d3d_ids, ids], axis=0)
+            self.kpt3d_list = np.concatenate([self.kpt3d_list, new3d], axis=0)
+            # FIXED (:225-226): the source ids stay a vector
+            self.kpt3d_source_id = np.concatenate([self.kpt3d_source_id, np.ones(new3d.shape[0], dtype=int) * self.id])
+            # FIXED (:229): the database ids of the new points by their position in the match list
+            self.db_3d_list = np.concatenate([self.db_3d_list, kf_db_ids[np.where(kf_exist == False)[0]]])  # noqa: E712
+            self.db_3d_index = np.concatenate([self.db_3d_index, np.arange(start3d, start3d + len(new3d))])
+        self.last_kf_info = kf
+        self.last_kf_id = self.id
+        self.id += 1
+
+    def flow_track(self, frame, kf_info):
+        from onepose_amd.tracker import cm_degree_5_metric
+        pose_homo, kpt_dist, kpt_new, valid_ids = self.flow_pnp(kf_info, frame)
+        trans, rot = cm_degree_5_metric(pose_homo, frame['pose_gt'])
+        if trans <= 7 and rot <= 7 and kpt_dist < 10:
+            frame['mkpts3d'] = np.asarray(kf_info['mkpts3d'])[valid_ids]
+            frame['mkpts2d'] = kpt_new[valid_ids]
+            self.last_kf_info = frame
+        return pose_homo, kpt_dist
+
+    def _errors(self, ba_log, frame, pose_init, pose_opt):
+        from onepose_amd.tracker import cm_degree_5_metric
+        for key, pose in (('pred', frame['pose_pred']), ('init', pose_init), ('opt', pose_opt)):
+            t, r = cm_degree_5_metric(pose, frame['pose_gt'])
+            ba_log[key + '_err_trans'], ba_log[key + '_err_rot'] = np.round(t, decimals=2), np.round(r, decimals=2)
+
+    def track_ba(self, frame):
+        from onepose_amd.tracker import get_cam_param, get_cam_params_back
+        ba_log = {}
+        pose_init = frame['pose_init']
+        kf_info = self.kf_frames[self.last_kf_id]
+        q = frame['kpt_pred']
+        q.pop('scores', None)
+        q_kpts, q_desc = np.asarray(q['keypoints']), np.asarray(q['descriptors'])
+        start, end = self.kf_kpt_index_dict[self.last_kf_id]
+        kpt_idx = np.arange(start, end + 1)
+        kf_kpts, kf_desc = self.kpt2ds[kpt_idx], self.kpt2d_descs[kpt_idx].transpose()
+
+        match_kq = self.match(kf_desc, q_desc)
+        u = self.update(match_kq, kf_kpts, q_kpts, self.kpt2d3d_ids[kpt_idx], self.kpt3d_list, kf_info['K'], frame['K'],
+                        np.asarray(kf_info['pose_pred'], np.float64)[:3], np.asarray(pose_init, np.float64)[:3])
+        m, known, _, cand, kept, _, _, n_unmatched = (int(v) for v in u.summary)
+        ba_log['pt_found'] = known
+        if cand > 0:
+            ba_log['pt_triang'], ba_log['pt_triang_rm'] = cand, cand - kept
+        pair_q = np.asarray(u.pair_q[:m], dtype=int)
+        mkpts2d_query = q_kpts[pair_q]
+        kpt2ds_f = np.concatenate([self.kpt2ds, mkpts2d_query])
+        kpt2d3d_ids_f = np.concatenate([self.kpt2d3d_ids, np.asarray(u.q_pt_ids[:m], dtype=int)])
+        new_points = np.asarray(u.new_points)[:kept]
+        kpt3d_list_f = np.concatenate([self.kpt3d_list, new_points]) if kept > 0 else np.copy(self.kpt3d_list)
+        cams_f = np.concatenate([self.cams, [get_cam_param(frame['K'], pose_init)]])
+        kpt2d_fids_f = np.concatenate([self.kpt2d_fids, np.ones([m], dtype=int) * self.id])
+
+        kpt3d_list_f, cams_f = self.ba(kpt2ds_f, kpt2d3d_ids_f, kpt2d_fids_f, kpt3d_list_f, cams_f, self.win_size)
+        _, pose_opt = get_cam_params_back(cams_f[-1])
+        self._errors(ba_log, frame, pose_init, pose_opt)
+
+        if self.frame_id % self.frame_interval == 0 or self.init_cnt > 0:
+            unmatched_idx = np.asarray(u.unmatched_q[:n_unmatched], dtype=int)
+            self.kpt2ds = np.concatenate([kpt2ds_f, q_kpts[unmatched_idx]])
+            self.kpt2d_descs = np.concatenate([self.kpt2d_descs, q_desc[:, pair_q].transpose(), q_desc[:, unmatched_idx].transpose()])
+            self.kpt2d_fids = np.concatenate([kpt2d_fids_f, np.ones(n_unmatched, dtype=int) * kpt2d_fids_f[-1]])
+            self.cams = cams_f
+            self.kpt3d_source_id = np.concatenate([self.kpt3d_source_id, np.ones([len(kpt3d_list_f) - len(self.kpt3d_list)], dtype=int) * self.id])
+            self.kpt3d_list = kpt3d_list_f
+            self.kpt2d3d_ids = np.concatenate([kpt2d3d_ids_f, np.ones(n_unmatched, dtype=int) * -1])
+            frame['pose_pred'] = pose_init
+            self.kf_kpt_index_dict[self.id] = (len(self.kpt2d_fids) - 1 - len(q_kpts), len(self.kpt2d_fids) - 1)      # as written at :703
+            self.kf_frames.pop(self.last_kf_id)
+            self.kf_frames[self.id] = frame
+            self.last_kf_id = self.id
+            self.id += 1
+            if np.max(self.kpt2d_fids) > self.win_size:
+                valid_idx_fid = np.where(self.kpt2d_fids > np.max(self.kpt2d_fids) - self.win_size)[0]
+                num_del = len(self.kpt2d_fids) - len(valid_idx_fid)      # FIXED (:715): the count, not len() of np.where's tuple
+                s, e = self.kf_kpt_index_dict[self.last_kf_id]
+                self.kf_kpt_index_dict[self.last_kf_id] = (s - num_del, e - num_del)
+                self.kpt2d_fids = self.kpt2d_fids[valid_idx_fid]
+                self.kpt2ds = self.kpt2ds[valid_idx_fid]
+                self.kpt2d3d_ids = self.kpt2d3d_ids[valid_idx_fid]
+                self.kpt2d_descs = self.kpt2d_descs[valid_idx_fid]
+        self.frame_id += 1
+        return pose_opt, ba_log, True
+
+    def track(self, frame, flow_track_only=False, auto_mode=False):
+        from onepose_amd.tracker import cm_degree_5_metric, motion_prediction
+        if not auto_mode:
+            pose_ftk, kpt_dist = self.flow_track(frame, self.last_kf_info)
+            trans, rot = cm_degree_5_metric(self.pose_list[-1], pose_ftk)
+            pose_mo = frame['pose_pred'] if len(self.pose_list) < 3 else motion_prediction(self.pose_list)
+            if ((trans > 10 or rot > 10) and self.use_motion_cnt < 3) or kpt_dist > 10:
+                frame['pose_init'] = pose_mo
+                self.use_motion_cnt += 1
+            elif trans < 20 and rot < 20:
+                frame['pose_init'] = pose_ftk
+                self.use_motion_cnt = 0
+            else:
+                frame['pose_init'] = pose_mo
+                self.use_motion_cnt += 1
+            if self.init_cnt > 0:
+                self.init_cnt -= 1
+                frame['pose_init'] = frame['pose_gt']
+        elif self.init_cnt > 0:
+            self.init_cnt -= 1
+            frame['pose_init'] = frame['pose_gt']
+        else:
+            frame['pose_init'] = motion_prediction(self.pose_list)
+        if not flow_track_only:
+            pose_opt, ba_log, _ = self.track_ba(frame)
+            self.pose_list.append(pose_opt)
+        else:
+            pose_opt, ba_log = frame['pose_init'], {}
+            self._errors(ba_log, frame, frame['pose_init'], pose_opt)
+            self.pose_list.append(frame['pose_init'])
+        return frame['pose_init'], pose_opt, ba_log
+
+
+STATE_ARRAYS = ("kpt2ds", "kpt2d_descs", "kpt2d_fids", "kpt2d3d_ids", "kpt3d_list", "kpt3d_source_id", "cams", "db_3d_list", "db_3d_index", "kpt2d_match")
+STATE_SCALARS = ("id", "last_kf_id", "frame_id", "init_cnt", "use_motion_cnt", "win_size", "frame_interval", "update_th")
+
+
+def state_of(tracker):
+    """The comparable state of a tracker (this one or onepose_amd.BATracker): arrays, scalars, the index dict, the pose list."""
+    s = {k: np.asarray(getattr(tracker, k)) for k in STATE_ARRAYS if hasattr(tracker, k)}
+    s.update({k: getattr(tracker, k) for k in STATE_SCALARS})
+    s["kf_kpt_index_dict"] = {k: tuple(v) for k, v in tracker.kf_kpt_index_dict.items()}
+    s["kf_frames"] = sorted(tracker.kf_frames)
+    s["pose_list"] = np.stack([np.asarray(p, np.float64)[:3] for p in tracker.pose_list]) if tracker.pose_list else np.zeros((0, 3, 4))
+    return s
