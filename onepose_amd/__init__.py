@@ -1,5 +1,5 @@
 """MI355X-native GATsSPG 2D-3D matcher (OnePose hot path), the SuperPoint extractor in front of it, the SuperGlue 2D-2D
-matcher, the nearest-neighbour matcher, the 2D object detector that uses it, the object database builder, the windowed bundle adjustment, the tracker's flow step, its map update step and the keyframe tracker around them -- see DESIGN.md."""
+matcher, the nearest-neighbour matcher, the 2D object detector that uses it, the object database builder, the windowed bundle adjustment, the tracker's flow step, its map update step, the keyframe tracker around them and the matcher's training step (HIP loss head) -- see DESIGN.md."""
 # Importing the package has NO process-wide side effect (round-5 judge, weak #11: it used to export GPU_MAX_HW_QUEUES).  A serving
 # process that wants four frames in flight on hardware queues of their own calls configure_hip_queues() before its first HIP call
 # (or exports GPU_MAX_HW_QUEUES=8 itself); StreamRing asks for it too and warns when it comes too late (runtime.py).
@@ -14,5 +14,6 @@ from .mapping import ObjectMapper, covis_pairs  # noqa: F401
 from .bundle_adjust import BundleAdjuster  # noqa: F401
 from .flow import FlowTracker, ImagePyramid, kpt_flow_track  # noqa: F401
 from .tracker import BATracker, MapUpdater, apply_triangulation  # noqa: F401
+from .training import MatchingLoss, SparseTarget, matching_descriptors, training_loss  # noqa: F401
 
-__all__ = ["GATsSuperGlue", "GATsSPGEngine", "KeypointEncoder", "SuperPoint", "SuperPointEngine", "SuperGlue", "SuperGlueEngine", "NearestNeighbour", "NearestNeighbourEngine", "FrameMatcher", "LocalFeatureObjectDetector", "ObjectMapper", "covis_pairs", "StreamRing", "configure_hip_queues", "FlowTracker", "ImagePyramid", "kpt_flow_track", "BATracker", "MapUpdater", "apply_triangulation", "BundleAdjuster"]
+__all__ = ["GATsSuperGlue", "GATsSPGEngine", "KeypointEncoder", "SuperPoint", "SuperPointEngine", "SuperGlue", "SuperGlueEngine", "NearestNeighbour", "NearestNeighbourEngine", "FrameMatcher", "LocalFeatureObjectDetector", "ObjectMapper", "covis_pairs", "StreamRing", "configure_hip_queues", "FlowTracker", "ImagePyramid", "kpt_flow_track", "BATracker", "MapUpdater", "apply_triangulation", "MatchingLoss", "SparseTarget", "matching_descriptors", "training_loss", "BundleAdjuster"]

@@ -35,9 +35,10 @@ class Library:
 # The SuperGlue, detector and mapping sources live in csrc/superglue/, csrc/detector/, csrc/mapping/ and their include/ twins: source_hash() (top-level
 # files only) does not see them.
 LIBRARIES = (
-    Library("gatsspg", ["gatsspg_gemm_kernels.hip", "gatsspg_split_kernels.hip", "gatsspg_stream_kernels.hip", "gatsspg_capi.hip"],
+    Library("gatsspg", ["gatsspg_gemm_kernels.hip", "gatsspg_split_kernels.hip", "gatsspg_stream_kernels.hip", "gatsspg_capi.hip",
+                        "gatsspg_train_kernels.hip"],       # the training head (gtr_*, include/gatsspg_train.h) lives in the matcher's library
             ["gatsspg_common.h", "gatsspg_launch.h", "gatsspg_epilogue.h", "gemm_f32_mfma.h", "gemm_split_glds.h", "capi_common.h",
-             _include("gatsspg.h")],
+             "wg_primitives.h", _include("gatsspg.h"), _include("gatsspg_train.h")],
             tuning=True),
     Library("spp", ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"],
             ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", "wg_primitives.h", _include("superpoint.h")], tuning=True),
