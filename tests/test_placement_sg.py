@@ -1,0 +1,174 @@
+"""Placement tests of the SuperGlue matcher and the nearest-neighbour matcher (include/superglue/superglue.h, nn_matcher.h):
+sg_pack_weights + sg_forward, sg_forward_ragged, nnm_match, nnm_match_ragged and nnm_similarity with every device argument an exact
+piece of a guarded arena (tests/arena.py) under the fills 0xFF and 0x00; the packed blob is exactly sg_packed_weights_bytes, the
+workspaces exactly sg_workspace_bytes / sg_ragged_workspace_bytes / nnm_workspace_bytes.  Bitwise comparisons only; the oracle
+comparisons stay in tests/test_sg_hip_*.py, tests/test_sg_ragged_hip.py and tests/test_nn_hip.py."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import nn_cases as nc
+import nn_oracle as no
+from arena import run_placement
+from onepose_amd import _native_sg, synthetic
+
+BINDING = _native_sg
+_SIDES = dict(kpts0="in", scores0="in", desc0="in", kpts1="in", scores1="in", desc1="in")
+_MATCHES = dict(matches0="out", matches1="out", mscores0="out", mscores1="out")
+ROLES = {
+    "sg_pack_weights": dict(packed="scratch"),            # (raw is a HOST array of device pointers: the tensors it names are pieces)
+    "sg_forward": dict(packed="in", **_SIDES, **_MATCHES, z_out="out", workspace="scratch"),
+    "sg_forward_ragged": dict(packed="in", **_SIDES, **_MATCHES, z_out="out", workspace="scratch"),
+    "nnm_match": dict(desc0="in", desc1="in", **_MATCHES, workspace="scratch"),
+    "nnm_match_ragged": dict(desc0="in", desc1="in", **_MATCHES, workspace="scratch"),
+    "nnm_similarity": dict(desc0="in", desc1="in", sim_out="out", workspace="scratch"),
+}
+N_LAYERS, KINDS = 2, (_native_sg.LAYER_SELF, _native_sg.LAYER_CROSS)      # the two-layer module of tests/test_sg_hip_edges.py
+SINKHORN_ITERS, MATCH_THRESHOLD = 20, 0.2
+# the smallest and the one-past-a-tile shapes of tests/test_sg_hip_edges.py::ATTN_SHAPES (64-source K/V tiles, 128-query blocks)
+SG_SHAPES = [(1, 1, 1), (1, 65, 127), (2, 129, 65)]
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+I64, F32 = torch.int64, torch.float32
+
+
+@functools.lru_cache(maxsize=None)
+def raw_weights():
+    sd = synthetic.make_superglue_state_dict(60, N_LAYERS)
+    raw = [torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items() if not k.endswith("num_batches_tracked")]
+    assert len(raw) == _native_sg.num_raw(N_LAYERS) and all(t.dtype == F32 for t in raw)
+    return raw
+
+
+def packed_weights(mem):
+    """every raw tensor a piece of its own; the blob exactly sg_packed_weights_bytes, written by sg_pack_weights"""
+    raw = [mem.place(t, "in", f"raw[{i}]") for i, t in enumerate(raw_weights())]
+    ptrs = (ctypes.c_void_p * len(raw))(*[t.data_ptr() for t in raw])
+    nbytes = BINDING.load().sg_packed_weights_bytes(N_LAYERS)
+    assert nbytes > 0 and nbytes % 4 == 0
+    packed = mem.place(torch.empty(nbytes // 4), "scratch", "packed")
+    mem.call(BINDING, "sg_pack_weights", ptrs, N_LAYERS, packed)
+    return packed
+
+
+def sides(mem, data):
+    return [mem.place(torch.from_numpy(data[k + s]), "in", k + s) for s in "01" for k in ("keypoints", "scores", "descriptors")]
+
+
+def match_outputs(mem, b, n0, n1):
+    return {nm: mem.place(torch.empty(b, n, dtype=t), "out", nm) for nm, n, t in
+            (("matches0", n0, I64), ("matches1", n1, I64), ("mscores0", n0, F32), ("mscores1", n1, F32))}
+
+
+@pytest.mark.parametrize("b,n0,n1", SG_SHAPES)
+def test_pack_weights_and_forward(b, n0, n1):
+    data = synthetic.make_superglue_inputs(b, n0, n1, 480, 640, seed=n0 + n1, planted=min(n0, n1) // 2, h1=640, w1=480)
+    kinds = (ctypes.c_int32 * N_LAYERS)(*KINDS)
+    nbytes = BINDING.load().sg_workspace_bytes(b, n0, n1)
+    assert nbytes > 0
+
+    def body(mem):
+        packed = packed_weights(mem)
+        t = sides(mem, data)
+        out = match_outputs(mem, b, n0, n1)
+        out["z_out"] = mem.place(torch.empty(b, n0 + 1, n1 + 1), "out", "z_out")
+        ws = mem.place(nbytes, "scratch", "workspace")
+        mem.call(BINDING, "sg_forward", packed, N_LAYERS, kinds, SINKHORN_ITERS, MATCH_THRESHOLD, *t, b, n0, n1, 480, 640, 640, 480, *out.values(),
+                 ws, nbytes)
+        return out                                         # (the blob is opaque: what it holds shows in the outputs)
+
+    got = run_placement(body, DEV, ROLES)
+    assert not torch.isnan(got["z_out"]).any()
+    assert int(got["matches0"].min()) >= -1 and int(got["matches0"].max()) < n1
+
+
+def test_forward_ragged():
+    """Three pairs at the capacities 129 x 127.  The header refuses an item with an empty side ("1 <= n0[i]": the caller answers
+    it), so the empty item the module-level tests use is replaced by the nearest the entry point takes: one point on each side."""
+    items = [(65, 127), (1, 1), (129, 65)]
+    b, cap0, cap1 = len(items), 129, 127
+    data = synthetic.make_superglue_inputs(b, cap0, cap1, 480, 640, seed=9, planted=40)         # the padding: plausible points
+    n0, n1 = ((ctypes.c_int32 * b)(*[it[s] for it in items]) for s in (0, 1))
+    hw0, hw1 = (ctypes.c_int32 * (2 * b))(*[480, 640, 481, 641, 640, 480]), (ctypes.c_int32 * (2 * b))(*[480, 640] * b)
+    kinds = (ctypes.c_int32 * N_LAYERS)(*KINDS)
+    nbytes = BINDING.load().sg_ragged_workspace_bytes(b, cap0, cap1)
+    assert nbytes > 0
+
+    def body(mem):
+        packed = packed_weights(mem)
+        t = sides(mem, data)
+        out = match_outputs(mem, b, cap0, cap1)
+        out["z_out"] = mem.place(torch.empty(b, cap0 + 1, cap1 + 1), "out", "z_out")
+        ws = mem.place(nbytes, "scratch", "workspace")
+        mem.call(BINDING, "sg_forward_ragged", packed, N_LAYERS, kinds, SINKHORN_ITERS, MATCH_THRESHOLD, *t, b, cap0, cap1, n0, n1, hw0, hw1,
+                 *out.values(), ws, nbytes)
+        # the header: item i occupies rows 0..n0[i] and columns 0..n1[i] of its z_out slot, "the rest of a slot is unspecified"
+        z = torch.cat([out["z_out"][i, :a + 1, :c + 1].reshape(-1) for i, (a, c) in enumerate(items)])
+        return out, {"z_out": z}
+
+    got = run_placement(body, DEV, ROLES)
+    for i, (a, c) in enumerate(items):                      # "entries past an item's count are -1 / 0.f"
+        assert bool((got["matches0"][i, a:] == -1).all()) and bool((got["mscores1"][i, c:] == 0).all())
+        assert not torch.isnan(got["z_out"][i, :a + 1, :c + 1]).any()
+
+
+def conf_args(conf):
+    c = dict(no.DEFAULT_CONF, **conf)
+    return float(c["ratio_threshold"] or 0.0), float(c["distance_threshold"] or 0.0), int(bool(c["do_mutual_check"]))
+
+
+CORNERS = [(n0, n1) for n0 in (nc.EDGE_N0[0], nc.EDGE_N0[-1]) for n1 in (nc.EDGE_N1[0], nc.EDGE_N1[-1])]
+
+
+@pytest.mark.parametrize("n0,n1", CORNERS)
+def test_nnm_match_and_similarity(n0, n1):
+    """the corners of nn_cases.EDGE_N0 x EDGE_N1 under the last configuration the shape runs (both tests where both sides have two
+    points, the distance test elsewhere); nnm_similarity on the same pair"""
+    d0, d1 = nc.edge_pair(n0, n1)
+    tests = conf_args(no.CONFS[nc.edge_confs(n0, n1)[-1]])
+    nbytes = BINDING.load().nnm_workspace_bytes(1, n0, n1)
+    assert nbytes > 0
+
+    def body(mem):
+        a, c = mem.place(torch.from_numpy(d0)[None], "in", "desc0"), mem.place(torch.from_numpy(d1)[None], "in", "desc1")
+        out = match_outputs(mem, 1, n0, n1)
+        ws = mem.place(nbytes, "scratch", "workspace")
+        mem.call(BINDING, "nnm_match", a, c, 1, n0, n1, *tests, *out.values(), ws, nbytes, 0)
+        sim = mem.place(torch.empty(n0, n1), "out", "sim_out")
+        mem.call(BINDING, "nnm_similarity", a[0], c[0], n0, n1, sim, ws, nbytes, 0)
+        return dict(out, sim_out=sim)
+
+    got = run_placement(body, DEV, ROLES)
+    assert float(got["sim_out"].abs().max()) <= 1.0 + 1e-5 and int(got["matches1"].max()) < n0
+
+
+@pytest.mark.parametrize("shared1", [0, 1])
+def test_nnm_match_ragged(shared1):
+    """nn_cases.RAGGED_ITEMS at their capacities; with one shared plane every item takes the n1 of the largest, as nn_cases says"""
+    items = nc.RAGGED_ITEMS
+    b, cap0, cap1 = len(items), max(i[0] for i in items), max(i[1] for i in items)
+    rng = np.random.default_rng(5)
+    d0, d1 = (no.unit(rng.standard_normal((b, no.D, cap))).astype(np.float32) for cap in (cap0, cap1))     # the padding: plausible descriptors
+    for i, (a, c, seed) in enumerate(items):
+        d0[i, :, :a], d1[i, :, :c] = no.make_pair(a, c, seed)
+    if shared1:
+        d1 = np.ascontiguousarray(d1[1])
+    n0, n1 = (ctypes.c_int32 * b)(*[i[0] for i in items]), (ctypes.c_int32 * b)(*[cap1 if shared1 else i[1] for i in items])
+    tests = conf_args(nc.RAGGED_CONF)
+    nbytes = BINDING.load().nnm_workspace_bytes(b, cap0, cap1)
+    assert nbytes > 0
+
+    def body(mem):
+        a, c = mem.place(torch.from_numpy(d0), "in", "desc0"), mem.place(torch.from_numpy(d1), "in", "desc1")
+        out = match_outputs(mem, b, cap0, cap1)
+        ws = mem.place(nbytes, "scratch", "workspace")
+        mem.call(BINDING, "nnm_match_ragged", a, c, n0, n1, b, cap0, cap1, shared1, *tests, *out.values(), ws, nbytes, 0)
+        return out
+
+    got = run_placement(body, DEV, ROLES)
+    for i, (a, _, _) in enumerate(items):
+        assert bool((got["matches0"][i, a:] == -1).all()) and bool((got["mscores0"][i, a:] == 0).all())
+    assert int((got["matches0"] >= 0).sum()) > 0
