@@ -42,15 +42,16 @@ LIBRARIES = (
             tuning=True),
     Library("spp", ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"],
             ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", "wg_primitives.h", _include("superpoint.h")], tuning=True),
-    Library("pnp", ["pnp_kernels.hip"], ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("pnp.h"), _include("pnp_batch.h")]),
+    Library("pnp", ["pnp_kernels.hip"], ["capi_common.h", "geometry_math.h", "ransac_sample.h", "wg_primitives.h", _include("pnp.h"), _include("pnp_batch.h")]),
     Library("superglue", [os.path.join("superglue", "superglue.hip"), os.path.join("superglue", "nn_matcher.hip")],
             ["capi_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", _include("superglue", "superglue.h"), _include("superglue", "nn_matcher.h")]),
     Library("det", [os.path.join("detector", "detector.hip"), os.path.join("detector", "flow.hip")],
-            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h"), _include("detector", "flow.h")]),
+            ["capi_common.h", "geometry_math.h", "ransac_sample.h", "wg_primitives.h", _include("detector", "detector.h"),
+             _include("detector", "flow.h")]),
     Library("map", [os.path.join("mapping", "mapping.hip"), os.path.join("mapping", "bundle_adjust.hip"),
                     os.path.join("mapping", "track_update.hip")],
-            ["capi_common.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h"), _include("mapping", "bundle_adjust.h"),
-             _include("mapping", "track_update.h")]),
+            ["capi_common.h", "geometry_math.h", "ransac_sample.h", "wg_primitives.h", _include("mapping", "mapping.h"),
+             _include("mapping", "bundle_adjust.h"), _include("mapping", "track_update.h")]),
 )
 # views of the table under the names other modules use
 LIB_PATH, SPP_LIB_PATH, PNP_LIB_PATH, SG_LIB_PATH, DET_LIB_PATH, MAP_LIB_PATH = (lib.path for lib in LIBRARIES)

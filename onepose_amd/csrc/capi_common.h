@@ -1,10 +1,12 @@
-// Host-side plumbing shared by the C ABIs of the five libraries: the per-thread error text behind *_last_error(), the
-// launch check, and the aligned bump allocator of the workspace carve-ups.  Nothing here is exported: each library gets
-// its own copy, shared by its translation units.
+// Host-side plumbing shared by the C ABIs of the six libraries: the per-thread error text behind *_last_error(), the
+// launch check, the aligned bump allocator of the workspace carve-ups and the refusals of an aligned workspace.  Integer and
+// host code only: no floating-point contraction setting reaches it.  Nothing here is exported: each library gets its own
+// copy, shared by its translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stddef.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #pragma GCC visibility push(hidden)
@@ -30,6 +32,7 @@ inline int check_launch(int code, const char* what, const char* sep = ": ") {
 }
 
 __host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+__host__ __device__ inline int ceil_div(int x, int m) { return (x + m - 1) / m; }   // the workgroups of m threads that cover x items
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) & ~(a - 1); }   // a: a power of two
 
 // Carves a buffer into pieces in the order they are asked for, each starting on a multiple of `align` bytes.  A null base
@@ -42,6 +45,14 @@ struct Bump {
     template <class T = char>
     T* take(size_t nbytes) { const size_t o = reserve(nbytes); return base ? reinterpret_cast<T*>(base + o) : nullptr; }
 };
+
+// The refusals of a caller-provided workspace that must start on a 256-byte boundary and hold `need` bytes; 0 when it will do.
+inline int check_workspace(const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (!workspace) return fail(-1, "%s: null workspace", who);
+    if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(-1, "%s: workspace must be 256-byte aligned", who);
+    if (workspace_bytes < need) return fail(-2, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, need);
+    return 0;
+}
 
 }  // namespace capi
 #pragma GCC visibility pop

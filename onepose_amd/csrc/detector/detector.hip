@@ -17,12 +17,13 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#pragma clang fp contract(off)   // above every project include: geometry_math.h takes the setting of the file that includes it
+
 #include "../../../include/detector/detector.h"
 #include "../capi_common.h"
+#include "../geometry_math.h"
 #include "../ransac_sample.h"
 #include "../wg_primitives.h"
-
-#pragma clang fp contract(off)
 
 namespace det {
 
@@ -257,12 +258,8 @@ __global__ __launch_bounds__(256) void det_vote_kernel(const double* __restrict_
     }
 }
 
-struct K9 {
-    double k[9];
-};
-
 __global__ __launch_bounds__(256) void det_crop_kernel(const uint8_t* __restrict__ img, int H, int W, const int32_t* __restrict__ bbox,
-                                                       K9 K, int crop, int log2crop, float* __restrict__ out,
+                                                       geom::K9 K, int crop, int log2crop, float* __restrict__ out,
                                                        double* __restrict__ K_crop, int32_t* __restrict__ info) {
     const long long x0 = bbox[0], y0 = bbox[1];
     const long long w = (long long)bbox[2] - x0, h = (long long)bbox[3] - y0;
@@ -356,7 +353,7 @@ int ransac(const float* kpts0, const int32_t* n0, const int64_t* matches0, const
     const double thr2 = thr * thr;
     hipLaunchKernelGGL(det_gather_kernel, dim3(V), dim3(1024), 0, s, kpts0, n0, reinterpret_cast<const long long*>(matches0), kpts1, cap0,
                        n1, n_host, w.pts, w.src, w.count, w.best, mask);
-    hipLaunchKernelGGL(det_score_kernel, dim3((iterations + HYP_PER_BLOCK - 1) / HYP_PER_BLOCK, V), dim3(SCORE_THREADS), 0, s, w.pts,
+    hipLaunchKernelGGL(det_score_kernel, dim3(ceil_div(iterations, HYP_PER_BLOCK), V), dim3(SCORE_THREADS), 0, s, w.pts,
                        w.count, cap0, min_matches, thr2, iterations, (unsigned long long)seed, w.best);
     hipLaunchKernelGGL(det_finish_kernel, dim3(V), dim3(FIN_THREADS), 0, s, w.pts, w.src, w.count, w.best, cap0, min_matches, thr2,
                        (unsigned long long)seed, affine, mask, info);
@@ -411,9 +408,9 @@ int det_crop_resize(const uint8_t* image_u8, int H, int W, const int32_t* bbox, 
                     crop_size);
     int lg = 0;
     while ((1 << lg) < crop_size) ++lg;
-    K9 K;
+    geom::K9 K;
     memcpy(K.k, K_host, sizeof(K.k));
-    hipLaunchKernelGGL(det_crop_kernel, dim3((crop_size + 63) / 64, (crop_size + 3) / 4), dim3(256), 0,
+    hipLaunchKernelGGL(det_crop_kernel, dim3(ceil_div(crop_size, 64), ceil_div(crop_size, 4)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), image_u8, H, W, bbox, K, crop_size, lg, out, K_crop, info);
     return check_launch(-1, "det_crop_resize");
 }

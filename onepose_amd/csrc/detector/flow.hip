@@ -16,11 +16,12 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#pragma clang fp contract(off)   // above every project include: geometry_math.h takes the setting of the file that includes it
+
 #include "../../../include/detector/flow.h"
 #include "../capi_common.h"
+#include "../geometry_math.h"
 #include "../wg_primitives.h"
-
-#pragma clang fp contract(off)
 
 namespace flow {
 
@@ -110,12 +111,6 @@ __device__ __forceinline__ void stage_block(const uint8_t* __restrict__ img, int
     __syncthreads();
 }
 
-__device__ __forceinline__ long long wave_sum64(long long v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // ival / ix / iy of the samples this lane owns (sample s = 64 k + lane, row-major over the window), and where each sits in
 // the window.  In registers (windows of at most FLOW_REGISTER_SAMPLES samples; a sample beyond the window holds zeros) ..
 template <bool REGS>
@@ -194,7 +189,7 @@ __device__ __forceinline__ void load_patches(const uint8_t* __restrict__ img, in
         store.put(k, sx, sy, valid, ival, ix, iy);
         if (valid) { a11 += ix * ix; a12 += ix * iy; a22 += iy * iy; }
     });
-    A[0] = wave_sum64(a11); A[1] = wave_sum64(a12); A[2] = wave_sum64(a22);
+    A[0] = wg::wave_sum<long long>(a11); A[1] = wg::wave_sum<long long>(a12); A[2] = wg::wave_sum<long long>(a22);
 }
 
 // step 7's sums for the window `w` of the second image: B1, B2 (the same on every lane)
@@ -223,7 +218,7 @@ __device__ __forceinline__ void mismatch(const uint8_t* __restrict__ img, int W,
         b1 += diff * ix;   // ix = iy = 0 for a sample beyond the window
         b2 += diff * iy;
     });
-    B[0] = wave_sum64(b1); B[1] = wave_sum64(b2);
+    B[0] = wg::wave_sum<long long>(b1); B[1] = wg::wave_sum<long long>(b2);
 }
 
 template <bool REGS>
@@ -355,11 +350,7 @@ __global__ __launch_bounds__(64) void flow_mismatch_kernel(const uint8_t* __rest
     if (lane < 2) out_sums[(size_t)i * 2 + lane] = B[lane];
 }
 
-struct K9 {
-    double k[9];
-};
-
-__global__ __launch_bounds__(FLOW_REPROJ_THREADS) void flow_reproj_kernel(const double* __restrict__ pose, K9 K, const float* __restrict__ X,
+__global__ __launch_bounds__(FLOW_REPROJ_THREADS) void flow_reproj_kernel(const double* __restrict__ pose, geom::K9 K, const float* __restrict__ X,
                                                                           const float* __restrict__ x, const int32_t* __restrict__ status,
                                                                           int n, double* __restrict__ out) {
     __shared__ double red[2 * FLOW_REPROJ_THREADS];
@@ -370,13 +361,10 @@ __global__ __launch_bounds__(FLOW_REPROJ_THREADS) void flow_reproj_kernel(const 
     double v[2] = {0.0, 0.0};   // sum of distances, count
     for (int i = t; i < n; i += FLOW_REPROJ_THREADS) {
         if (status[i] != 1) continue;
-        const double X0 = (double)X[3 * i], X1 = (double)X[3 * i + 1], X2 = (double)X[3 * i + 2];
-        double c[3], h[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) c[r] = ((P[4 * r] * X0 + P[4 * r + 1] * X1) + P[4 * r + 2] * X2) + P[4 * r + 3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) h[r] = (K.k[3 * r] * c[0] + K.k[3 * r + 1] * c[1]) + K.k[3 * r + 2] * c[2];
-        const double ex = h[0] / h[2] - (double)x[2 * i], ey = h[1] / h[2] - (double)x[2 * i + 1];
+        const double Xi[3] = {(double)X[3 * i], (double)X[3 * i + 1], (double)X[3 * i + 2]};
+        double px, py;
+        geom::project(Xi, K.k, P, px, py);
+        const double ex = px - (double)x[2 * i], ey = py - (double)x[2 * i + 1];
         v[0] += sqrt(ex * ex + ey * ey);
         v[1] += 1.0;
     }
@@ -470,7 +458,7 @@ int flow_build_pyramid(const uint8_t* image_u8, int H, int W, int levels, uint8_
         if (e != hipSuccess) return fail(-3, "flow_build_pyramid: %s", hipGetErrorString(e));
     }
     for (int l = 1; l < levels; ++l)
-        hipLaunchKernelGGL(flow_pyr_down_kernel, dim3((lv.W[l] + 63) / 64, (lv.H[l] + 3) / 4), dim3(256), 0, s, pyramid + lv.off[l - 1],
+        hipLaunchKernelGGL(flow_pyr_down_kernel, dim3(ceil_div(lv.W[l], 64), ceil_div(lv.H[l], 4)), dim3(256), 0, s, pyramid + lv.off[l - 1],
                            lv.H[l - 1], lv.W[l - 1], pyramid + lv.off[l], lv.H[l], lv.W[l]);
     return check_launch(-3, "flow_build_pyramid");
 }
@@ -522,10 +510,7 @@ int flow_track(const uint8_t* pyramid_i, const uint8_t* pyramid_j, int H, int W,
     if (!(min_eig_threshold >= 0.0)) return fail(-1, "flow_track: min_eig_threshold must not be negative (got %g)", min_eig_threshold);
     if (n == 0) return 0;
     if (!pyramid_i || !pyramid_j || !pts || !next_pts || !status || !matches0) return fail(-1, "flow_track: null argument");
-    if (!workspace) return fail(-1, "flow_track: null workspace");
-    if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(-1, "flow_track: the workspace must be 256-byte aligned");
-    const size_t need = align_up(patch_bytes(n, win_w, win_h) + 1);
-    if (workspace_bytes < need) return fail(-2, "flow_track: workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    if (const int rc = check_workspace("flow_track", workspace, workspace_bytes, align_up(patch_bytes(n, win_w, win_h) + 1))) return rc;
     const Levels lv = make_levels(H, W, levels);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     auto* m0 = reinterpret_cast<long long*>(matches0);
@@ -543,7 +528,7 @@ int flow_reproj_mean(const double* pose, const double* K_host, const float* pts3
                      double* out, flow_stream_t stream) {
     if (n < 0 || n > FLOW_MAX_POINTS) return fail(-1, "flow_reproj_mean: n in [0, %d] expected (got %d)", FLOW_MAX_POINTS, n);
     if (!pose || !K_host || !out || (n > 0 && (!pts3d || !pts2d || !status))) return fail(-1, "flow_reproj_mean: null argument");
-    K9 K;
+    geom::K9 K;
     memcpy(K.k, K_host, sizeof(K.k));
     hipLaunchKernelGGL(flow_reproj_kernel, dim3(1), dim3(FLOW_REPROJ_THREADS), 0, reinterpret_cast<hipStream_t>(stream), pose, K, pts3d, pts2d,
                        status, n, out);

@@ -8,11 +8,11 @@
 
 #include <algorithm>
 
+#pragma clang fp contract(off)   // above every project include: a shared header takes the setting of the file that includes it
+
 #include "../../../include/mapping/bundle_adjust.h"
 #include "../capi_common.h"
 #include "../wg_primitives.h"
-
-#pragma clang fp contract(off)
 
 namespace bak {
 
@@ -678,8 +678,8 @@ using namespace capi;
 
 namespace {
 
-int chunk_points(int P) { return std::max(MIN_CHUNK_POINTS, (P + MAX_CHUNKS - 1) / MAX_CHUNKS); }
-int chunk_count(int P) { return (P + chunk_points(P) - 1) / chunk_points(P); }
+int chunk_points(int P) { return std::max(MIN_CHUNK_POINTS, ceil_div(P, MAX_CHUNKS)); }
+int chunk_count(int P) { return ceil_div(P, chunk_points(P)); }
 
 struct Workspace {
     Ctrl* ctrl;
@@ -725,13 +725,6 @@ int check_sizes(const char* who, int C, int P, int M) {
     return 0;
 }
 
-int check_workspace(const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
-    if (!workspace) return fail(-1, "%s: null workspace", who);
-    if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(-1, "%s: workspace must be 256-byte aligned", who);
-    if (workspace_bytes < need) return fail(-2, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, need);
-    return 0;
-}
-
 int radix_passes(int K) {  // keys 0 .. K inclusive
     int passes = 1;
     while ((K >> (RADIX_BITS * passes)) != 0) ++passes;
@@ -758,21 +751,21 @@ bool sort_list(const int32_t* obs_cam, const int32_t* obs_pt, int C, int P, int 
 bool enqueue_sort(const Workspace& w, const int32_t* obs_cam, const int32_t* obs_pt, int C, int P, int M, hipStream_t s) {
     if (!sort_list<0>(obs_cam, obs_pt, C, P, M, w.cam_obs, w.tmp, s)) return false;
     if (!sort_list<1>(obs_cam, obs_pt, C, P, M, w.pt_obs, w.tmp, s)) return false;
-    hipLaunchKernelGGL(ba_offsets_kernel, dim3((M + 1 + LIN_THREADS - 1) / LIN_THREADS, 2), dim3(LIN_THREADS), 0, s, obs_cam, obs_pt, C, P, M,
+    hipLaunchKernelGGL(ba_offsets_kernel, dim3(ceil_div(M + 1, LIN_THREADS), 2), dim3(LIN_THREADS), 0, s, obs_cam, obs_pt, C, P, M,
                        w.cam_obs, w.pt_obs, w.cam_off, w.pt_off);
     return true;
 }
 
 void enqueue_linearize(const double* cams, const double* intr, const double* points, const int32_t* obs_cam, const int32_t* obs_pt,
                        const double* obs_xy, int C, int P, int M, double* r, double* Jc, double* Jp, const Ctrl* ctrl, hipStream_t s) {
-    hipLaunchKernelGGL(ba_lin_kernel, dim3((M + LIN_THREADS - 1) / LIN_THREADS), dim3(LIN_THREADS), 0, s, cams, intr, points, obs_cam, obs_pt,
+    hipLaunchKernelGGL(ba_lin_kernel, dim3(ceil_div(M, LIN_THREADS)), dim3(LIN_THREADS), 0, s, cams, intr, points, obs_cam, obs_pt,
                        obs_xy, C, P, M, r, Jc, Jp, ctrl);
 }
 
 void enqueue_blocks(const Workspace& w, const double* r, const double* Jc, const double* Jp, const int32_t* cam_fixed, const int32_t* pt_fixed,
                     int C, int P, double* U, double* V, double* g_c, double* g_p, double* cost_cam, const Ctrl* ctrl, hipStream_t s) {
     hipLaunchKernelGGL(ba_cam_blocks_kernel, dim3(C), dim3(CAM_THREADS), 0, s, r, Jc, w.cam_obs, w.cam_off, cam_fixed, U, g_c, cost_cam, ctrl);
-    hipLaunchKernelGGL(ba_pt_blocks_kernel, dim3((P + LIN_THREADS - 1) / LIN_THREADS), dim3(LIN_THREADS), 0, s, r, Jp, w.pt_obs, w.pt_off, pt_fixed,
+    hipLaunchKernelGGL(ba_pt_blocks_kernel, dim3(ceil_div(P, LIN_THREADS)), dim3(LIN_THREADS), 0, s, r, Jp, w.pt_obs, w.pt_off, pt_fixed,
                        P, V, g_p, ctrl);
 }
 
@@ -785,10 +778,10 @@ bool enqueue_step(const Workspace& w, const double* U, const double* V, const do
         return false;
     hipLaunchKernelGGL(ba_schur_partial_kernel, dim3(chunks), dim3(SCHUR_THREADS), 0, s, V, g_p, Jc, Jp, obs_cam, w.pt_obs, w.pt_off, cam_fixed,
                        pt_fixed, C, P, chunk_points(P), mu, w.partial, ctrl);
-    hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3((n * (n + 1) + LIN_THREADS - 1) / LIN_THREADS), dim3(LIN_THREADS), 0, s, U, g_c, w.partial, chunks,
+    hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3(ceil_div(n * (n + 1), LIN_THREADS)), dim3(LIN_THREADS), 0, s, U, g_c, w.partial, chunks,
                        w.cam_off, cam_fixed, C, mu, w.S, w.rhs, ctrl);
     hipLaunchKernelGGL(ba_cholesky_kernel, dim3(1), dim3(CHOL_THREADS), lds, s, w.S, w.rhs, n, dc, ctrl, w.fail);
-    hipLaunchKernelGGL(ba_backsub_kernel, dim3((P + LIN_THREADS - 1) / LIN_THREADS), dim3(LIN_THREADS), 0, s, V, g_p, Jc, Jp, obs_cam, w.pt_obs,
+    hipLaunchKernelGGL(ba_backsub_kernel, dim3(ceil_div(P, LIN_THREADS)), dim3(LIN_THREADS), 0, s, V, g_p, Jc, Jp, obs_cam, w.pt_obs,
                        w.pt_off, pt_fixed, P, mu, dc, dp, ctrl, w.fail);
     hipLaunchKernelGGL(ba_model_kernel, dim3(1), dim3(MODEL_THREADS), 0, s, r, Jc, Jp, obs_cam, obs_pt, w.pt_obs, w.pt_off, P, dc, dp, md, ctrl);
     return true;
@@ -852,7 +845,7 @@ int ba_solve(double* cams, const double* intr, double* points, const int32_t* ob
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(ba_init_kernel, dim3(1), dim3(1), 0, s, w.ctrl);
     if (!enqueue_sort(w, obs_cam, obs_pt, C, P, M, s)) return check_launch(-3, "ba_solve");
-    const int apply_blocks = (CAM * C + PT * P + LIN_THREADS - 1) / LIN_THREADS;
+    const int apply_blocks = ceil_div(CAM * C + PT * P, LIN_THREADS);
     for (int it = 0; it < num_iterations; ++it) {
         enqueue_linearize(cams, intr, points, obs_cam, obs_pt, obs_xy, C, P, M, w.r, w.Jc, w.Jp, w.ctrl, s);
         enqueue_blocks(w, w.r, w.Jc, w.Jp, cam_fixed, pt_fixed, C, P, w.U, w.V, w.g_c, w.g_p, w.cost_cam, w.ctrl, s);

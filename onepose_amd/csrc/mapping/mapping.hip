@@ -20,12 +20,12 @@
 #include <math.h>
 #include <string.h>
 
+#pragma clang fp contract(off)   // above every project include: a shared header takes the setting of the file that includes it
+
 #include "../../../include/mapping/mapping.h"
 #include "../capi_common.h"
 #include "../ransac_sample.h"
 #include "../wg_primitives.h"
-
-#pragma clang fp contract(off)
 
 namespace mapk {
 
@@ -648,7 +648,7 @@ int map_merge_points(const float* xyz32, int n, double dist_threshold, float* me
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int W = (n + 31) / 32;
     if (hipMemsetAsync(w.deg, 0, (size_t)n * sizeof(int), s) != hipSuccess) return check_launch(-1, "map_merge_points");
-    hipLaunchKernelGGL(map_adjacency_kernel, dim3((W + 255) / 256, n), dim3(256), 0, s, xyz32, n, W, dist_threshold, w.bits, w.deg);
+    hipLaunchKernelGGL(map_adjacency_kernel, dim3(ceil_div(W, 256), n), dim3(256), 0, s, xyz32, n, W, dist_threshold, w.bits, w.deg);
     hipLaunchKernelGGL(map_sweep_kernel, dim3(1), dim3(256), 0, s, xyz32, n, W, w.bits, w.deg, merged_xyz, member_offsets, members, count);
     return check_launch(-1, "map_merge_points");
 }

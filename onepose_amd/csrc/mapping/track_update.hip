@@ -8,11 +8,12 @@
 #include <math.h>
 #include <stdint.h>
 
+#pragma clang fp contract(off)   // above every project include: geometry_math.h takes the setting of the file that includes it
+
 #include "../../../include/mapping/track_update.h"
 #include "../capi_common.h"
+#include "../geometry_math.h"
 #include "../wg_primitives.h"
-
-#pragma clang fp contract(off)
 
 namespace trk {
 
@@ -34,20 +35,9 @@ struct Ctrl {
 
 // ---- per-pair geometry -----------------------------------------------------------------------------------------------------
 
-// tracking_utils.py:74-88 on one point; pose: [4][4] row-major, top three rows; K: the full 3x3
-__device__ __forceinline__ void project(const double (&X)[3], const double* __restrict__ K, const double* __restrict__ pose, double& x, double& y) {
-    double c[3], h[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) c[r] = ((pose[4 * r] * X[0] + pose[4 * r + 1] * X[1]) + pose[4 * r + 2] * X[2]) + pose[4 * r + 3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) h[r] = (K[3 * r] * c[0] + K[3 * r + 1] * c[1]) + K[3 * r + 2] * c[2];
-    x = h[0] / h[2];
-    y = h[1] / h[2];
-}
-
 __device__ __forceinline__ double reproj_dist(const double (&X)[3], const double* K, const double* pose, float u, float v) {
     double x, y;
-    project(X, K, pose, x, y);
+    geom::project(X, K, pose, x, y);   // tracking_utils.py:74-88
     const double dx = x - (double)u, dy = y - (double)v;
     return sqrt(dx * dx + dy * dy);
 }
@@ -60,53 +50,7 @@ __device__ __forceinline__ void projection_matrix(const double* __restrict__ K, 
         for (int c = 0; c < 4; ++c) P[4 * r + c] = (K[3 * r] * pose[c] + K[3 * r + 1] * pose[4 + c]) + K[3 * r + 2] * pose[8 + c];
 }
 
-// index of element (i, j) of a symmetric 4 x 4 matrix stored as its upper triangle, row by row
-__host__ __device__ constexpr int tri4(int i, int j) { return i <= j ? i * 4 - i * (i - 1) / 2 + (j - i) : j * 4 - j * (j - 1) / 2 + (i - j); }
-
-// Cyclic Jacobi on the packed symmetric 4 x 4 (the scheme of the pose solver's jacobi_eig, restated here because this file's
-// contraction setting is its own): on exit S[tri4(i, i)] = eigenvalues, columns of V = eigenvectors.  Every index is a
-// compile-time constant after unrolling, so the matrices live in registers.
-__device__ __forceinline__ void jacobi4(double (&S)[10], double (&V)[4][4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sw = 0; sw < 16; ++sw) {
-        double off = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            diag += S[tri4(p, p)] * S[tri4(p, p)];
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) off += S[tri4(p, q)] * S[tri4(p, q)];
-        }
-        if (!(off > 1e-30 * diag)) break;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = S[tri4(p, q)];
-                if (apq != 0.0) {
-                    const double theta = (S[tri4(q, q)] - S[tri4(p, p)]) / (2.0 * apq);
-                    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (k != p && k != q) {
-                            const double akp = S[tri4(k, p)], akq = S[tri4(k, q)];
-                            S[tri4(k, p)] = c * akp - s * akq;
-                            S[tri4(k, q)] = s * akp + c * akq;
-                        }
-                        const double vkp = V[k][p], vkq = V[k][q];
-                        V[k][p] = c * vkp - s * vkq;
-                        V[k][q] = s * vkp + c * vkq;
-                    }
-                    S[tri4(p, p)] -= t * apq;
-                    S[tri4(q, q)] += t * apq;
-                    S[tri4(p, q)] = 0.0;
-                }
-            }
-    }
-}
+using geom::tri;   // geometry_math.h: the packed upper triangle geom::jacobi_eig works on
 
 // ba_tracker.py:251-265 on one pair: view 1 sees (u1, v1), view 2 (u2, v2)
 __device__ __forceinline__ void dlt(const double (&P1)[12], const double (&P2)[12], float u1, float v1, float u2, float v2, double (&X)[3]) {
@@ -123,13 +67,13 @@ __device__ __forceinline__ void dlt(const double (&P1)[12], const double (&P2)[1
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = a; b < 4; ++b) S[tri4(a, b)] = ((A[0][a] * A[0][b] + A[1][a] * A[1][b]) + A[2][a] * A[2][b]) + A[3][a] * A[3][b];
-    jacobi4(S, V);
-    double best = S[tri4(0, 0)], v[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
+        for (int b = a; b < 4; ++b) S[tri<4>(a, b)] = ((A[0][a] * A[0][b] + A[1][a] * A[1][b]) + A[2][a] * A[2][b]) + A[3][a] * A[3][b];
+    geom::jacobi_eig<4>(S, V, 16);
+    double best = S[tri<4>(0, 0)], v[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
 #pragma unroll
     for (int i = 1; i < 4; ++i)
-        if (S[tri4(i, i)] < best) {   // ties: the lowest index stays
-            best = S[tri4(i, i)];
+        if (S[tri<4>(i, i)] < best) {   // ties: the lowest index stays
+            best = S[tri<4>(i, i)];
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] = V[k][i];
         }
@@ -149,7 +93,9 @@ __device__ __forceinline__ double key_value(unsigned long long k) { return __lon
 
 // Sums over the workgroup of four counters per thread, packed as 16-bit fields of v; every total stays below 65536, so no
 // field carries into the next.  wsum: WG / 64 entries of LDS.  Every thread calls it and gets the totals; it starts with a
-// barrier, so two calls may follow each other on the same wsum.
+// barrier, so two calls may follow each other on the same wsum.  The two halves step through the butterfly of wg::wave_sum
+// together, in this loop of their own: as two wg::wave_sum<unsigned> calls the same instructions get other registers in
+// trk_finish_kernel and trk_gate_kernel, and trk_update then measured 0.05 to 0.15 us (of 98) slower in each of three sessions.
 __device__ __forceinline__ unsigned long long wg_sum4(unsigned long long v, unsigned long long* wsum) {
     unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
 #pragma unroll
@@ -480,13 +426,6 @@ int check_sizes(const char* who, int n_kf, int n_q) {
     return 0;
 }
 
-int check_workspace(const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
-    if (!workspace) return fail(-1, "%s: null workspace", who);
-    if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(-1, "%s: workspace must be 256-byte aligned", who);
-    if (workspace_bytes < need) return fail(-2, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, need);
-    return 0;
-}
-
 bool positive_finite(double v) { return v > 0.0 && v < INFINITY; }
 
 }  // namespace
@@ -517,7 +456,7 @@ int trk_update(const int32_t* matches0, const float* kf_xy, const float* q_xy, c
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(trk_pairs_kernel, dim3(1), dim3(WG), 0, s, matches0, kf_pt_ids, n_kf, n_q, n_points, pair_kf, pair_q, q_pt_ids, pair_dist,
                        w.cls, w.matched, w.ctrl);
-    hipLaunchKernelGGL(trk_geometry_kernel, dim3((n_kf + PAIR_THREADS - 1) / PAIR_THREADS), dim3(PAIR_THREADS), 0, s, kf_xy, q_xy, kf_pt_ids, points,
+    hipLaunchKernelGGL(trk_geometry_kernel, dim3(ceil_div(n_kf, PAIR_THREADS)), dim3(PAIR_THREADS), 0, s, kf_xy, q_xy, kf_pt_ids, points,
                        K_kf, K_q, pose_kf, pose_q, max_reproj, max_z, pair_kf, pair_q, w.cls, w.ctrl, pair_dist, w.X, w.cand);
     hipLaunchKernelGGL(trk_finish_kernel, dim3(1), dim3(WG), 0, s, kf_pt_ids, n_kf, n_q, n_points, gate_factor, pair_kf, pair_dist, w.cls, w.cand,
                        w.X, w.matched, w.ctrl, q_pt_ids, new_points, unmatched_q, median, summary);
@@ -527,7 +466,7 @@ int trk_update(const int32_t* matches0, const float* kf_xy, const float* q_xy, c
 int trk_triangulate_pairs(const double* P1, const double* P2, const float* xy1, const float* xy2, int n, double* X, map_stream_t stream) {
     if (!P1 || !P2 || !xy1 || !xy2 || !X) return fail(-1, "trk_triangulate_pairs: null argument");
     if (n < 1) return fail(-1, "trk_triangulate_pairs: n >= 1 expected (got %d)", n);
-    hipLaunchKernelGGL(trk_triangulate_kernel, dim3((n + PAIR_THREADS - 1) / PAIR_THREADS), dim3(PAIR_THREADS), 0,
+    hipLaunchKernelGGL(trk_triangulate_kernel, dim3(ceil_div(n, PAIR_THREADS)), dim3(PAIR_THREADS), 0,
                        reinterpret_cast<hipStream_t>(stream), P1, P2, xy1, xy2, n, X);
     return check_launch(-3, "trk_triangulate_pairs");
 }

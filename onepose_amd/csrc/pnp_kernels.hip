@@ -18,6 +18,7 @@
 
 #include "../../include/pnp.h"
 #include "capi_common.h"
+#include "geometry_math.h"
 #include "ransac_sample.h"
 #include "wg_primitives.h"
 
@@ -33,58 +34,8 @@ constexpr int MODEL_POINTS = 5;
 // live in registers.  (A first version with run-time indices kept them in scratch memory and one 5-point EPnP took
 // 10 ms of serial scratch latency.)
 
-// index of element (i, j) of a symmetric N x N matrix stored as its upper triangle, row by row
-template <int N>
-__host__ __device__ constexpr int tri(int i, int j) {
-    return i <= j ? i * N - i * (i - 1) / 2 + (j - i) : j * N - j * (j - 1) / 2 + (i - j);
-}
-
-// cyclic Jacobi for a symmetric N x N matrix held as its packed upper triangle S (N (N + 1) / 2 doubles: together with
-// the N x N eigenvector matrix that is 444 registers for N = 12 instead of 576): on exit S[tri(i, i)] = eigenvalues,
-// columns of V = eigenvectors.  The (p, q) sweep is fully unrolled; the sweep loop is rolled and stops when the
-// off-diagonal mass is below 1e-30 of the diagonal mass.
-template <int N>
-__device__ __forceinline__ void jacobi_eig(double (&S)[N * (N + 1) / 2], double (&V)[N][N], int max_sweeps) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sw = 0; sw < max_sweeps; ++sw) {
-        double off = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < N; ++p) {
-            diag += S[tri<N>(p, p)] * S[tri<N>(p, p)];
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) off += S[tri<N>(p, q)] * S[tri<N>(p, q)];
-        }
-        if (!(off > 1e-30 * diag)) break;
-#pragma unroll
-        for (int p = 0; p < N - 1; ++p)
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = S[tri<N>(p, q)];
-                if (apq != 0.0) {
-                    const double theta = (S[tri<N>(q, q)] - S[tri<N>(p, p)]) / (2.0 * apq);
-                    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        if (k != p && k != q) {
-                            const double akp = S[tri<N>(k, p)], akq = S[tri<N>(k, q)];
-                            S[tri<N>(k, p)] = c * akp - s * akq;
-                            S[tri<N>(k, q)] = s * akp + c * akq;
-                        }
-                        const double vkp = V[k][p], vkq = V[k][q];
-                        V[k][p] = c * vkp - s * vkq;
-                        V[k][q] = s * vkp + c * vkq;
-                    }
-                    S[tri<N>(p, p)] -= t * apq;
-                    S[tri<N>(q, q)] += t * apq;
-                    S[tri<N>(p, q)] = 0.0;
-                }
-            }
-    }
-}
+using geom::jacobi_eig;   // geometry_math.h: packed-symmetric cyclic Jacobi, N = 3 and N = 12 here
+using geom::tri;
 
 // least squares min |A x - b| for a 6 x NC system by Householder QR
 template <int NC>
@@ -757,8 +708,8 @@ Batch one_frame(const double* K, int n, uint64_t seed) {
 // the device knows them; src: the query keypoint of each, for the mask)
 void launch_solve(const float* p3, const float* p2, const int* n_dev, const int* src, const Batch& f, int b, double scale,
                   double thr2, int iterations, const Workspace& w, double* pose, int32_t* mask, int32_t* info, hipStream_t s) {
-    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64, b), dim3(64), 0, s, p3, p2, n_dev, scale, f, iterations, w.hyp);
-    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4, b), dim3(256), 0, s, p3, p2, n_dev, scale, f, thr2, iterations, w.hyp,
+    hipLaunchKernelGGL(hyp_kernel, dim3(ceil_div(iterations, 64), b), dim3(64), 0, s, p3, p2, n_dev, scale, f, iterations, w.hyp);
+    hipLaunchKernelGGL(score_kernel, dim3(ceil_div(iterations, 4), b), dim3(256), 0, s, p3, p2, n_dev, scale, f, thr2, iterations, w.hyp,
                        w.counts);
     hipLaunchKernelGGL(best_kernel, dim3(1, b), dim3(1024), 0, s, p3, p2, n_dev, scale, f, thr2, iterations, w.hyp, w.counts, src, mask,
                        w.inl, info);
@@ -897,7 +848,7 @@ int pnp_hypotheses(const float* pts_3d, const float* pts_2d, const double* K_hos
     if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
     if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
     if (!(scale > 0.0)) return fail(-1, "scale must be positive");
-    hipLaunchKernelGGL(hyp_kernel, dim3((iterations + 63) / 64, 1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d,
+    hipLaunchKernelGGL(hyp_kernel, dim3(ceil_div(iterations, 64), 1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d,
                        (const int*)nullptr, scale, one_frame(K_host, n, seed), iterations, hyp);
     return check_launch(-1, "pnp_hypotheses");
 }
@@ -908,7 +859,7 @@ int pnp_score_hypotheses(const float* pts_3d, const float* pts_2d, const double*
     if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
     if (iterations < 1 || iterations > (1 << 24)) return fail(-1, "iterations out of range");
     if (!(scale > 0.0) || !(reproj_error > 0.0)) return fail(-1, "scale and reproj_error must be positive");
-    hipLaunchKernelGGL(score_kernel, dim3((iterations + 3) / 4, 1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d,
+    hipLaunchKernelGGL(score_kernel, dim3(ceil_div(iterations, 4), 1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d,
                        (const int*)nullptr, scale, one_frame(K_host, n, 0), reproj_error * reproj_error, iterations, hyp, counts);
     return check_launch(-1, "pnp_score_hypotheses");
 }

@@ -1,8 +1,11 @@
-// Workgroup primitives of the small latency-bound geometry kernels (pnp_kernels.hip, detector/detector.hip, mapping/mapping.hip,
-// spp_detect_kernels.hip).  Integer arithmetic and floating-point additions only: nothing here can be contracted into an FMA, so
+// Workgroup primitives of the small latency-bound kernels: the geometry files (pnp_kernels.hip, detector/detector.hip,
+// detector/flow.hip, mapping/mapping.hip, mapping/bundle_adjust.hip, mapping/track_update.hip), spp_detect_kernels.hip and
+// gatsspg_train_kernels.hip.  Integer arithmetic and floating-point additions only: nothing here can be contracted into an FMA, so
 // a primitive means the same in a file compiled with the default contraction and in one that sets fp contract(off).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace wg {
 
@@ -32,8 +35,10 @@ __device__ __forceinline__ int excl_scan(int v, int* wsum, int& total) {
     return before + inc - v;
 }
 
-// Sum of one int per lane over the 64 lanes of the wave (xor butterfly), the same on every lane.
-__device__ __forceinline__ int wave_sum(int v) {
+// Sum of one integer (int, long long, ..) per lane over the 64 lanes of the wave (xor butterfly), the same on every lane.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+    static_assert(std::is_integral<T>::value, "integers only: a floating-point sum depends on the order of the butterfly");
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
     return v;

@@ -7,6 +7,8 @@ Not OpenCV: cv2.calcOpticalFlowPyrLK keeps points and the 2x2 algebra in fp32 an
 """
 import numpy as np
 
+from oracle.ransac_common import lane_tree_sum
+
 KERNEL = np.array([1, 4, 6, 4, 1], np.int64)
 W_BITS = 14
 ONE = 1 << W_BITS                         # 16384: the bilinear weights sum to it
@@ -244,16 +246,6 @@ def track(pyr_i, pyr_j, pts, init=None, win=(15, 15), max_iter=10, eps=0.03, min
     return out, status, matches0, trace, margins
 
 
-def lane_tree_sum(v, lanes=REPROJ_LANES):
-    """wg::tree_sum over `lanes` per-thread values: red[t] += red[t + s] for s = lanes / 2 .. 1."""
-    red = np.array(v)
-    s = lanes // 2
-    while s > 0:
-        red[:s] = red[:s] + red[s:2 * s]
-        s //= 2
-    return red[0]
-
-
 def reproj_mean(pose, K, pts3d, pts2d, status, dtype=np.float64):
     """(mean ||project(X, K, pose) - x|| over status == 1, count) in the kernel's order: thread t adds points t, t + 256, ..
     in turn, then the fixed tree.  project = tracking_utils.project: (R X + t), then K, then the division."""
@@ -269,6 +261,6 @@ def reproj_mean(pose, K, pts3d, pts2d, status, dtype=np.float64):
         ex, ey = h[0] / h[2] - x[i, 0], h[1] / h[2] - x[i, 1]
         lanes[i % REPROJ_LANES] = lanes[i % REPROJ_LANES] + np.sqrt(ex * ex + ey * ey)
         count += 1
-    total = lane_tree_sum(lanes)
+    total = lane_tree_sum(lanes, REPROJ_LANES)   # one value a lane: wg::tree_sum alone
     with np.errstate(invalid="ignore", divide="ignore"):
         return total / dtype(count), count

@@ -105,6 +105,31 @@ def test_bind_lowers_the_markers_to_void_pointers():
             assert getattr(fn, "errcheck", None) is None
 
 
+def test_build_table_lists_the_headers_the_sources_include():
+    """Every library's ``headers`` are exactly the project headers its sources reach through ``#include "..."``, directly or
+    through another header: an entry that is missing would let a change to that header go without a rebuild."""
+    from onepose_amd import build_ext
+
+    def reach(path, seen):
+        with open(path) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), flags=re.M):
+                target = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+                assert os.path.isfile(target), f"{path} includes {inc}, which is not there"
+                if target not in seen:
+                    seen.add(target)
+                    reach(target, seen)
+        return seen
+
+    assert len(build_ext.LIBRARIES) == 6
+    for lib in build_ext.LIBRARIES:
+        reached = set()
+        for s in lib.sources:
+            reach(os.path.join(build_ext.CSRC, s), reached)
+        listed = {os.path.normpath(os.path.join(build_ext.CSRC, h)) for h in lib.headers}
+        assert len(listed) == len(lib.headers) and reached == listed, \
+            f"{os.path.basename(lib.path)}: not listed {sorted(reached - listed)}, listed but not included {sorted(listed - reached)}"
+
+
 def test_every_loaded_library_has_its_own_call(monkeypatch):
     """An engine keeps ``lib.call`` of the library it was built on: re-binding the module (``_lib = None``, as the A/B tools do
     after assigning LIB_PATH) gives the new library a call table of its own and leaves the old one alone."""

@@ -25,6 +25,7 @@ def canonical(a):
 
 
 def tri4(i, j):
+    """geom::tri<4> of csrc/geometry_math.h: where (i, j) sits in the packed upper triangle of a symmetric 4 x 4."""
     if i > j:
         i, j = j, i
     return i * 4 - i * (i - 1) // 2 + (j - i)
@@ -59,7 +60,8 @@ def projection_matrix(K, pose):
 
 def jacobi4(S):
     """Cyclic Jacobi on n packed symmetric 4 x 4 matrices (S: list of 10 arrays [n], upper triangle row by row), every element
-    taking exactly the rotations and the stopping decision the scalar loop of the kernel takes.  Returns (S, V[4][4])."""
+    taking exactly the rotations and the stopping decision the scalar loop of geom::jacobi_eig<4> (csrc/geometry_math.h, as
+    trk::dlt calls it: JACOBI_SWEEPS sweeps, no contraction) takes.  Returns (S, V[4][4])."""
     n = S[0].shape[0]
     S = [s.copy() for s in S]
     V = [[np.ones(n) if i == j else np.zeros(n) for j in range(4)] for i in range(4)]
