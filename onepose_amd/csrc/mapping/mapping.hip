@@ -11,6 +11,7 @@
 //                         track's result is the same in any batch and in any run
 //   map_threshold_kernel  LDS histogram of the track lengths and the reference's selection rule
 //   map_filter_kernel     track-length and fp32 box test, ordered compaction (wg::excl_scan)
+//   map_zero_kernel       the degree counts the next kernel adds to (a kernel, so that a captured call holds kernel nodes only)
 //   map_adjacency_kernel  n x n closeness bits, 32 per thread; map_sweep_kernel: the reference's greedy sweep, one
 //                         workgroup walking the bit rows in index order
 //   map_gather_kernel     one workgroup per point, one lane per descriptor channel
@@ -429,6 +430,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void map_filter_kernel(const double* 
     if (tid == 0) *count = run;
 }
 
+__global__ __launch_bounds__(256) void map_zero_kernel(int* __restrict__ deg, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) deg[i] = 0;
+}
+
 // word w of row i: bit k set when point 32 w + k is closer to point i than the threshold; deg[i]: bits of row i
 __global__ __launch_bounds__(256) void map_adjacency_kernel(const float* __restrict__ xyz, int n, int W, double thr,
                                                             unsigned* __restrict__ bits, int* __restrict__ deg) {
@@ -647,7 +653,8 @@ int map_merge_points(const float* xyz32, int n, double dist_threshold, float* me
     if (workspace_bytes < w.bytes) return fail(-2, "map_merge_points: workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int W = (n + 31) / 32;
-    if (hipMemsetAsync(w.deg, 0, (size_t)n * sizeof(int), s) != hipSuccess) return check_launch(-1, "map_merge_points");
+    // a kernel, not hipMemsetAsync: the memset node of a captured call wrote other values than 0 from the fifth replay of its graph on
+    hipLaunchKernelGGL(map_zero_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, w.deg, n);
     hipLaunchKernelGGL(map_adjacency_kernel, dim3(ceil_div(W, 256), n), dim3(256), 0, s, xyz32, n, W, dist_threshold, w.bits, w.deg);
     hipLaunchKernelGGL(map_sweep_kernel, dim3(1), dim3(256), 0, s, xyz32, n, W, w.bits, w.deg, merged_xyz, member_offsets, members, count);
     return check_launch(-1, "map_merge_points");

@@ -817,6 +817,11 @@ __global__ __launch_bounds__(256) void export_plane_kernel(const float* __restri
 // =====================================================================================================
 // weight packing
 // =====================================================================================================
+// the blob's fp32 part before anything is packed into it: the padding rows and columns stay 0
+__global__ __launch_bounds__(256) void zero_packed_kernel(float* __restrict__ dst, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = 0.f;
+}
+
 // src [cout][cin][k][k] -> dst rows [row0, row0 + cout) of [rows][taps*cin]; rows beyond are zeroed by the caller
 __global__ void pack_conv_kernel(const float* __restrict__ src, const float* __restrict__ bsrc, float* __restrict__ dst,
                                  float* __restrict__ bdst, int cout, int cin, int taps, int row0) {
@@ -847,7 +852,8 @@ __global__ __launch_bounds__(256) void split_conv_weights_kernel(const float* __
 
 void launch_pack_weights(const void* raw_host, float* packed, hipStream_t s) {
     const spp_raw_weights& r = *static_cast<const spp_raw_weights*>(raw_host);
-    (void)hipMemsetAsync(packed, 0, sizeof(float) * PW_TOTAL, s);
+    // a kernel, not hipMemsetAsync: the memset node of a captured call left other values than 0 behind when its graph was replayed
+    hipLaunchKernelGGL(zero_packed_kernel, dim3(1024), dim3(256), 0, s, packed, PW_TOTAL);
     // conv1a: [64][1][3][3] is already [64][9]
     (void)hipMemcpyAsync(packed + PW_C1A_W, r.weight[0], sizeof(float) * 64 * 9, hipMemcpyDeviceToDevice, s);
     (void)hipMemcpyAsync(packed + PW_C1A_B, r.bias[0], sizeof(float) * 64, hipMemcpyDeviceToDevice, s);

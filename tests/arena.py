@@ -14,8 +14,16 @@ what the call wrote is the same bits under both patterns.  No tolerance anywhere
 
 The role of a device pointer comes from the header: ``const T*`` is "in", ``T*`` is "out", or "scratch" for a workspace, a packed
 blob or a cache that the call fills.  ``prototypes()`` is the header parser of tests/test_abi_tables.py, restated, keeping ``const``;
-``check_roles`` holds a test module's ROLES table to it (tests/test_arena.py, no GPU)."""
+``check_roles`` holds a test module's ROLES table to it (tests/test_arena.py, no GPU).
+
+``run_captured(body, device, roles)`` runs the same bodies against the other clause every header carries -- "work enqueued on
+`stream`, no allocation, no synchronisation": in the arena run's place every single library call is captured in a graph of its own
+on a side stream and replayed twice, each time from the contents its pieces had before the call.  A launch or memset sent to
+stream 0, a host read of a device count and a lazy allocation give the right bits on the default stream; here the capture fails, or
+the replay lacks what ran outside it.  ``NOT_CAPTURED`` names the stream-taking functions that have no case, and why."""
+import functools
 import glob
+import inspect
 import os
 import re
 
@@ -184,14 +192,107 @@ def check_roles(module, roles):
                 assert (role == "in") == const, f"{name}: {'const ' if const else ''}{ctype}{'*' * stars} {pname} is declared '{role}'"
 
 
-# ---- the two kinds of memory a case body runs on ----
+# ---- which entry points take a stream, and which of them have no captured case ----
+def stream_functions():
+    """the names of the functions the headers declare with a stream parameter"""
+    return sorted(name for name, params in prototypes().items() if any(p[2] == "stream" for p in params))
+
+
+def _stage(of, *names):
+    return {n: f"stage entry for tests: enqueues a prefix or a slice of the launches of {of}, which is covered" for n in names}
+
+
+# Every function of stream_functions() is a key of some placement module's ROLES (and then runs captured as well as placed) or of this
+# table (tests/test_arena.py holds the two to the headers).
+NOT_CAPTURED = {
+    **_stage("gatsspg_forward", "gatsspg_load_state", "gatsspg_store_state", "gatsspg_gats_layer", "gatsspg_attn_layer",
+             "gatsspg_final_proj_norm", "gatsspg_score_dual_softmax_match"),
+    **_stage("gatsspg_forward_frames", "gatsspg_gats_layer_frames"),
+    **_stage("sg_forward", "sg_keypoint_encode", "sg_layer", "sg_attention", "sg_sinkhorn", "sg_match_tail"),
+    **_stage("sg_forward_ragged", "sg_attention_ragged", "sg_sinkhorn_ragged", "sg_match_tail_ragged"),
+    **_stage("pnp_ransac_epnp", "pnp_epnp", "pnp_hypotheses", "pnp_score_hypotheses", "pnp_select_best"),
+    **_stage("spp_dense", "spp_dense_stage"),
+    **_stage("flow_track", "flow_patch_sums", "flow_mismatch_sums"),
+    "gatsspg_forward_profiled": "records events by design",
+    "spp_forward_profiled": "records events by design",
+}
+
+
+# ---- the two kinds of memory a case body runs on, and the captured mode of the plain one ----
+class CaptureFailure(AssertionError):
+    pass
+
+
+class HostGraph:
+    """The CPU stand-in of a captured graph (tests/test_arena.py): while one is capturing, ``HostGraph.enqueue(launch)`` stores
+    ``launch`` -- a stand-in library function enqueues its writes this way, as a library call enqueues kernels on the stream --
+    and ``replay()`` runs what was stored, in order.  Outside a capture ``enqueue`` runs the launch at once."""
+    capturing = None
+
+    def __init__(self):
+        self.launches = []
+
+    @staticmethod
+    def enqueue(launch):
+        if HostGraph.capturing is None:
+            launch()
+        else:
+            HostGraph.capturing.launches.append(launch)
+
+    def capture(self, fn):
+        HostGraph.capturing = self
+        try:
+            fn()
+        finally:
+            HostGraph.capturing = None
+        return len(self.launches) == 0
+
+    def replay(self):
+        for launch in self.launches:
+            launch()
+
+
+class DeviceGraph:
+    """One ``torch.cuda.CUDAGraph`` captured under ``torch.cuda.graph``: torch's default capture error mode, on torch's own side
+    stream.  ``capture(fn)`` -> whether the graph came out empty (torch warns of a graph without nodes when the capture ends)."""
+
+    def __init__(self):
+        self.graph = torch.cuda.CUDAGraph()
+
+    def capture(self, fn):
+        import warnings
+        raised = []
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            try:
+                with torch.cuda.graph(self.graph):
+                    try:
+                        fn()
+                    except Exception as e:      # the capture is ended before anything is raised
+                        raised.append(e)
+            except Exception as e:
+                if raised:
+                    raise RuntimeError(f"{raised[0]}; and when the capture was ended: {e}") from e
+                raise
+        if raised:
+            raise raised[0]
+        return any("graph is empty" in str(w.message).lower() for w in caught)
+
+    def replay(self):
+        self.graph.replay()
+
+
 class Memory:
     """What a case body sees.  ``place`` as Arena.place; ``call(module, name, *args)`` is ``module.load().call(name, device, *args)``
     with, in an arena, a snapshot before and a check behind: writable are the pieces whose parameter is "out" or "scratch" in
-    ROLES[name] -- a blob that one call packs ("scratch") is protected in the next that takes it as ``const``."""
+    ROLES[name] -- a blob that one call packs ("scratch") is protected in the next that takes it as ``const``.
 
-    def __init__(self, device, fill, roles=None, arena=None):
-        self.device, self.fill, self.roles, self.arena = torch.device(device), fill, roles or {}, arena
+    ``captured`` (no arena): every single call is captured in a graph of its own and replayed twice, each time from the contents
+    its pieces had before the call (``_replayed``); the body goes on with what the second replay left."""
+
+    def __init__(self, device, fill, roles=None, arena=None, captured=False):
+        assert not (captured and arena is not None)
+        self.device, self.fill, self.roles, self.arena, self.captured = torch.device(device), fill, roles or {}, arena, captured
         self.placed = []                # plain buffers live as long as the arena's pieces do: until the body is done
 
     def place(self, what, role, name=None, skew=0, copy=None):
@@ -213,8 +314,16 @@ class Memory:
         slack = 64 if self.device.type == "cpu" else 0
         return torch.empty(nbytes + slack, dtype=torch.uint8, device=self.device).fill_(self.fill)[:nbytes]
 
-    def guarded(self, fn, writable):
-        """run ``fn()``; in an arena: between a snapshot and a check that lets it write the pieces of ``writable`` (tensors)"""
+    def _sync(self):
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+
+    def guarded(self, fn, writable, inputs=(), name=None, empty_ok=None):
+        """run ``fn()``; in an arena: between a snapshot and a check that lets it write the pieces of ``writable`` (tensors).
+        Captured: ``fn`` is one library call that may write ``writable`` and reads ``inputs`` (see ``_replayed``)."""
+        if self.captured:
+            return self._replayed(name or getattr(fn, "__name__", "the call"), fn, [(f"writable[{i}]", t) for i, t in enumerate(writable)],
+                                  [(f"inputs[{i}]", t) for i, t in enumerate(inputs)], None, empty_ok)
         if self.arena is None:
             return fn()
         self.arena.snapshot()
@@ -222,22 +331,64 @@ class Memory:
         self.arena.check(writable)
         return result
 
-    def call(self, module, name, *args):
+    def _replayed(self, name, fn, writable, inputs, last_error, empty_ok):
+        """The stream contract of one call: ``fn`` is captured, not run, and what it enqueued is all it does.  The pieces are cloned;
+        the capture; then twice: the writable pieces are put back (a launch that ran during the capture instead of being recorded
+        is wiped here, and an argument the call updates in place starts from its start value again) and the graph is replayed.
+        The two replays leave the same bits and no input has changed.  ``writable`` / ``inputs``: [(parameter name, tensor)]."""
+        self._sync()
+        before = [(pname, t, t.clone()) for pname, t in writable]
+        held = [(pname, t, t.clone()) for pname, t in inputs]
+        graph = HostGraph() if self.device.type == "cpu" else DeviceGraph()
+        try:
+            empty = graph.capture(fn)
+        except Exception as e:
+            text = last_error() if last_error is not None else None
+            raise CaptureFailure(f"{name} could not be captured: it allocated, synchronised or used a stream other than the one it was given"
+                                 f" ({type(e).__name__}: {e}; the library's last error: {text.decode() if text else 'none'})") from e
+        self._sync()
+        if empty and not empty_ok:
+            raise CaptureFailure(f"{name}: the captured graph is empty -- nothing was enqueued on the stream the call was given")
+        if empty_ok and not empty:
+            raise CaptureFailure(f"{name}: the call enqueued work, but its call site says that it enqueues nothing ({empty_ok})")
+        if empty:
+            return
+
+        def replay():
+            for _, t, start in before:
+                t.copy_(start)
+            graph.replay()
+            self._sync()
+
+        replay()
+        first = [t.clone() for _, t, _ in before]
+        replay()
+        for pname, t, start in held:
+            assert bitwise_equal(start, t), f"{name} {pname}: an input was modified ({_differing(start, t)})"
+        for (pname, t, _), a in zip(before, first):
+            assert bitwise_equal(a, t), f"{name} {pname}: two replays from the same contents differ in {_differing(a, t)}"
+
+    def call(self, module, name, *args, empty_ok=None):
+        """``empty_ok`` (captured runs): the header's sentence by which this call enqueues nothing for this input"""
         declared = self.roles[name]
         from onepose_amd._binding import STREAM
-        table = {**module.SYMBOLS, **getattr(module, "MORE_SYMBOLS", {})}[name][1]
+        symbols = {**module.SYMBOLS, **getattr(module, "MORE_SYMBOLS", {})}
+        table = symbols[name][1]
         pnames = [p[2] for p, entry in zip(parameters(name), table) if entry is not STREAM]
         assert len(pnames) == len(args), f"{name}: {len(pnames)} parameters besides the stream, {len(args)} given"
-        writable = []
+        writable, inputs = [], []
         for pname, a in zip(pnames, args):
             if isinstance(a, torch.Tensor):
                 role = declared[pname]                      # KeyError: a device pointer the test module did not declare
                 if self.arena is not None:
                     self.arena.piece_of(a)                  # KeyError: a tensor that was not placed
-                if role != "in":
-                    writable.append(a)
+                (inputs if role == "in" else writable).append((pname, a))
         lib = module.load()
-        self.guarded(lambda: lib.call(name, self.device, *args), writable)
+        if self.captured:
+            last_error = getattr(lib, next(k for k in symbols if k.endswith("_last_error")))
+            self._replayed(name, lambda: lib.call(name, self.device, *args), writable, inputs, last_error, empty_ok)
+            return
+        self.guarded(lambda: lib.call(name, self.device, *args), [a for _, a in writable])
         if self.arena is None and self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
@@ -247,12 +398,37 @@ def run_placement(body, device, roles=None, guard=65536, capacity=64 << 20):
     for those the header says are partly "not written" the part it says is written.  Per pattern: plain run, arena run (every
     ``mem.call`` checked), outputs bitwise equal.  Across the patterns: what was written is bitwise equal.  Returns the arena outputs
     of the first pattern."""
+    return _run_twice(body, device, "arena", lambda fill: Memory(device, fill, roles, Arena(device, guard=guard, fill=fill, capacity=capacity)))
+
+
+def run_captured(body, device, roles=None, guard=None, capacity=None):
+    """``run_placement`` with the captured run in the arena run's place (``guard`` and ``capacity`` are taken and not used: there is
+    no arena).  Per pattern: plain run -- the eager reference, which also makes the runtime load every kernel of the case before
+    anything is captured --, then the body on plain buffers with every single ``mem.call`` captured in a graph and replayed
+    (``Memory._replayed``); outputs bitwise equal.  Across the patterns: what was written is bitwise equal.  Returns the captured
+    run's outputs of the first pattern."""
+    return _run_twice(body, device, "captured", lambda fill: Memory(device, fill, roles, captured=True))
+
+
+def captured_twin(test):
+    """A placement test takes its runner as ``run=run_placement``; this is the same test -- parameters, marks, ids and every
+    assertion behind the runner -- with ``run_captured``.  A module binds it as ``test_x_captured = captured_twin(test_x)``."""
+    @functools.wraps(test)
+    def twin(*args, **kwargs):
+        return test(*args, run=run_captured, **kwargs)
+    assert "run" in inspect.signature(test).parameters, test.__name__
+    twin.__name__ = twin.__qualname__ = test.__name__ + "_captured"
+    return twin
+
+
+def _run_twice(body, device, kind, second):
     written = {}
     first = None
     for fill in PATTERNS:
         runs = []
-        for arena in (None, Arena(device, guard=guard, fill=fill, capacity=capacity)):
-            got = body(Memory(device, fill, roles, arena))
+        other = second(fill)
+        for mem in (Memory(device, fill, other.roles), other):
+            got = body(mem)
             full, part = got if isinstance(got, tuple) else (got, {})
             assert full, "a case body returns its outputs"
             runs.append((full, {k: part.get(k, v).clone() for k, v in full.items()}))
@@ -260,7 +436,7 @@ def run_placement(body, device, roles=None, guard=65536, capacity=64 << 20):
         assert set(plain) == set(placed)
         for k in plain:
             assert bitwise_equal(plain[k], placed[k]), \
-                f"{k}: the arena run differs from the plain run under fill {fill:#04x} in {_differing(plain[k], placed[k])}"
+                f"{k}: the {kind} run differs from the plain run under fill {fill:#04x} in {_differing(plain[k], placed[k])}"
         written[fill] = part
         first = first or placed
     a, b = (written[f] for f in PATTERNS)

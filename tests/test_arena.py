@@ -2,14 +2,17 @@
 library call -- a correct one, one that writes one byte behind an output, one that writes one element before the workspace, one that
 modifies an input, one whose result reads a guard byte -- are driven through the arena; the first passes, each of the others is
 reported with the right piece and offset.  Then the ROLES table of every placement test module against the ``const`` of the header
-prototypes.  No GPU: nothing here launches anything."""
+prototypes.  Then the captured mode (``run_captured``): the stand-ins enqueue their writes on ``arena.HostGraph`` as a library call
+enqueues kernels, and one that writes while it is recorded, one that updates an argument in place, one that modifies an input, one that
+enqueues nothing and one that raises are each answered as the stream contract says.  Last, every function the headers declare with a
+stream parameter has a captured case or a reason in ``arena.NOT_CAPTURED``.  No GPU: nothing here launches anything."""
 import importlib
 
 import pytest
 import torch
 
 import arena
-from arena import Arena, GuardViolation, run_placement
+from arena import Arena, CaptureFailure, GuardViolation, HostGraph, run_captured, run_placement
 
 CPU = torch.device("cpu")
 SMALL = dict(guard=4096, capacity=2 << 20)           # the stand-ins move a few bytes: a small arena keeps this file quick
@@ -66,7 +69,7 @@ def body_of(fn):
         x = mem.place(torch.arange(N, dtype=torch.float32), "in", "x")
         out = mem.place(torch.empty(N), "out", "out")
         ws = mem.place(torch.empty(N), "scratch", "workspace")
-        mem.guarded(lambda: fn(x, out, ws), [out, ws])
+        mem.guarded(lambda: fn(x, out, ws), [out, ws], inputs=[x], name=fn.__name__)
         return {"out": out}
     return body
 
@@ -179,3 +182,136 @@ def test_check_roles_refuses_a_wrong_or_missing_role():
         arena.check_roles(_native_train, {"gtr_scores_exp": dict(good, E="in")})
     with pytest.raises(AssertionError, match="roles declared for"):
         arena.check_roles(_native_train, {"gtr_scores_exp": {k: v for k, v in good.items() if k != "r"}})
+
+
+# ---- the captured mode: stand-ins that enqueue their writes, as a library call enqueues kernels on its stream ----
+def enqueued(fn):
+    def call(*tensors):
+        HostGraph.enqueue(lambda: fn(*tensors))
+    call.__name__ = fn.__name__
+    return call
+
+
+def strays_from_the_stream(x, out, ws):
+    """the first five elements are written when the call is made, not when its stream runs: a launch on another stream"""
+    out[:5].copy_(2 * x[:5])
+    HostGraph.enqueue(lambda: (ws.copy_(x), out[5:].copy_(ws[5:] * 2)))
+
+
+def test_a_correct_call_passes_captured():
+    got = run_captured(body_of(enqueued(correct)), CPU, **SMALL)
+    assert arena.bitwise_equal(got["out"], run_placement(body_of(correct), CPU, **SMALL)["out"])
+    assert torch.equal(got["out"], 2 * torch.arange(N, dtype=torch.float32))
+    assert HostGraph.capturing is None
+
+
+def test_a_write_made_while_the_call_is_recorded_is_reported():
+    """the plain run is right (outside a capture every launch runs at once); the replay lacks the five elements: they hold the fill"""
+    assert torch.equal(run_placement(body_of(strays_from_the_stream), CPU, **SMALL)["out"], 2 * torch.arange(N, dtype=torch.float32))
+    with pytest.raises(AssertionError, match=r"out: the captured run differs from the plain run under fill 0xff in 20 byte\(s\), the first at "
+                                             r"byte 0, the last at byte 19"):
+        run_captured(body_of(strays_from_the_stream), CPU)
+
+
+def in_place_body(fn):
+    def body(mem):
+        x = mem.place(torch.arange(N, dtype=torch.float32), "out", "x", copy=True)
+        mem.guarded(lambda: fn(x), [x], name="add_one")
+        return {"x": x}
+    return body
+
+
+def test_an_argument_updated_in_place_is_replayed_from_its_start_value():
+    """x += 1 once per replay, each replay from x0: x0 + 1, not x0 + 2 (no restore) or x0 + 3 (the capture ran it as well)"""
+    got = run_captured(in_place_body(lambda x: HostGraph.enqueue(lambda: x.add_(1))), CPU)
+    assert torch.equal(got["x"], torch.arange(N, dtype=torch.float32) + 1)
+    with pytest.raises(CaptureFailure, match="add_one: the captured graph is empty"):        # done at once: nothing was enqueued
+        run_captured(in_place_body(lambda x: x.add_(1)), CPU)
+
+
+def test_a_modified_input_is_reported_captured():
+    with pytest.raises(AssertionError, match=r"modifies_input inputs\[0\]: an input was modified \(1 byte\(s\), the first at byte 22, the last at byte 22\)"):
+        run_captured(body_of(enqueued(modifies_input)), CPU)
+
+
+def test_replays_that_differ_are_reported():
+    """state kept outside the pieces: the second replay writes something else"""
+    runs = []
+
+    def counts_its_runs(x, out, ws):
+        HostGraph.enqueue(lambda: (runs.append(0), correct(x, out, ws), out[3].fill_(len(runs) % 2)))
+    with pytest.raises(AssertionError, match=r"counts_its_runs writable\[0\]: two replays from the same contents differ in \d byte\(s\), the first at byte 1[2-5]"):
+        run_captured(body_of(counts_its_runs), CPU)
+
+
+def test_an_empty_graph_and_a_failed_capture():
+    def nothing(x, out, ws):
+        pass
+
+    def refuses(x, out, ws):
+        """as a call that allocates: fine on a stream of its own, an error while the stream is captured"""
+        if HostGraph.capturing is not None:
+            raise RuntimeError("operation not permitted when stream is capturing")
+        out.fill_(1)
+
+    def empty_body(fn, empty_ok):
+        def body(mem):
+            out = mem.place(torch.zeros(N), "out", "out", copy=True)
+            mem.guarded(lambda: fn(None, out, None), [out], name=fn.__name__, empty_ok=empty_ok)
+            return {"out": out}
+        return body
+    with pytest.raises(CaptureFailure, match="nothing: the captured graph is empty"):
+        run_captured(empty_body(nothing, None), CPU)
+    assert not run_captured(empty_body(nothing, "n = 0 enqueues nothing"), CPU)["out"].any()
+    def fills(x, out, ws):
+        HostGraph.enqueue(lambda: out.fill_(1))
+    with pytest.raises(CaptureFailure, match=r"fills: the call enqueued work, but its call site says that it enqueues nothing \(n = 0"):
+        run_captured(empty_body(fills, "n = 0 enqueues nothing"), CPU)
+    with pytest.raises(CaptureFailure, match="refuses could not be captured.*RuntimeError: operation not permitted when stream is capturing"):
+        run_captured(empty_body(refuses, None), CPU)
+    assert HostGraph.capturing is None
+
+
+def test_rows_the_header_calls_unwritten_are_compared_per_pattern_only_captured():
+    def body(mem):
+        out = mem.place(torch.empty(8, dtype=torch.int32), "out", "out")
+        mem.guarded(lambda: HostGraph.enqueue(lambda: out[:5].fill_(3)), [out])
+        return {"out": out}, {"out": out[:5]}
+    got = run_captured(body, CPU)
+    assert got["out"].tolist() == [3] * 5 + [-1] * 3
+    with pytest.raises(AssertionError, match="depends on the fill pattern"):
+        run_captured(lambda mem: body(mem)[0], CPU)
+
+
+# ---- every stream-taking function of the headers: a captured case, or a reason ----
+def covered_and_excused(streams, covered, excused):
+    """the complaints of the completeness rule: [] when every name of ``streams`` is in exactly one of the two tables and ``excused``
+    names nothing else"""
+    bad = [f"{n} takes a stream and has neither a captured case nor a reason in NOT_CAPTURED" for n in streams if n not in covered and n not in excused]
+    bad += [f"{n} has a captured case and a reason in NOT_CAPTURED" for n in streams if n in covered and n in excused]
+    bad += [f"NOT_CAPTURED names {n}, which no header declares with a stream parameter" for n in excused if n not in streams]
+    return bad
+
+
+def roles_of_all_modules():
+    return {name for module in PLACEMENT_MODULES for name in importlib.import_module(module).ROLES}
+
+
+def test_every_entry_point_with_a_stream_is_captured_or_excused():
+    streams, covered = arena.stream_functions(), roles_of_all_modules()
+    assert len(streams) > 60 and "ba_solve" in streams and "pnp_workspace_bytes" not in streams
+    assert covered_and_excused(streams, covered, arena.NOT_CAPTURED) == []
+    allowed = ("stage entry for tests: enqueues a prefix or a slice of the launches of ", "records events by design")
+    for name, reason in arena.NOT_CAPTURED.items():
+        assert reason.startswith(allowed), (name, reason)
+        if reason.startswith(allowed[0]):
+            assert reason[len(allowed[0]):].split(",")[0] in covered, (name, reason)
+
+
+def test_the_completeness_rule_complains():
+    streams, covered = arena.stream_functions(), roles_of_all_modules()
+    less = {k: v for k, v in arena.NOT_CAPTURED.items() if k != "sg_layer"}
+    assert covered_and_excused(streams, covered, less) == ["sg_layer takes a stream and has neither a captured case nor a reason in NOT_CAPTURED"]
+    assert covered_and_excused(streams + ["new_entry"], covered, arena.NOT_CAPTURED)[0].startswith("new_entry takes a stream")
+    assert "has a captured case and a reason" in covered_and_excused(streams, covered, dict(arena.NOT_CAPTURED, ba_solve="x"))[0]
+    assert "which no header declares" in covered_and_excused(streams, covered, dict(arena.NOT_CAPTURED, gone="x"))[0]

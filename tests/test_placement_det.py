@@ -1,7 +1,8 @@
 """Placement tests of the detector tail and the flow step (include/detector/detector.h, flow.h): det_affine_partial_from_matches,
 det_bbox_vote, det_crop_resize, flow_build_pyramid, flow_track and flow_reproj_mean with every device argument an exact piece of a
 guarded arena (tests/arena.py) under the fills 0xFF and 0x00; the workspaces are exactly det_workspace_bytes / flow_workspace_bytes,
-the pyramids exactly flow_pyramid_bytes.  Bitwise comparisons only; the oracle comparisons stay in tests/test_det_hip.py and
+the pyramids exactly flow_pyramid_bytes; det_affine_partial_ransac, the points form, view by view.  Every case runs a second time with
+each call captured and replayed (arena.run_captured).  Bitwise comparisons only; the oracle comparisons stay in tests/test_det_hip.py and
 tests/test_flow_hip.py."""
 import ctypes
 import functools
@@ -14,11 +15,12 @@ import det_cases as dc
 import detector_oracle as do
 import flow_cases as fc
 import flow_oracle as fo
-from arena import run_placement
+from arena import captured_twin, run_placement
 from onepose_amd import _native_det
 
 BINDING = _native_det
 ROLES = {
+    "det_affine_partial_ransac": dict(src="in", dst="in", affine="out", inlier_mask="out", info="out", workspace="scratch"),
     "det_affine_partial_from_matches": dict(kpts0="in", n0="in", matches0="in", kpts1="in", affine="out", inlier_mask="out", info="out",
                                             workspace="scratch"),
     "det_bbox_vote": dict(affine="in", info="in", hw0="in", boxes="out", bbox="out", best_view="out"),
@@ -53,7 +55,7 @@ def sixteen_views():
     return views, dc.embed(views, V)
 
 
-def test_affine_from_matches_and_bbox_vote():
+def test_affine_from_matches_and_bbox_vote(run=run_placement):
     """det_affine_partial_from_matches on the 16 views, then det_bbox_vote on the affines and infos it wrote (``const`` there)."""
     views, emb = sixteen_views()
     V, cap0, n1 = len(views), emb["cap0"], len(emb["kpts1"])
@@ -71,13 +73,45 @@ def test_affine_from_matches_and_bbox_vote():
         mem.call(BINDING, "det_bbox_vote", fit["affine"], fit["info"], hw, V, 480, 640, _native_det.RANK_BY["matches"], *vote.values())
         return {**fit, **vote}
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["info"].tolist() == [[int(v["ok"]), len(v["src"]), v["best"], v["count"]] for v in views]
     assert got["best_view"].item() == dc.N_MATCHES.index(4096)
 
 
+@pytest.mark.parametrize("V", [1, 16])
+def test_affine_partial_ransac(V, run=run_placement):
+    """The points form, one call per view of the batches of V = 1 and V = 16 of tests/test_det_hip.py (16: every size of
+    det_cases.N_MATCHES), on the source and destination points det_affine_partial_from_matches selects on the device.  The views of
+    0 matches are left out: the body places no empty piece.  Workspace: det_workspace_bytes(1, n, iterations), as the header says."""
+    ns = [dc.N_MATCHES[(3 * V + 4 * i) % len(dc.N_MATCHES)] for i in range(V)]
+    if V == 16:
+        ns[:11] = dc.N_MATCHES
+    views = [v for v in (dc.planted_view(n, 100 * V + i) for i, n in enumerate(ns)) if len(v["src"])]
+    assert views
+    lib = BINDING.load()
+
+    def body(mem):
+        out = {}
+        for i, v in enumerate(views):
+            n = len(v["src"])
+            nbytes = lib.det_workspace_bytes(1, n, do.ITERATIONS)
+            assert nbytes > 0
+            src, dst = mem.place(tensor(v["src"], F32), "in", f"src[{i}]"), mem.place(tensor(v["dst"], F32), "in", f"dst[{i}]")
+            fit = outputs(mem, ((f"affine[{i}]", (2, 3), F64), (f"inlier_mask[{i}]", (n,), I32), (f"info[{i}]", (4,), I32)))
+            ws = mem.place(nbytes, "scratch", f"workspace[{i}]")
+            mem.call(BINDING, "det_affine_partial_ransac", src, dst, n, do.REPROJ_THRESHOLD, do.ITERATIONS, 0, *fit.values(), ws, nbytes)
+            out.update(fit)
+        return out
+
+    got = run(body, DEV, ROLES)
+    for i, v in enumerate(views):
+        n = len(v["src"])
+        ok, count, best, inliers = got[f"info[{i}]"].tolist()          # the header: {ok, n, index of the best hypothesis, its inlier count}
+        assert ok == 1 and count == n and 0 <= best < do.ITERATIONS and int(got[f"inlier_mask[{i}]"].sum()) == inliers >= 2
+
+
 @pytest.mark.parametrize("name", sorted(CROP_BOXES))
-def test_crop_resize(name):
+def test_crop_resize(name, run=run_placement):
     img = np.random.RandomState(11).randint(0, 256, size=(480, 640)).astype(np.uint8)
     K9 = (ctypes.c_double * 9)(1063.2, 0.0, 318.7, 0.0, 1071.9, 243.1, 0.0, 0.0, 1.0)
     box, crop = CROP_BOXES[name], 256
@@ -88,12 +122,12 @@ def test_crop_resize(name):
         mem.call(BINDING, "det_crop_resize", image, 480, 640, bbox, K9, crop, *out.values())
         return out
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["info"].tolist() == [1, box[2] - box[0], box[3] - box[1], 0] and (name != "outside" or not got["out"].any())
 
 
 @pytest.mark.parametrize("H,W,levels", [(29, 37, 4), (2, 2, 3)])
-def test_build_pyramid(H, W, levels):
+def test_build_pyramid(H, W, levels, run=run_placement):
     img = np.random.RandomState(H + W).randint(0, 256, (H, W)).astype(np.uint8)
     nbytes = BINDING.load().flow_pyramid_bytes(H, W, levels - 1)
     assert nbytes == sum(h * w for h, w in fo.level_sizes(H, W, levels))
@@ -103,7 +137,7 @@ def test_build_pyramid(H, W, levels):
         mem.call(BINDING, "flow_build_pyramid", image, H, W, levels, pyr)
         return dict(pyramid=pyr)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert torch.equal(got["pyramid"][:H * W].cpu(), tensor(img).reshape(-1))
 
 
@@ -130,26 +164,26 @@ def track_body(first, second, pts, win, levels, max_iter=10, eps=0.03):
 
 
 @pytest.mark.parametrize("n", [5, 257])
-def test_track_noisy_case(n):
+def test_track_noisy_case(n, run=run_placement):
     """flow_cases.noisy_case() cut to 5 points and extended to 257 as tests/test_flow_hip.py extends it (15 x 15: patches in registers)."""
     case = fc.noisy_case()
     pts = np.concatenate([case.pts, case.pts[:55] + np.float32(0.375)])[:n]
-    got = run_placement(track_body(case.first, case.second, pts, case.win, case.levels, case.max_iter, case.eps), DEV, ROLES)
+    got = run(track_body(case.first, case.second, pts, case.win, case.levels, case.max_iter, case.eps), DEV, ROLES)
     assert got["status"].any() and got["matches0"].tolist() == [i if s else -1 for i, s in enumerate(got["status"].tolist())]
 
 
-def test_track_31x31_window():
+def test_track_31x31_window(run=run_placement):
     """The 31 x 31 case of tests/test_flow_hip.py: above FLOW_REGISTER_SAMPLES the patches live in the workspace."""
     a, b = fc.image_pair(150, 170, (3, 2), sigma=0.06, seed=5, noise_sd=4.0)
     pts = np.concatenate([fc.interior_points(150, 170, 30, 5, 6), np.array([[0, 0], [169, 149], [-40, 3]], np.float32)])
     levels = fo.pyramid_levels(150, 170, (31, 31), 2)
     assert levels == 3 and 31 * 31 > _native_det.FLOW_REGISTER_SAMPLES
-    got = run_placement(track_body(a, b, pts, (31, 31), levels), DEV, ROLES)
+    got = run(track_body(a, b, pts, (31, 31), levels), DEV, ROLES)
     assert got["status"][:-1].any() and not got["status"][-1]
 
 
 @pytest.mark.parametrize("n", [5, 257])
-def test_reproj_mean(n):
+def test_reproj_mean(n, run=run_placement):
     """the inputs of tests/test_flow_hip.py at the point counts of the tracking cases above (257: one over FLOW_REPROJ_THREADS)"""
     rs = np.random.RandomState(n)
     X = rs.uniform(-0.1, 0.1, (n, 3)).astype(np.float32)
@@ -166,5 +200,15 @@ def test_reproj_mean(n):
         mem.call(BINDING, "flow_reproj_mean", ins[0], K9, *ins[1:], n, out)
         return dict(out=out)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["out"][1] == status.sum() and got["out"][0] > 0
+
+
+# every case again with each library call captured in a graph and replayed (arena.run_captured): the stream contract
+test_affine_from_matches_and_bbox_vote_captured = captured_twin(test_affine_from_matches_and_bbox_vote)
+test_crop_resize_captured = captured_twin(test_crop_resize)
+test_build_pyramid_captured = captured_twin(test_build_pyramid)
+test_track_noisy_case_captured = captured_twin(test_track_noisy_case)
+test_track_31x31_window_captured = captured_twin(test_track_31x31_window)
+test_reproj_mean_captured = captured_twin(test_reproj_mean)
+test_affine_partial_ransac_captured = captured_twin(test_affine_partial_ransac)

@@ -2,7 +2,8 @@
 gatsspg_forward_cached and gatsspg_forward_frames with every device argument an exact piece of a guarded arena (tests/arena.py) under
 the fills 0xFF and 0x00, in all five arithmetics (the workspace layout depends on the arithmetic): the blob is exactly
 gatsspg_packed_weights_bytes, the cache exactly gatsspg_db_cache_bytes, every workspace exactly the gatsspg_workspace_bytes the header
-names for that call.  Bitwise comparisons only; the oracle comparisons stay in tests/test_hip_parity.py, tests/test_gats_*.py."""
+names for that call; and gatsspg_keypoint_encoder, which no forward calls.  Every case runs a second time with each call captured and
+replayed (arena.run_captured).  Bitwise comparisons only; the oracle comparisons stay in tests/test_hip_parity.py, tests/test_gats_*.py."""
 import ctypes
 import functools
 
@@ -10,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from arena import run_placement
+from arena import captured_twin, run_placement
 from onepose_amd import _native, synthetic
 from onepose_amd.gats_superglue import GNN_LAYER_NAMES
 
@@ -22,6 +23,7 @@ ROLES = {
     "gatsspg_prepare_database": dict(packed="in", desc3d_db="in", desc2d_db="in", cache="scratch", ws="scratch"),
     "gatsspg_forward_cached": dict(packed="in", desc2d_query="in", desc2d_db="in", cache="in", **_OUT),
     "gatsspg_forward_frames": dict(packed="in", desc2d_query="in", desc2d_db="in", cache="in", **_OUT),
+    "gatsspg_keypoint_encoder": dict(kpts="in", scores="in", out="out", scratch="scratch"),     # (w is a HOST struct of device pointers)
 }
 SHAPES = [(2, 7, 65, 8), (1, 129, 129, 3)]            # (b, n1, n2, num_leaf)
 SCALE, THRESHOLD = 0.07, 0.2
@@ -94,7 +96,7 @@ def inputs(b, n1, n2, num_leaf):
 
 @pytest.mark.parametrize("precision", sorted(_native.PRECISIONS))
 @pytest.mark.parametrize("b,n1,n2,num_leaf", SHAPES)
-def test_pack_weights_and_forward(b, n1, n2, num_leaf, precision):
+def test_pack_weights_and_forward(b, n1, n2, num_leaf, precision, run=run_placement):
     data = inputs(b, n1, n2, num_leaf)
 
     def body(mem):
@@ -105,13 +107,13 @@ def test_pack_weights_and_forward(b, n1, n2, num_leaf, precision):
         mem.call(BINDING, "gatsspg_forward", packed, dq, d3, d2, b, n1, n2, num_leaf, flags(precision), SCALE, THRESHOLD, *out.values(), ws, ws.numel())
         return out                                         # (the blob is opaque: what it holds shows in the outputs)
 
-    got = run_placement(body, DEV, ROLES, capacity=CAPACITY)
+    got = run(body, DEV, ROLES, capacity=CAPACITY)
     assert not torch.isnan(got["conf"]).any() and float(got["conf"].max()) > 0
 
 
 @pytest.mark.parametrize("precision", sorted(_native.PRECISIONS))
 @pytest.mark.parametrize("b,n1,n2,num_leaf", SHAPES)
-def test_prepare_database_and_forward_cached(b, n1, n2, num_leaf, precision):
+def test_prepare_database_and_forward_cached(b, n1, n2, num_leaf, precision, run=run_placement):
     """The cache is written by gatsspg_prepare_database (its workspace: gatsspg_workspace_bytes(b, 2, n2, num_leaf), as the header says)
     and ``const`` in gatsspg_forward_cached, which gets a workspace of its own."""
     data = inputs(b, n1, n2, num_leaf)
@@ -130,12 +132,12 @@ def test_prepare_database_and_forward_cached(b, n1, n2, num_leaf, precision):
                  *out.values(), ws, ws.numel())
         return out
 
-    got = run_placement(body, DEV, ROLES, capacity=CAPACITY)
+    got = run(body, DEV, ROLES, capacity=CAPACITY)
     assert not torch.isnan(got["conf"]).any() and float(got["conf"].max()) > 0
 
 
 @pytest.mark.parametrize("precision", sorted(_native.PRECISIONS))
-def test_forward_frames(precision):
+def test_forward_frames(precision, run=run_placement):
     """Frames of 2, 64 and 65 keypoints in one ragged call against a database of 65 points with 8 leaves.  The header refuses a
     count below 2 (as gatsspg_forward does: the reference raises for a single point), so the frame of 1 keypoint is replaced by the
     nearest the entry point takes.  The conf rows past a frame's count are "NOT WRITTEN"; matches0 / mscores0 there are -1 / 0."""
@@ -159,8 +161,43 @@ def test_forward_frames(precision):
                  *out.values(), ws, ws.numel())
         return out, {"conf": torch.cat([out["conf"][i, :k].reshape(-1) for i, k in enumerate(counts)])}
 
-    got = run_placement(body, DEV, ROLES, capacity=CAPACITY)
+    got = run(body, DEV, ROLES, capacity=CAPACITY)
     for i, k in enumerate(counts):
         assert not torch.isnan(got["conf"][i, :k]).any()
         assert bool((got["matches0"][i, k:] == -1).all()) and bool((got["mscores0"][i, k:] == 0).all())
         assert bool((got["conf"][i, k:].reshape(-1).view(torch.int32) == -1).all())          # still the first fill: every byte 0xFF
+
+
+@pytest.mark.parametrize("name,inp_dim", [("kenc_2d", 3), ("kenc_3d", 4)])
+@pytest.mark.parametrize("b,n", [(2, 7), (1, 257)])
+def test_keypoint_encoder(b, n, name, inp_dim, run=run_placement):
+    """gatsspg_keypoint_encoder, which no forward calls: both encoders of the module at 7 keypoints and at one over a block of 256.
+    The weights are pieces of their own, reached through the host struct; the scratch is exactly gatsspg_kenc_scratch_bytes."""
+    sd = synthetic.make_state_dict(0)
+    weights = [torch.from_numpy(np.ascontiguousarray(sd[f"{name}.encoder.{j}.{kind}"])) for j in (0, 3, 6, 9) for kind in ("weight", "bias")]
+    rs = np.random.RandomState(n + inp_dim)
+    kpts, scores = rs.uniform(-1, 1, (b, n, inp_dim - 1)).astype(np.float32), rs.uniform(0, 1, (b, n)).astype(np.float32)
+    nbytes = BINDING.load().gatsspg_kenc_scratch_bytes(b, n)
+    assert nbytes > 0
+
+    def body(mem):
+        keep = [mem.place(t, "in", f"weights[{i}]") for i, t in enumerate(weights)]
+        kw = _native.KencWeights()
+        for j in range(4):
+            kw.w[j], kw.b[j] = keep[2 * j].data_ptr(), keep[2 * j + 1].data_ptr()
+        kw.inp_dim = inp_dim
+        k, s = mem.place(torch.from_numpy(kpts), "in", "kpts"), mem.place(torch.from_numpy(scores), "in", "scores")
+        out = mem.place(torch.empty(b, 256, n), "out", "out")
+        scratch = mem.place(nbytes, "scratch", "scratch")
+        mem.call(BINDING, "gatsspg_keypoint_encoder", ctypes.byref(kw), k, s, b, n, out, scratch, nbytes)
+        return dict(out=out)
+
+    got = run(body, DEV, ROLES, capacity=CAPACITY)
+    assert not torch.isnan(got["out"]).any() and got["out"].any()
+
+
+# every case again with each library call captured in a graph and replayed (arena.run_captured): the stream contract
+test_pack_weights_and_forward_captured = captured_twin(test_pack_weights_and_forward)
+test_prepare_database_and_forward_cached_captured = captured_twin(test_prepare_database_and_forward_cached)
+test_forward_frames_captured = captured_twin(test_forward_frames)
+test_keypoint_encoder_captured = captured_twin(test_keypoint_encoder)

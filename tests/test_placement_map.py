@@ -2,7 +2,9 @@
 map_verify_matches, map_triangulate_tracks, map_filter_points, map_merge_points, map_gather_descriptors and ba_solve with every
 device argument an exact piece of a guarded arena (tests/arena.py) under the fills 0xFF and 0x00; the workspaces are exactly
 map_workspace_bytes / ba_workspace_bytes.  Where the header calls rows "undefined" or says nothing is written past a count, the rows
-it says are written are compared across the two fills.  Bitwise comparisons only; the oracle comparisons stay in
+it says are written are compared across the two fills.  Also map_track_length_threshold and the stage entries ba_linearize ->
+ba_normal_blocks -> ba_step.  Every case runs a second time with each call captured and replayed (arena.run_captured).  Bitwise
+comparisons only; the oracle comparisons stay in
 tests/test_map_hip.py and tests/test_ba_hip.py."""
 import ctypes
 
@@ -13,7 +15,7 @@ import torch
 import ba_cases as bc
 import map_cases as mc
 import mapping_oracle as mo
-from arena import run_placement
+from arena import captured_twin, run_placement
 from onepose_amd import _native_map
 
 BINDING = _native_map
@@ -29,6 +31,12 @@ ROLES = {
     # cams and points are updated in place: ``double*`` in the header, placed with their start values
     "ba_solve": dict(cams="out", intr="in", points="out", obs_cam="in", obs_pt="in", obs_xy="in", cam_fixed="in", pt_fixed="in",
                      trace="out", summary="out", workspace="scratch"),
+    "ba_linearize": dict(cams="in", intr="in", points="in", obs_cam="in", obs_pt="in", obs_xy="in", r="out", Jc="out", Jp="out"),
+    "ba_normal_blocks": dict(r="in", Jc="in", Jp="in", obs_cam="in", obs_pt="in", cam_fixed="in", pt_fixed="in", U="out", V="out", g_c="out",
+                             g_p="out", cost_cam="out", workspace="scratch"),
+    "ba_step": dict(U="in", V="in", g_c="in", g_p="in", r="in", Jc="in", Jp="in", obs_cam="in", obs_pt="in", cam_fixed="in", pt_fixed="in",
+                    delta_c="out", delta_p="out", model_decrease="out", workspace="scratch"),
+    "map_track_length_threshold": dict(lengths="in", threshold="out"),
 }
 T = dict(max_epipolar_error=4.0, min_pair_inliers=15, max_reproj_error=4.0, min_tri_angle=1.5, max_hypotheses=120,
          refine_iterations=10, dist_threshold=1e-3, seed=0)       # onepose_amd.mapping.THRESHOLDS
@@ -46,7 +54,7 @@ def outputs(mem, spec):
 
 
 @pytest.mark.parametrize("P", [mc.VERIFY_PAIRS[0], mc.VERIFY_PAIRS[-1]])
-def test_verify_matches(P):
+def test_verify_matches(P, run=run_placement):
     b = mc.verify_batch(P)
     V, total = len(b["cams"]), int(b["match_offsets"][-1])
 
@@ -59,12 +67,12 @@ def test_verify_matches(P):
         rows = [out["out_matches"][base:base + n] for base, n in zip(b["match_offsets"][:-1].tolist(), out["counts"].tolist())]
         return out, {"out_matches": torch.cat(rows)}
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["counts"].tolist() == [c["count"] for c in b["pairs"]]
 
 
 @pytest.mark.parametrize("m", [63, 64, 65, 200])
-def test_triangulate_tracks(m):
+def test_triangulate_tracks(m, run=run_placement):
     """Every kind of track at the wave edge (63, 64, 65: one wave a track up to 64) and on the workgroup path (65, 200)."""
     cases = [mc.track_case(m, kind, 1) for kind in mc.TRACK_KINDS]
     b = mc.track_batch(cases)
@@ -77,12 +85,12 @@ def test_triangulate_tracks(m):
                  T["refine_iterations"], T["seed"], *out.values())
         return out
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["info"].tolist() == [list(c["result"]["info"]) for c in cases]
 
 
 @pytest.mark.parametrize("n", [mc.POINT_COUNTS[0], mc.POINT_COUNTS[-1]])
-def test_filter_and_merge_points(n):
+def test_filter_and_merge_points(n, run=run_placement):
     """map_filter_points at the oracle's threshold, then map_merge_points on the points the oracle keeps (its fp32 coordinates are
     the kernel's bit for bit, tests/test_map_hip.py)."""
     c = mc.points_case(n)
@@ -98,7 +106,7 @@ def test_filter_and_merge_points(n):
         k = int(out["count"])
         return out, {"kept_ids": out["kept_ids"][:k], "kept_xyz": out["kept_xyz"][:k]}          # the kept points; nothing is said of the rest
 
-    got = run_placement(filter_body, DEV, ROLES)
+    got = run(filter_body, DEV, ROLES)
     k = int(got["count"])
     assert got["kept_ids"][:k].tolist() == ref_ids.tolist()
     if k == 0:
@@ -116,11 +124,26 @@ def test_filter_and_merge_points(n):
         offs = out["member_offsets"][:q + 1]
         return out, {"merged_xyz": out["merged_xyz"][:q], "member_offsets": offs, "members": out["members"][:int(offs[-1])]}
 
-    merged = run_placement(merge_body, DEV, ROLES)
+    merged = run(merge_body, DEV, ROLES)
     assert int(merged["count"]) == len(mo.merge_points(ref_xyz)[1])
 
 
-def test_gather_descriptors():
+@pytest.mark.parametrize("n", [mc.POINT_COUNTS[0], mc.POINT_COUNTS[-1]])
+def test_track_length_threshold(n, run=run_placement):
+    """the lengths of map_cases.points_case (0 = no point, 2 .. 12) against the oracle's threshold"""
+    c = mc.points_case(n)
+
+    def body(mem):
+        lengths = mem.place(tensor(c["lengths"], I32), "in", "lengths")
+        threshold = mem.place(torch.empty(1, dtype=I32), "out", "threshold")
+        mem.call(BINDING, "map_track_length_threshold", lengths, n, c["max_num_kp3d"], threshold)
+        return dict(threshold=threshold)
+
+    got = run(body, DEV, ROLES)
+    assert got["threshold"].item() == mo.track_length_threshold(c["lengths"], c["max_num_kp3d"])
+
+
+def test_gather_descriptors(run=run_placement):
     """map_cases.gather_case(): every image's descriptors and scores are pieces of their own, reached through the two pointer tables."""
     c = mc.gather_case()
     dim, V = c["features"][0]["descriptors"].shape[0], len(c["features"])
@@ -138,7 +161,7 @@ def test_gather_descriptors():
         mem.call(BINDING, "map_gather_descriptors", dtab, stab, n_kpts, V, *ins, N, dim, *out.values())
         return out
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["idxs"].tolist() == mc.GATHER_COUNTS + [3, 3]
 
 
@@ -147,7 +170,7 @@ def ba_problems():
 
 
 @pytest.mark.parametrize("name", sorted(ba_problems()))
-def test_ba_solve(name):
+def test_ba_solve(name, run=run_placement):
     """One observation over a pass of the per-camera kernels (camera 0 has BA_CAMERA_CHUNK + 1), nothing fixed, the reference's 5 / 5
     iterations; and the 32-camera limit with its gauge fixed, 3 / 3 iterations as tests/test_ba_hip.py runs it."""
     pb, iterations = ba_problems()[name]()
@@ -165,5 +188,44 @@ def test_ba_solve(name):
         mem.call(BINDING, "ba_solve", cams, intr, points, *obs, *fixed, pb.C, pb.P, pb.M, iterations, iterations, *out.values(), ws, nbytes)
         return dict(out, cams=cams, points=points)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["summary"][5] == _native_map.BA_STATUS_OK and got["summary"][1] <= got["summary"][0]
+
+
+def test_ba_stage_entries(run=run_placement):
+    """ba_linearize, then ba_normal_blocks on its r, Jc, Jp, then ba_step at mu = 1e4 (where ba_solve starts) on the blocks of that:
+    the outputs of one stage are the ``const`` inputs of the next, and protected there.  blocks_case(BA_CAMERA_CHUNK + 1): camera 0
+    has one observation over a pass of the per-camera kernels, camera 2 and point 0 have none; nothing fixed (NULL masks)."""
+    pb = bc.blocks_case(bc.CAMERA_CHUNK + 1)
+    C, P, M = pb.C, pb.P, pb.M
+    nbytes = BINDING.load().ba_workspace_bytes(C, P, M)
+    assert nbytes > 0
+
+    def body(mem):
+        cams, intr, points = (mem.place(tensor(a, F64), "in", nm) for a, nm in ((pb.cams, "cams"), (pb.intr, "intr"), (pb.points, "points")))
+        obs_cam, obs_pt = mem.place(tensor(pb.obs_cam, I32), "in", "obs_cam"), mem.place(tensor(pb.obs_pt, I32), "in", "obs_pt")
+        obs_xy = mem.place(tensor(pb.obs_xy, F64), "in", "obs_xy")
+        lin = outputs(mem, (("r", (M, 2), F64), ("Jc", (M, 2, 6), F64), ("Jp", (M, 2, 3), F64)))
+        blocks = outputs(mem, (("U", (C, 6, 6), F64), ("V", (P, 3, 3), F64), ("g_c", (C, 6), F64), ("g_p", (P, 3), F64), ("cost_cam", (C,), F64)))
+        step = outputs(mem, (("delta_c", (C, 6), F64), ("delta_p", (P, 3), F64), ("model_decrease", (1,), F64)))
+        ws = mem.place(nbytes, "scratch", "workspace")
+        mem.call(BINDING, "ba_linearize", cams, intr, points, obs_cam, obs_pt, obs_xy, C, P, M, *lin.values())
+        mem.call(BINDING, "ba_normal_blocks", *lin.values(), obs_cam, obs_pt, None, None, C, P, M, *blocks.values(), ws, nbytes)
+        U, V, g_c, g_p, _ = blocks.values()
+        mem.call(BINDING, "ba_step", U, V, g_c, g_p, *lin.values(), obs_cam, obs_pt, None, None, C, P, M, 1e4, *step.values(), ws, nbytes)
+        return {**lin, **blocks, **step}
+
+    got = run(body, DEV, ROLES)
+    assert not any(torch.isnan(v).any() for v in got.values()) and got["model_decrease"].item() > 0
+    # the header: zeros for an unobserved variable, exactly 0 in the step
+    assert not got["U"][2].any() and not got["V"][0].any() and not got["delta_c"][2].any() and not got["delta_p"][0].any()
+
+
+# every case again with each library call captured in a graph and replayed (arena.run_captured): the stream contract
+test_verify_matches_captured = captured_twin(test_verify_matches)
+test_triangulate_tracks_captured = captured_twin(test_triangulate_tracks)
+test_filter_and_merge_points_captured = captured_twin(test_filter_and_merge_points)
+test_gather_descriptors_captured = captured_twin(test_gather_descriptors)
+test_ba_solve_captured = captured_twin(test_ba_solve)
+test_track_length_threshold_captured = captured_twin(test_track_length_threshold)
+test_ba_stage_entries_captured = captured_twin(test_ba_stage_entries)

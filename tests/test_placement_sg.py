@@ -1,8 +1,8 @@
 """Placement tests of the SuperGlue matcher and the nearest-neighbour matcher (include/superglue/superglue.h, nn_matcher.h):
 sg_pack_weights + sg_forward, sg_forward_ragged, nnm_match, nnm_match_ragged and nnm_similarity with every device argument an exact
 piece of a guarded arena (tests/arena.py) under the fills 0xFF and 0x00; the packed blob is exactly sg_packed_weights_bytes, the
-workspaces exactly sg_workspace_bytes / sg_ragged_workspace_bytes / nnm_workspace_bytes.  Bitwise comparisons only; the oracle
-comparisons stay in tests/test_sg_hip_*.py, tests/test_sg_ragged_hip.py and tests/test_nn_hip.py."""
+workspaces exactly sg_workspace_bytes / sg_ragged_workspace_bytes / nnm_workspace_bytes.  Every case runs a second time with each
+call captured and replayed (arena.run_captured).  Bitwise comparisons only; the oracle comparisons stay in tests/test_sg_hip_*.py, tests/test_sg_ragged_hip.py and tests/test_nn_hip.py."""
 import ctypes
 import functools
 
@@ -12,7 +12,7 @@ import torch
 
 import nn_cases as nc
 import nn_oracle as no
-from arena import run_placement
+from arena import captured_twin, run_placement
 from onepose_amd import _native_sg, synthetic
 
 BINDING = _native_sg
@@ -64,7 +64,7 @@ def match_outputs(mem, b, n0, n1):
 
 
 @pytest.mark.parametrize("b,n0,n1", SG_SHAPES)
-def test_pack_weights_and_forward(b, n0, n1):
+def test_pack_weights_and_forward(b, n0, n1, run=run_placement):
     data = synthetic.make_superglue_inputs(b, n0, n1, 480, 640, seed=n0 + n1, planted=min(n0, n1) // 2, h1=640, w1=480)
     kinds = (ctypes.c_int32 * N_LAYERS)(*KINDS)
     nbytes = BINDING.load().sg_workspace_bytes(b, n0, n1)
@@ -80,12 +80,12 @@ def test_pack_weights_and_forward(b, n0, n1):
                  ws, nbytes)
         return out                                         # (the blob is opaque: what it holds shows in the outputs)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert not torch.isnan(got["z_out"]).any()
     assert int(got["matches0"].min()) >= -1 and int(got["matches0"].max()) < n1
 
 
-def test_forward_ragged():
+def test_forward_ragged(run=run_placement):
     """Three pairs at the capacities 129 x 127.  The header refuses an item with an empty side ("1 <= n0[i]": the caller answers
     it), so the empty item the module-level tests use is replaced by the nearest the entry point takes: one point on each side."""
     items = [(65, 127), (1, 1), (129, 65)]
@@ -109,7 +109,7 @@ def test_forward_ragged():
         z = torch.cat([out["z_out"][i, :a + 1, :c + 1].reshape(-1) for i, (a, c) in enumerate(items)])
         return out, {"z_out": z}
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     for i, (a, c) in enumerate(items):                      # "entries past an item's count are -1 / 0.f"
         assert bool((got["matches0"][i, a:] == -1).all()) and bool((got["mscores1"][i, c:] == 0).all())
         assert not torch.isnan(got["z_out"][i, :a + 1, :c + 1]).any()
@@ -124,7 +124,7 @@ CORNERS = [(n0, n1) for n0 in (nc.EDGE_N0[0], nc.EDGE_N0[-1]) for n1 in (nc.EDGE
 
 
 @pytest.mark.parametrize("n0,n1", CORNERS)
-def test_nnm_match_and_similarity(n0, n1):
+def test_nnm_match_and_similarity(n0, n1, run=run_placement):
     """the corners of nn_cases.EDGE_N0 x EDGE_N1 under the last configuration the shape runs (both tests where both sides have two
     points, the distance test elsewhere); nnm_similarity on the same pair"""
     d0, d1 = nc.edge_pair(n0, n1)
@@ -141,12 +141,12 @@ def test_nnm_match_and_similarity(n0, n1):
         mem.call(BINDING, "nnm_similarity", a[0], c[0], n0, n1, sim, ws, nbytes, 0)
         return dict(out, sim_out=sim)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert float(got["sim_out"].abs().max()) <= 1.0 + 1e-5 and int(got["matches1"].max()) < n0
 
 
 @pytest.mark.parametrize("shared1", [0, 1])
-def test_nnm_match_ragged(shared1):
+def test_nnm_match_ragged(shared1, run=run_placement):
     """nn_cases.RAGGED_ITEMS at their capacities; with one shared plane every item takes the n1 of the largest, as nn_cases says"""
     items = nc.RAGGED_ITEMS
     b, cap0, cap1 = len(items), max(i[0] for i in items), max(i[1] for i in items)
@@ -168,7 +168,14 @@ def test_nnm_match_ragged(shared1):
         mem.call(BINDING, "nnm_match_ragged", a, c, n0, n1, b, cap0, cap1, shared1, *tests, *out.values(), ws, nbytes, 0)
         return out
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     for i, (a, _, _) in enumerate(items):
         assert bool((got["matches0"][i, a:] == -1).all()) and bool((got["mscores0"][i, a:] == 0).all())
     assert int((got["matches0"] >= 0).sum()) > 0
+
+
+# every case again with each library call captured in a graph and replayed (arena.run_captured): the stream contract
+test_pack_weights_and_forward_captured = captured_twin(test_pack_weights_and_forward)
+test_forward_ragged_captured = captured_twin(test_forward_ragged)
+test_nnm_match_and_similarity_captured = captured_twin(test_nnm_match_and_similarity)
+test_nnm_match_ragged_captured = captured_twin(test_nnm_match_ragged)

@@ -2,7 +2,7 @@
 exactly, back to back with 64 KiB guards, from an arena (tests/arena.py), under the fill patterns 0xFF and 0x00.  The arena run writes
 nothing outside its outputs and its workspace of exactly gtr_workspace_bytes, equals the plain run bit for bit, and gives the same
 bits under both patterns.  Then the two things no test had passed before: a ``cls`` that is not 4-byte aligned, and class values
-other than 0, 1, 2.  All comparisons are bitwise; the oracle comparisons stay in tests/test_training_gpu.py."""
+other than 0, 1, 2.  Every test runs a second time with each call captured and replayed (arena.run_captured).  All comparisons are bitwise; the oracle comparisons stay in tests/test_training_gpu.py."""
 import ctypes
 
 import numpy as np
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import train_oracle
-from arena import bitwise_equal, run_placement
+from arena import bitwise_equal, captured_twin, run_placement
 from onepose_amd import _native_train
 
 BINDING = _native_train
@@ -72,13 +72,13 @@ DEV = torch.device("cuda")
 
 @pytest.mark.parametrize("grads", [True, False], ids=["with_dx_dy", "forward_only"])
 @pytest.mark.parametrize("name", CASES)
-def test_loss_head(name, grads):
-    got = run_placement(head_body(case(name), grads), DEV, ROLES)
+def test_loss_head(name, grads, run=run_placement):
+    got = run(head_body(case(name), grads), DEV, ROLES)
     assert not torch.isnan(got["loss"]).any() and int(got["counts"].sum()) == case(name)["cls"].numel()
 
 
 @pytest.mark.parametrize("name", CASES)
-def test_stage_entries(name):
+def test_stage_entries(name, run=run_placement):
     """gtr_scores_exp, then gtr_loss_terms on its E, r, c, then gtr_score_grad on the counts and H sums of that: the outputs of one
     stage are the ``const`` inputs of the next, and protected there."""
     c = case(name)
@@ -98,12 +98,12 @@ def test_stage_entries(name):
         mem.call(BINDING, "gtr_score_grad", E, r, cc, cls, counts, rowh, colh, b, n, m, *focal, dS, ws, ws.numel())
         return dict(E=E, r=r, c=cc, loss_sums=sums, counts=counts, loss=loss, rowsum_h=rowh, colsum_h=colh, dS=dS)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert not any(torch.isnan(v.double()).any() for v in got.values())
 
 
 @pytest.mark.parametrize("name", CASES)
-def test_build_target(name):
+def test_build_target(name, run=run_placement):
     """The case's pairs, with one pair of negative indices and one past the shape appended to the first sample (kcap two over the
     longest list); n_orig, m_orig as the case pads, else two short of the shape so that the pad band exists."""
     c = case(name)
@@ -122,23 +122,23 @@ def test_build_target(name):
         mem.call(BINDING, "gtr_build_target", pairs, *host, b, kcap, n, m, int(i.get("pad_val", 0) == 0), cls, neg)
         return dict(cls=cls, negative_pairs=neg)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["negative_pairs"].item() == 1 and set(got["cls"].unique().tolist()) <= {0, 1, 2}
 
 
 @pytest.mark.parametrize("name", [BAND, "2x130x132"])
-def test_a_cls_that_is_not_4_byte_aligned(name):
+def test_a_cls_that_is_not_4_byte_aligned(name, run=run_placement):
     """m % 4 == 0: the aligned placement reads four classes per load, one byte further it must take the byte path -- same bits."""
     c = case(name)
     assert shape(c)[2] % 4 == 0
-    aligned = run_placement(head_body(c), DEV, ROLES)
-    skewed = run_placement(head_body(c, cls_skew=1), DEV, ROLES)
+    aligned = run(head_body(c), DEV, ROLES)
+    skewed = run(head_body(c, cls_skew=1), DEV, ROLES)
     for k in aligned:
         assert bitwise_equal(aligned[k], skewed[k]), k
     assert aligned["counts"][2] > 0
 
 
-def test_foreign_class_values_count_as_ignored():
+def test_foreign_class_values_count_as_ignored(run=run_placement):
     """The header: "any other value counts as ignored".  The ignored band rewritten with -128, -1, 3 and 127 mixed."""
     c = case(BAND)
     cls = c["cls"].clone()
@@ -146,7 +146,15 @@ def test_foreign_class_values_count_as_ignored():
     assert band.sum() > 1000
     cls[band] = torch.tensor([-128, -1, 3, 127], dtype=torch.int8).repeat(int(band.sum()) // 4 + 1)[:int(band.sum())]
     assert not (cls == 2).any() and bool(((cls == 1) == (c["cls"] == 1)).all())
-    want = run_placement(head_body(c), DEV, ROLES)
-    got = run_placement(head_body(c, cls=cls), DEV, ROLES)
+    want = run(head_body(c), DEV, ROLES)
+    got = run(head_body(c, cls=cls), DEV, ROLES)
     for k in ("loss", "counts", "dx", "dy"):
         assert bitwise_equal(want[k], got[k]), k
+
+
+# every case again with each library call captured in a graph and replayed (arena.run_captured): the stream contract
+test_loss_head_captured = captured_twin(test_loss_head)
+test_stage_entries_captured = captured_twin(test_stage_entries)
+test_build_target_captured = captured_twin(test_build_target)
+test_a_cls_that_is_not_4_byte_aligned_captured = captured_twin(test_a_cls_that_is_not_4_byte_aligned)
+test_foreign_class_values_count_as_ignored_captured = captured_twin(test_foreign_class_values_count_as_ignored)

@@ -1,14 +1,15 @@
 """Placement tests of the tracker's map update step (include/mapping/track_update.h): trk_update, trk_gate_median and
 trk_triangulate_pairs at the shapes 5x7, 63x65, 257x300 and 1025x1000 of track_cases.shape_cases(), every device argument an exact
-piece of a guarded arena (tests/arena.py) under the fills 0xFF and 0x00; the workspace is exactly trk_workspace_bytes.  Bitwise
-comparisons only; the oracle comparisons stay in tests/test_track_hip.py."""
+piece of a guarded arena (tests/arena.py) under the fills 0xFF and 0x00; the workspace is exactly trk_workspace_bytes.  Every case
+runs a second time with each call captured and replayed (arena.run_captured).  Bitwise comparisons only; the oracle comparisons stay
+in tests/test_track_hip.py."""
 import numpy as np
 import pytest
 import torch
 
 import track_cases as tc
 import track_oracle as orc
-from arena import run_placement
+from arena import captured_twin, run_placement
 from onepose_amd import _native_trk
 
 BINDING = _native_trk
@@ -29,7 +30,7 @@ def tensor(a):
 
 
 @pytest.mark.parametrize("name", NAMES)
-def test_update(name):
+def test_update(name, run=run_placement):
     c = tc.shape_cases()[name]
     n_kf, n_q, n_points = len(c["matches0"]), len(c["q_xy"]), len(c["points"])
     nbytes = BINDING.load().trk_workspace_bytes(n_kf, n_q)
@@ -47,14 +48,14 @@ def test_update(name):
         # the header: new_points "rows past the kept count are not written"
         return outs, {"new_points": outs["new_points"][:kept]}
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     m, kept = int(got["summary"][0]), int(got["summary"][4])
     assert 0 < m <= n_kf and (n_kf < 60 or 0 < kept < m)
     assert bool((got["new_points"][kept:].view(torch.int64) == -1).all())          # still the first pattern: every byte 0xFF
 
 
 @pytest.mark.parametrize("name", NAMES)
-def test_gate_median(name):
+def test_gate_median(name, run=run_placement):
     """n = the case's keyframe count; the distances of tests/test_track_hip.py (one run of them with ties).  The workspace is that of
     trk_workspace_bytes(n, 1), as the header says."""
     n = len(tc.shape_cases()[name]["matches0"])
@@ -68,12 +69,12 @@ def test_gate_median(name):
         mem.call(BINDING, "trk_gate_median", dist, n, 1.2, median, keep, ws, ws.numel())
         return dict(median=median, keep=keep)
 
-    got = run_placement(body, DEV, ROLES)
+    got = run(body, DEV, ROLES)
     assert got["median"].item() == np.median(d) * 1.2 and got["keep"].tolist() == (d < np.median(d) * 1.2).astype(int).tolist()
 
 
 @pytest.mark.parametrize("name", NAMES)
-def test_triangulate_pairs(name):
+def test_triangulate_pairs(name, run=run_placement):
     """n = the case's keyframe count: one pair per keyframe keypoint, query keypoints taken in order (cycled)."""
     c = tc.shape_cases()[name]
     n = len(c["kf_xy"])
@@ -86,4 +87,10 @@ def test_triangulate_pairs(name):
         mem.call(BINDING, "trk_triangulate_pairs", *ins, n, X)
         return dict(X=X)
 
-    run_placement(body, DEV, ROLES)
+    run(body, DEV, ROLES)
+
+
+# every case again with each library call captured in a graph and replayed (arena.run_captured): the stream contract
+test_update_captured = captured_twin(test_update)
+test_gate_median_captured = captured_twin(test_gate_median)
+test_triangulate_pairs_captured = captured_twin(test_triangulate_pairs)
