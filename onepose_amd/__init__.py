@@ -15,5 +15,6 @@ from .bundle_adjust import BundleAdjuster  # noqa: F401
 from .flow import FlowTracker, ImagePyramid, kpt_flow_track  # noqa: F401
 from .tracker import BATracker, MapUpdater, apply_triangulation  # noqa: F401
 from .training import MatchingLoss, SparseTarget, matching_descriptors, training_loss  # noqa: F401
+from .trainset import TrainingSet  # noqa: F401
 
-__all__ = ["GATsSuperGlue", "GATsSPGEngine", "KeypointEncoder", "SuperPoint", "SuperPointEngine", "SuperGlue", "SuperGlueEngine", "NearestNeighbour", "NearestNeighbourEngine", "FrameMatcher", "LocalFeatureObjectDetector", "ObjectMapper", "covis_pairs", "StreamRing", "configure_hip_queues", "FlowTracker", "ImagePyramid", "kpt_flow_track", "BATracker", "MapUpdater", "apply_triangulation", "MatchingLoss", "SparseTarget", "matching_descriptors", "training_loss", "BundleAdjuster"]
+__all__ = ["GATsSuperGlue", "GATsSPGEngine", "KeypointEncoder", "SuperPoint", "SuperPointEngine", "SuperGlue", "SuperGlueEngine", "NearestNeighbour", "NearestNeighbourEngine", "FrameMatcher", "LocalFeatureObjectDetector", "ObjectMapper", "covis_pairs", "StreamRing", "configure_hip_queues", "FlowTracker", "ImagePyramid", "kpt_flow_track", "BATracker", "MapUpdater", "apply_triangulation", "MatchingLoss", "SparseTarget", "matching_descriptors", "training_loss", "TrainingSet", "BundleAdjuster"]

@@ -36,9 +36,10 @@ class Library:
 # files only) does not see them.
 LIBRARIES = (
     Library("gatsspg", ["gatsspg_gemm_kernels.hip", "gatsspg_split_kernels.hip", "gatsspg_stream_kernels.hip", "gatsspg_capi.hip",
-                        "gatsspg_train_kernels.hip"],       # the training head (gtr_*, include/gatsspg_train.h) lives in the matcher's library
+                        "gatsspg_train_kernels.hip",        # the training head (gtr_*, include/gatsspg_train.h) lives in the matcher's library
+                        "gatsspg_trainset_kernels.hip"],    # and the training-set builder (gts_*, include/gatsspg_trainset.h) next to it
             ["gatsspg_common.h", "gatsspg_launch.h", "gatsspg_epilogue.h", "gemm_f32_mfma.h", "gemm_split_glds.h", "capi_common.h",
-             "wg_primitives.h", _include("gatsspg.h"), _include("gatsspg_train.h")],
+             "wg_primitives.h", "ransac_sample.h", _include("gatsspg.h"), _include("gatsspg_train.h"), _include("gatsspg_trainset.h")],
             tuning=True),
     Library("spp", ["spp_conv_kernels.hip", "spp_detect_kernels.hip", "spp_capi.hip"],
             ["spp_common.h", "gemm_f32_mfma.h", "gatsspg_common.h", "capi_common.h", "wg_primitives.h", _include("superpoint.h")], tuning=True),

@@ -96,6 +96,15 @@ def build_leaves(collect_desc, idxs, num_leaf, rng):
     return table[:, src.reshape(-1)]
 
 
+def read_annotation_arrays(avg_anno_path, collect_anno_path, idxs_path):
+    """The three annotation files as they are stored -> (average, collect, idxs): the two npz files as dicts of arrays, idxs int64;
+    refuses files whose idxs do not add up to the collected descriptors."""
+    avg, clt, idxs = dict(np.load(avg_anno_path)), dict(np.load(collect_anno_path)), np.asarray(np.load(idxs_path), dtype=np.int64)
+    if int(idxs.sum()) != clt["descriptors3d"].shape[1]:
+        raise ValueError(f"idxs sums to {int(idxs.sum())} but anno_3d_collect holds {clt['descriptors3d'].shape[1]} descriptors")
+    return avg, clt, idxs
+
+
 def load_object_database(avg_anno_path, collect_anno_path, idxs_path, num_leaf=8, seed=None, device="cuda", reference_rng=True):
     """inference.py:113-130 -> dict(keypoints3d [1,N,3], descriptors3d_db [1,256,N], descriptors2d_db [1,256,N*num_leaf])
     on `device`, the three database-side entries of the matcher's input (GATs_SuperGlue.py:181-189).

@@ -12,8 +12,8 @@ averaging.  Only the track building sits on the host between the kernels (``buil
 over the verified matches, whose semantics are ordering, not arithmetic.
 
 The reference hands verification and triangulation to COLMAP, an external binary.  Parity with COLMAP is NOT claimed and has
-not been measured: see DESIGN.md section 15 for the list of known differences.  ``anno_2d.json`` (per-image training
-annotations, feature_process.py:233-294) is out of scope: nothing in this repository trains.
+not been measured: see DESIGN.md section 15 for the list of known differences.  The per-image training annotations
+(``anno_2d.json``, feature_process.py:233-294) come from ``ObjectMapper.training_set`` (onepose_amd/trainset.py).
 """
 from __future__ import annotations
 
@@ -309,6 +309,7 @@ class ObjectMapper:
         self.cfg = dict(THRESHOLDS, **thresholds)
         self.tail = MapTail(device)
         self.last = None
+        self._resident = None           # the device tensors of the latest build that TrainingSet.from_mapper takes
 
     @torch.no_grad()
     def build(self, frames, poses, Ks, box3d_corners, seq_ids=None, out_dir=None):
@@ -395,9 +396,16 @@ class ObjectMapper:
                          xyz=host(xyz), inlier_mask=mask_h, info=host(info), lengths=host(lengths), threshold=int(threshold.item()),
                          kept_ids=kept_h, kept_xyz=host(kept_xyz), merged_xyz=host(merged), member_offsets=moffs_h, members=members_h,
                          point_offsets=point_offsets, gather_image=g_img, gather_kpt=g_kpt, anno=anno)
+        self._resident = dict(point_offsets=point_offsets, obs_image=g_img, obs_kpt=g_kpt, collect=cd, mean_desc=md, points3d=merged)
         if out_dir is not None:
             self.last["paths"] = write_annotation_files(out_dir, anno)
         return database_from_annotation(anno, self.num_leaf, self.leaf_seed, dev)
+
+    def training_set(self, features, image_size=None):
+        """The ``TrainingSet`` of the latest build (onepose_amd/trainset.py): ``features`` as the build took them, with their ``size``
+        (H, W) or one ``image_size`` for all."""
+        from .trainset import TrainingSet
+        return TrainingSet.from_mapper(self, features, image_size)
 
 
 def scan_lists(data_dir, obj, sequences=None, down_ratio=DOWN_RATIO):

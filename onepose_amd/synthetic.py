@@ -455,6 +455,7 @@ def make_map_model(seed=0, n_images=40, n_points=600, dim=16, hw=(96, 128)):
     xyz[17], xyz[25] = xyz[14] + step, xyz[14] + 2 * step
     lengths = rs.randint(2, 13, size=n_points)
     lengths[[2, 5, 7, 11, 20, 14, 17, 25]] = 12
+    lengths = np.minimum(lengths, n_images)                 # a track sees an image once: fewer than 12 images shorten it
     obs_image = np.concatenate([np.sort(rs.permutation(n_images)[:m]) for m in lengths]).astype(np.int32)
     per_image = np.bincount(obs_image, minlength=n_images)
     n_kpts = per_image + rs.randint(3, 9, size=n_images)
