@@ -11,7 +11,14 @@
  * inliers wins, final EPnP over the inliers) -- in fp64 like the reference's float64 call.  Two
  * documented differences: sample indices come from a counter-based hash (cv::RNG cannot be
  * reproduced without OpenCV) and every one of the `iterations` hypotheses is evaluated (OpenCV stops
- * at its adaptive confidence bound: a subset of this search).  See oracle/pnp_oracle.py.
+ * at its adaptive confidence bound: a subset of this search).  A third, since pnp_version() 3: a
+ * FLAT point set gets no pose.  EPnP's four control points span a volume only if the points do; where
+ * the smallest eigenvalue of the points' covariance is not above PNP_FLATNESS_TAU times the largest
+ * (a plane, a line, a point, or a slab thinner than about 3e-6 of its extent) the solve is refused:
+ * twelve NaNs in a hypothesis row, no model from such a sample, ok = 0 from a refit of such inliers.
+ * OpenCV inverts the control-point matrix by SVD and continues; the two have never been compared on
+ * such input (cv2 is not available here), and without the guard the result was NaN or a finite wrong
+ * pose as rounding had it.  See oracle/pnp_oracle.py, which has the same guard.
  *
  * Conventions as in gatsspg.h: device pointers, caller-provided workspace, work enqueued on
  * `stream`, no allocation, no synchronisation, 0 = OK / non-zero = error + pnp_last_error().
@@ -28,6 +35,12 @@ extern "C" {
 
 typedef struct ihipStream_t* pnp_stream_t; /* hipStream_t */
 
+/* smallest / largest eigenvalue of the 3x3 covariance of the (scaled) object points at or below which EPnP refuses
+ * (tools/pnp_flatness_sweep.py measures a library built with another value; the product is built with this one) */
+#ifndef PNP_FLATNESS_TAU
+#define PNP_FLATNESS_TAU 1e-11
+#endif
+
 int pnp_version(void);
 const char* pnp_last_error(void);
 
@@ -38,7 +51,10 @@ size_t pnp_workspace_bytes(int n, int iterations);
  * (eval_utils.py:27,35: OnePose passes 1000);
  * pose  [12] doubles (device): row-major 3x4 [R | t]; identity if the solve fails (:40-42);
  * inlier_mask [n] int32 (device): 1 for the inliers of the best hypothesis;
- * info  [4] int32 (device): {ok, number of inliers, index of the best hypothesis, its inlier count}. */
+ * info  [4] int32 (device): {ok, number of inliers, index of the best hypothesis, its inlier count}.
+ * NO MODEL, whichever stage says so, is one state: identity pose, inlier_mask all zero, info = {0, 0, -1, c}.  c is the
+ * largest inlier count any hypothesis reached: below 5 when no hypothesis made a model (0 for a flat object: every row is
+ * NaN); 5 or more when the best hypothesis had inliers and the final EPnP over them refused (they were flat). */
 int pnp_ransac_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n,
                     double reproj_error, int iterations, uint64_t seed, double* pose, int32_t* inlier_mask,
                     int32_t* info, void* workspace, size_t workspace_bytes, pnp_stream_t stream);
@@ -68,6 +84,10 @@ int pnp_score_hypotheses(const float* pts_3d, const float* pts_2d, const double*
 int pnp_select_best(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n,
                     double reproj_error, const double* hyp, const int32_t* counts, int iterations,
                     int32_t* inlier_mask, int32_t* inlier_idx, int32_t* info, pnp_stream_t stream);
+/* the last stage, on pnp_select_best's outputs: EPnP over the info[1] correspondences inlier_idx lists if info[0], pose
+ * [12] as pnp_ransac_epnp writes it; where it refuses, the n entries of inlier_mask and info are set to the NO MODEL state */
+int pnp_refit(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n,
+              const int32_t* inlier_idx, int32_t* inlier_mask, int32_t* info, double* pose, pnp_stream_t stream);
 
 #ifdef __cplusplus
 }

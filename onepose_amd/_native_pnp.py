@@ -22,6 +22,7 @@ SYMBOLS = {
     "pnp_hypotheses": (c_int, [F32, F32, _K, c_double, c_int, c_int, c_uint64, F64, STREAM]),
     "pnp_score_hypotheses": (c_int, [F32, F32, _K, c_double, c_int, c_double, F64, c_int, I32, STREAM]),
     "pnp_select_best": (c_int, [F32, F32, _K, c_double, c_int, c_double, F64, I32, c_int, I32, I32, I32, STREAM]),
+    "pnp_refit": (c_int, [F32, F32, _K, c_double, c_int, I32, I32, I32, F64, STREAM]),
 }
 # every symbol include/pnp_batch.h declares (the header include/pnp.h ends with): bound with the table above
 MORE_SYMBOLS = {

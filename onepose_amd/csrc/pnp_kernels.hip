@@ -107,6 +107,78 @@ __device__ __forceinline__ void eig3_desc(double (&S)[6], double (&w)[3], double
     }
 }
 
+// The frames U, Vs of the SVD of a 3x3 matrix M by one-sided Jacobi (Hestenes): the COLUMNS of A = M V are rotated against each other
+// until they are orthogonal; their lengths are then the singular values, each to its own relative accuracy -- which the eigenvalues
+// of M^T M do not have below 1e-8 of the largest.  Columns sorted by descending length (ties: lower index first).  U's first column
+// is a column of A, the second is orthogonalised against it once more, the third is their cross product with the orientation of
+// A's third column -- or, where that column is exactly zero (rank 2), the orientation that makes det(U Vs^T) = +1.
+__device__ __forceinline__ void svd3_frames(const double (&M)[3][3], double (&U)[3][3], double (&Vs)[3][3]) {
+    double A[3][3], V[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { A[i][j] = M[i][j]; V[i][j] = i == j ? 1.0 : 0.0; }
+    for (int sw = 0; sw < 12; ++sw) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double al = A[0][p] * A[0][p] + A[1][p] * A[1][p] + A[2][p] * A[2][p];
+                const double be = A[0][q] * A[0][q] + A[1][q] * A[1][q] + A[2][q] * A[2][q];
+                const double ga = A[0][p] * A[0][q] + A[1][p] * A[1][q] + A[2][p] * A[2][q];
+                if (ga * ga > 1e-30 * al * be) {               // false for a NaN
+                    const double zeta = (be - al) / (2.0 * ga);
+                    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+                    const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const double ap = A[i][p], aq = A[i][q], vp = V[i][p], vq = V[i][q];
+                        A[i][p] = c * ap - sn * aq; A[i][q] = sn * ap + c * aq;
+                        V[i][p] = c * vp - sn * vq; V[i][q] = sn * vp + c * vq;
+                    }
+                    rotated = true;
+                }
+            }
+        if (!rotated) break;
+    }
+    double len2[3], As[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) len2[c] = A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { As[i][k] = A[i][k]; Vs[i][k] = V[i][k]; }       // a NaN length ranks nowhere: kept in place
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) rank += (len2[j] > len2[c]) || (len2[j] == len2[c] && j < c);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (rank == k) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { As[i][k] = A[i][c]; Vs[i][k] = V[i][c]; }
+            }
+    }
+    const double n0 = sqrt(As[0][0] * As[0][0] + As[1][0] * As[1][0] + As[2][0] * As[2][0]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) U[i][0] = As[i][0] / n0;
+    const double d01 = U[0][0] * As[0][1] + U[1][0] * As[1][1] + U[2][0] * As[2][1];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) U[i][1] = As[i][1] - d01 * U[i][0];
+    const double n1 = sqrt(U[0][1] * U[0][1] + U[1][1] * U[1][1] + U[2][1] * U[2][1]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) U[i][1] /= n1;
+    const double w[3] = {U[1][0] * U[2][1] - U[2][0] * U[1][1], U[2][0] * U[0][1] - U[0][0] * U[2][1], U[0][0] * U[1][1] - U[1][0] * U[0][1]};
+    const double along = w[0] * As[0][2] + w[1] * As[1][2] + w[2] * As[2][2];
+    const double detv = Vs[0][0] * (Vs[1][1] * Vs[2][2] - Vs[1][2] * Vs[2][1]) - Vs[0][1] * (Vs[1][0] * Vs[2][2] - Vs[1][2] * Vs[2][0]) +
+                        Vs[0][2] * (Vs[1][0] * Vs[2][1] - Vs[1][1] * Vs[2][0]);
+    const double sgn = along < 0.0 ? -1.0 : (along > 0.0 ? 1.0 : (detv < 0.0 ? -1.0 : 1.0));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) U[i][2] = sgn * w[i];
+}
+
 // R = U V^T of the SVD of a 3x3 matrix (absolute orientation), reflection fixed as epnp.cpp does (third row negated)
 __device__ __forceinline__ void procrustes_rotation(const double (&M)[3][3], double (&R)[3][3]) {
     double B[6], w[3], Vs[3][3], U[3][3];
@@ -115,51 +187,28 @@ __device__ __forceinline__ void procrustes_rotation(const double (&M)[3][3], dou
 #pragma unroll
         for (int j = i; j < 3; ++j) B[tri<3>(i, j)] = M[0][i] * M[0][j] + M[1][i] * M[1][j] + M[2][i] * M[2][j];   // M^T M
     eig3_desc(B, w, Vs);
-    const double s0 = sqrt(fmax(w[0], 0.0));
+    const double s0 = sqrt(fmax(w[0], 0.0)), s2 = sqrt(fmax(w[2], 0.0));
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < 3; ++k) {
         const double sk = sqrt(fmax(w[k], 0.0));
 #pragma unroll
         for (int i = 0; i < 3; ++i) U[i][k] = (M[i][0] * Vs[0][k] + M[i][1] * Vs[1][k] + M[i][2] * Vs[2][k]) / sk;
     }
-    const double s2 = sqrt(fmax(w[2], 0.0));
-    if (s2 > 1e-12 * s0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) U[i][2] = (M[i][0] * Vs[0][2] + M[i][1] * Vs[1][2] + M[i][2] * Vs[2][2]) / s2;
-    } else {                                                   // rank 2: complete the frame
-        U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-        U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-        U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    }
-    // U = M V / sigma is orthonormal only to about eps (sigma_0 / sigma_k)^2: a minimal set with an outlier in it makes M
-    // ill-conditioned and R was a rotation to no better than 1e-7.  Where the Gram matrix of U is off by more than 1e-13,
-    // rebuild the frame from its best-conditioned column on (Gram-Schmidt, twice; third column = cross product with the
-    // orientation it had).  A well-conditioned U -- every all-inlier sample, the refit -- is left as it is.
+    // U = M V / sigma from the eigenpairs of M^T M is the cheap way and is kept, bit for bit, wherever it is good: every all-inlier
+    // sample and the refit of a solid object.  It squares the condition number: U is orthonormal only to about
+    // eps (sigma_0 / sigma_k)^2, and a sigma_k below 1e-8 sigma_0 is rounding noise.  A minimal set with an outlier in it, a thin slab
+    // (sigma_2 / sigma_0 = its eigenvalue ratio: 1e-10 at thickness 1e-5) or a rod make M that ill-conditioned.  The first version
+    // completed a rank-2 U by a cross product WITHOUT looking at det(Vs) -- a thin slab whose noise eigenvalue rounded to <= 0 then
+    // got a reflection, 'fixed' into a wrong rotation 16 .. 147 px off -- and rebuilt a non-orthonormal U by Gram-Schmidt, which is
+    // a rotation but not the nearest one (rods: 1e-5 between scale 1 and scale 1000).  Where the Gram matrix of U is off by more
+    // than 1e-13, or sigma_2 is not above 1e-12 sigma_0, both frames now come from the SVD of M itself.
     double dev = 0.0;
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = a; b < 3; ++b)
             dev = fmax(dev, fabs(U[0][a] * U[0][b] + U[1][a] * U[1][b] + U[2][a] * U[2][b] - (a == b ? 1.0 : 0.0)));
-    if (!(dev <= 1e-13)) {                                     // also taken for a NaN, which stays one
-        const double n0 = sqrt(U[0][0] * U[0][0] + U[1][0] * U[1][0] + U[2][0] * U[2][0]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) U[i][0] /= n0;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const double d = U[0][0] * U[0][1] + U[1][0] * U[1][1] + U[2][0] * U[2][1];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) U[i][1] -= d * U[i][0];
-            const double n1 = sqrt(U[0][1] * U[0][1] + U[1][1] * U[1][1] + U[2][1] * U[2][1]);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) U[i][1] /= n1;
-        }
-        const double w[3] = {U[1][0] * U[2][1] - U[2][0] * U[1][1], U[2][0] * U[0][1] - U[0][0] * U[2][1],
-                             U[0][0] * U[1][1] - U[1][0] * U[0][1]};
-        const double sgn = w[0] * U[0][2] + w[1] * U[1][2] + w[2] * U[2][2] < 0.0 ? -1.0 : 1.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) U[i][2] = sgn * w[i];
-    }
+    if (!(s2 > 1e-12 * s0 && dev <= 1e-13)) svd3_frames(M, U, Vs);              // also taken for a NaN, which stays one
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -221,6 +270,9 @@ __device__ __forceinline__ bool epnp_solve(int n_rt, Get get, const Cam& cam, do
     for (int k = 0; k < 6; ++k) cov[k] = red(cov[k]);
     double w3[3], EV[3][3];
     eig3_desc(cov, w3, EV);
+    // a flat set gets no pose (pnp.h): below PNP_FLATNESS_TAU the fourth control point sits on the first to rounding, CC is
+    // singular and what follows is NaN or a finite wrong pose as rounding has it.  False for a NaN and for an all-zero covariance.
+    if (!(w3[2] > PNP_FLATNESS_TAU * w3[0])) return false;
     double cws[4][3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) cws[0][k] = c0[k];
@@ -628,10 +680,11 @@ __global__ __launch_bounds__(1024) void gather_matches_kernel(const float* __res
     if (tid == 0) *count = run;
 }
 
-// EPnP over the listed correspondences (idx == nullptr: all f.frame[frame].n); info != nullptr: RANSAC refit (count from info[1])
+// EPnP over the listed correspondences (idx == nullptr: all f.frame[frame].n); info != nullptr: RANSAC refit (count from info[1]).
+// A refit that refuses leaves what a solve without a model leaves (pnp.h): the frame's mask row is zeroed again, all f.cap entries.
 __global__ __launch_bounds__(64) void refit_kernel(const float* __restrict__ p3_all, const float* __restrict__ p2_all, double scale,
                                                    Batch f, const int* __restrict__ idx_all, int32_t* __restrict__ info_all,
-                                                   double* __restrict__ pose_all) {
+                                                   int32_t* __restrict__ mask_all, double* __restrict__ pose_all) {
     const int lane = threadIdx.x, frame = blockIdx.y;
     const float* __restrict__ p3 = frame_of(p3_all, f.p3_stride, frame);
     const float* __restrict__ p2 = frame_of(p2_all, f.p2_stride, frame);
@@ -642,6 +695,7 @@ __global__ __launch_bounds__(64) void refit_kernel(const float* __restrict__ p3_
     bool ok = true;
     int n = f.frame[frame].n;
     if (info) { ok = info[0] != 0; n = info[1]; }
+    const bool had_model = info && ok;
     double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
     if (ok && n >= 4) {
         auto get = [&](int i, double (&pw)[3], double (&uv)[2]) {
@@ -662,7 +716,10 @@ __global__ __launch_bounds__(64) void refit_kernel(const float* __restrict__ p3_
             for (int c = 0; c < 3; ++c) pose[r * 4 + c] = R[r][c];
             pose[r * 4 + 3] = t[r];
         }
-        if (info && !ok) { info[0] = 0; info[1] = 0; }
+    }
+    if (had_model && !ok) {                                // the selection found a model and the refit refused it (ok: the same in every lane)
+        for (int i = lane; i < f.cap; i += 64) mask_all[(size_t)frame * f.cap + i] = 0;
+        if (lane == 0) { info[0] = 0; info[1] = 0; info[2] = -1; }
     }
 }
 
@@ -713,7 +770,7 @@ void launch_solve(const float* p3, const float* p2, const int* n_dev, const int*
                        w.counts);
     hipLaunchKernelGGL(best_kernel, dim3(1, b), dim3(1024), 0, s, p3, p2, n_dev, scale, f, thr2, iterations, w.hyp, w.counts, src, mask,
                        w.inl, info);
-    hipLaunchKernelGGL(refit_kernel, dim3(1, b), dim3(64), 0, s, p3, p2, scale, f, (const int*)w.inl, info, pose);
+    hipLaunchKernelGGL(refit_kernel, dim3(1, b), dim3(64), 0, s, p3, p2, scale, f, (const int*)w.inl, info, mask, pose);
 }
 
 // what the two batched entry points check alike; 0 or the code to return
@@ -749,7 +806,7 @@ Batch batch_of(const double* K_host, const int32_t* n, const uint64_t* seeds, in
 
 extern "C" {
 
-int pnp_version(void) { return 2; }
+int pnp_version(void) { return 3; }
 const char* pnp_last_error(void) { return g_err; }
 
 size_t pnp_workspace_bytes(int n, int iterations) {
@@ -837,7 +894,7 @@ int pnp_epnp(const float* pts_3d, const float* pts_2d, const double* K_host, dou
     if (n < 4) return fail(-1, "EPnP needs at least 4 correspondences (got %d)", n);
     if (!(scale > 0.0)) return fail(-1, "scale must be positive");
     hipLaunchKernelGGL(refit_kernel, dim3(1, 1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, scale,
-                       one_frame(K_host, n, 0), (const int*)nullptr, (int32_t*)nullptr, pose);
+                       one_frame(K_host, n, 0), (const int*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, pose);
     return check_launch(-1, "pnp_epnp");
 }
 
@@ -875,6 +932,16 @@ int pnp_select_best(const float* pts_3d, const float* pts_2d, const double* K_ho
                        scale, one_frame(K_host, n, 0), reproj_error * reproj_error, iterations, hyp, counts, (const int*)nullptr,
                        inlier_mask, inlier_idx, info);
     return check_launch(-1, "pnp_select_best");
+}
+
+int pnp_refit(const float* pts_3d, const float* pts_2d, const double* K_host, double scale, int n, const int32_t* inlier_idx,
+              int32_t* inlier_mask, int32_t* info, double* pose, pnp_stream_t stream) {
+    if (!pts_3d || !pts_2d || !K_host || !inlier_idx || !inlier_mask || !info || !pose) return fail(-1, "null argument");
+    if (n < MODEL_POINTS) return fail(-1, "solvePnPRansac with EPNP needs at least %d correspondences (got %d)", MODEL_POINTS, n);
+    if (!(scale > 0.0)) return fail(-1, "scale must be positive");
+    hipLaunchKernelGGL(refit_kernel, dim3(1, 1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), pts_3d, pts_2d, scale,
+                       one_frame(K_host, n, 0), (const int*)inlier_idx, info, inlier_mask, pose);
+    return check_launch(-1, "pnp_refit");
 }
 
 }  // extern "C"

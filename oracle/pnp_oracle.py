@@ -21,6 +21,11 @@ formulations), not against cv2 outputs:
   over the inliers of the best model.  Differences, deliberate and documented: the sample indices come from a
   counter-based hash (OpenCV's cv::RNG stream cannot be reproduced without OpenCV), and ALL `iterations` hypotheses are
   evaluated instead of stopping early at OpenCV's adaptive confidence bound (a superset of its search).
+  A third: a FLAT point set gets no pose.  Where the smallest eigenvalue of the points' covariance is not above FLATNESS_TAU times
+  the largest (a plane, a line, a point, a slab thinner than about 3e-6 of its extent) ``epnp`` returns NaNs -- it never raises --
+  and ``solve_pnp_ransac`` treats such a sample as no model.  OpenCV inverts the control-point matrix by SVD and continues; nobody
+  has compared the two on such input, because cv2 is not available here.  Without the guard this file raised LinAlgError on an
+  exact plane and returned finite wrong poses (up to 240 px) from eigenvalue ratios of 1e-14 and below (tools/pnp_flatness_sweep.py).
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ from . import ransac_common
 F64 = np.float64
 PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
 MODEL_POINTS = 5          # solvePnPRansac: minimal set for SOLVEPNP_EPNP
+FLATNESS_TAU = 1e-11      # include/pnp.h PNP_FLATNESS_TAU: smallest / largest covariance eigenvalue at or below which EPnP refuses
 
 
 # sample_indices(seed, hyp, n): the minimal set of hypothesis `hyp` (the same integer arithmetic runs on the GPU)
@@ -41,11 +47,13 @@ sample_indices = functools.partial(ransac_common.sample_indices, k=MODEL_POINTS)
 
 # ---- EPnP -----------------------------------------------------------------------------------------------
 def _control_points(pw):
-    """epnp.cpp choose_control_points: centroid + sqrt(eigenvalue / n) * principal directions."""
+    """epnp.cpp choose_control_points: centroid + sqrt(eigenvalue / n) * principal directions; None for a flat set."""
     n = len(pw)
     c0 = pw.mean(axis=0)
     d = pw - c0
     w, v = np.linalg.eigh(d.T @ d)            # ascending
+    if not w[0] > FLATNESS_TAU * w[2]:        # also a NaN and an all-zero covariance
+        return None
     cws = [c0]
     for i in (2, 1, 0):                       # descending eigenvalues, like the SVD OpenCV uses
         d = v[:, i]
@@ -154,6 +162,8 @@ def epnp(pw, uv, k):
     pw = np.asarray(pw, F64); uv = np.asarray(uv, F64); k = np.asarray(k, F64)
     fu, fv, uc, vc = k[0, 0], k[1, 1], k[0, 2], k[1, 2]
     cws = _control_points(pw)
+    if cws is None:
+        return np.full((3, 3), np.nan), np.full(3, np.nan)
     alphas = _barycentric(pw, cws)
     m = _fill_m(alphas, uv, fu, fv, uc, vc)
     w, vecs = np.linalg.eigh(m.T @ m)                                      # ascending: columns 0..3 span the null space

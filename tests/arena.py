@@ -210,7 +210,7 @@ NOT_CAPTURED = {
     **_stage("gatsspg_forward_frames", "gatsspg_gats_layer_frames"),
     **_stage("sg_forward", "sg_keypoint_encode", "sg_layer", "sg_attention", "sg_sinkhorn", "sg_match_tail"),
     **_stage("sg_forward_ragged", "sg_attention_ragged", "sg_sinkhorn_ragged", "sg_match_tail_ragged"),
-    **_stage("pnp_ransac_epnp", "pnp_epnp", "pnp_hypotheses", "pnp_score_hypotheses", "pnp_select_best"),
+    **_stage("pnp_ransac_epnp", "pnp_epnp", "pnp_hypotheses", "pnp_score_hypotheses", "pnp_select_best", "pnp_refit"),
     **_stage("spp_dense", "spp_dense_stage"),
     **_stage("flow_track", "flow_patch_sums", "flow_mismatch_sums"),
     "gatsspg_forward_profiled": "records events by design",

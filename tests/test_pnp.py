@@ -51,7 +51,7 @@ def test_every_declared_symbol_is_exported():
     lib = _native_pnp.load()
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pnp.h")).read(), flags=re.S)
     names = sorted(set(re.findall(r"\b(pnp_[a-z0-9_]+)\s*\(", text)))
-    assert set(names) == set(_native_pnp.SYMBOLS) and len(names) == 9
+    assert set(names) == set(_native_pnp.SYMBOLS) and len(names) == 10         # pnp_version() 3 added pnp_refit
     for n in names:
         assert hasattr(lib, n)
     assert lib.pnp_workspace_bytes(300, 10000) > 10000 * 12 * 8 and lib.pnp_workspace_bytes(0, 10) == 0

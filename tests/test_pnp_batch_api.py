@@ -33,7 +33,7 @@ def u64(*values):
 def test_batch_symbols_are_declared_exported_and_bound(lib):
     """The batched entry points are part of the ABI of include/pnp.h through include/pnp_batch.h, which it includes, and are bound from
     _native_pnp.MORE_SYMBOLS: tests/test_pnp.py and tests/test_abi_tables.py pin the functions pnp.h ITSELF declares, and SYMBOLS, to the
-    nine of pnp_version() 1."""
+    nine of pnp_version() 1 and pnp_refit of pnp_version() 3."""
     with open(os.path.join(ROOT, "include", "pnp.h")) as f:
         assert re.search(r'^#include "pnp_batch.h"', f.read(), flags=re.M)
     with open(os.path.join(ROOT, "include", "pnp_batch.h")) as f:
@@ -47,7 +47,7 @@ def test_batch_symbols_are_declared_exported_and_bound(lib):
         assert fn.restype is restype and len(fn.argtypes) == len(table)
         assert all(got is (ctypes.c_void_p if isinstance(entry, _binding.DevicePointer) else entry) for got, entry in zip(fn.argtypes, table))
     assert re.search(r"#define\s+PNP_MAX_ITEMS\s+32\b", text) and _native_pnp.MAX_ITEMS == 32
-    assert lib.pnp_version() == 2
+    assert lib.pnp_version() == 3                                          # 3: the flatness guard, pnp_refit and the one NO MODEL state
 
 
 def test_batch_table_mirrors_its_header():
